@@ -15,8 +15,8 @@ Multi-GPU (torchrun, one process per GPU):
     fixed, "weak"): value = all ranks' evals / max-over-ranks time.  One C2
     evaluation fits a GPU, so replicas are the highest-throughput way to
     spend N GPUs on the n=16384 metric.
-  * `sharded` leg (N > 1, after the replicas): ONE evaluation spread over
-    all N GPUs -- A block-column-sharded, RCCL panel broadcast + all-gather
+  * `sharded` leg (`--full`, N > 1, after the replicas): ONE evaluation
+    spread over all N GPUs -- A block-column-sharded, RCCL panel broadcast + all-gather
     per sweep step -- on the BASELINE config for that GPU
     count (C3 n=32768 at 4, C4 n=65536 at 8, C2-shaped n = 16384 N^(1/3)
     otherwise), with the weak-scaling efficiency of SURVEY §8d,
@@ -26,12 +26,25 @@ Multi-GPU (torchrun, one process per GPU):
   * `--mode sharded`: the sharded leg alone (also at N = 1, where it runs the
     RCCL code path with one rank).
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the result line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (milliseconds one timed step took)
+and the configuration.  `--full` adds everything else to that line: the
+roofline / phase / timeline figures of the timed steps, the `predict` and
+`r6_drop_in` legs, the CPU baseline and, at N > 1, the `sharded` leg.
+`--dump-outputs DIR` writes what the last timed step computed -- the
+gradients and the two statistics of the device `para_update` and the
+parameter vector after the Nadam step -- as DIR/<name>.npy (float64, rank 0).
+The data are seeded, so two builds run with the same arguments can be
+compared array for array.
+
 `--gpus N` is the world size.  Without a launcher (WORLD_SIZE unset) and
 N > 1, bench.py starts `torch.distributed.run --nproc-per-node N` on itself as
 a child process and exits with its status; under a launcher, WORLD_SIZE must
 equal N (else exit 2).  `--launch-check` only rendezvouses and max-reduces.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2]
+                       [--full] [--dump-outputs DIR]
                        [--mode auto|replicas|sharded] [--shard-config C4]
                        [--launch-check]
 """
@@ -284,6 +297,13 @@ def make_step(kernel, p, B, theta, std_y, ctx, y, X, Z, model=None):
     else:
         k.use_model(model, y, X, Z)
     state = {"it": 0}
+    # the optimizer clips the gradients in place: keep what the device returned
+    update = opt.update
+
+    def keep_gradients(it, parameters, gradients):
+        state["gradients"] = gradients.copy()
+        return update(it, parameters, gradients)
+    opt.update = keep_gradients
 
     # ACE_BENCH_DIAG=1: timing of deliberately broken diagnostic builds
     # (tools/build_variant.sh -DACE_DIAG_SKIP=...): a non-finite gradient
@@ -301,7 +321,19 @@ def make_step(kernel, p, B, theta, std_y, ctx, y, X, Z, model=None):
             k.parameters = theta0.copy()
             return [float("nan"), float("nan")]
     step.kernel_object = k
+    step.state = state
     return step, model
+
+
+def dump_outputs(path, step, stats):
+    """--dump-outputs: what the last timed step handed back, as float64
+    <name>.npy under `path` (a few hundred bytes each)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"stats": stats, "gradients": step.state["gradients"],
+              "parameters": step.kernel_object.parameters}
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def timed_steps(dist, step, steps, warmup, model, profile=True):
@@ -381,7 +413,7 @@ def r6_leg(kernel, p, B, theta, std_y, ctx, y, X, Z, iters=5, warmup=2):
     return out
 
 
-def run_sharded(dist, rank, world, ctx, steps, warmup, name=None, proxy=False):
+def run_sharded(dist, rank, world, ctx, steps, warmup, name=None, proxy=False, dump=None):
     """One evaluation over all ranks (block-column-sharded model, RCCL).
     proxy: rank `rank` of `world` alone in this process with the
     -DACE_DIAG_SHARD_PROXY library (tools/build_variant.sh): collectives are
@@ -399,6 +431,8 @@ def run_sharded(dist, rank, world, ctx, steps, warmup, name=None, proxy=False):
                             sharded=True)
     step, model = make_step(kernel, p, B, theta, std_y, ctx, y, X, Z, model=model)
     dt, stats = timed_steps(dist, step, steps, warmup, model)
+    if dump and rank == 0:
+        dump_outputs(dump, step, stats)
     upd_ms, upd_n, upd_work = model.kernel_time(0)
     asm_ms = model.kernel_time(1)[0]
     grad_ms = model.kernel_time(2)[0]
@@ -461,7 +495,12 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="C2")
-    ap.add_argument("--mode", default="auto", choices=["auto", "replicas", "sharded"])
+    ap.add_argument("--full", action="store_true",
+                    help="also: roofline / phase / timeline figures, the predict and R6 drop-in "
+                         "legs, the CPU baseline and (N > 1) the sharded leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--mode",default="auto", choices=["auto", "replicas", "sharded"])
     ap.add_argument("--shard-config", default=None)
     ap.add_argument("--shard-steps", type=int, default=2)
     ap.add_argument("--shard-timeout", type=float, default=240.0)
@@ -475,6 +514,8 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="only rendezvous and max-reduce over the ranks (launcher test)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # --gpus N is the world size: a bare `bench.py --gpus N` launches N ranks
     # itself; under a launcher the two must agree
@@ -498,11 +539,13 @@ def main():
         if a.proxy:
             os.environ["ACE_BENCH_DIAG"] = "1"  # the proxy's gradients are not finite
             pr, pg = (int(x) for x in a.proxy.split("/"))
-            sh = run_sharded(None, pr, pg, ctx, a.steps, a.warmup, a.shard_config, proxy=True)
+            sh = run_sharded(None, pr, pg, ctx, a.steps, a.warmup, a.shard_config, proxy=True,
+                             dump=a.dump_outputs if pr == 0 else None)
             sh["proxy"] = {"rank": pr, "world": pg,
                            "note": "one rank alone, collectives replaced by same-size device copies"}
         else:
-            sh = run_sharded(dist, rank, world, ctx, a.steps, a.warmup, a.shard_config)
+            sh = run_sharded(dist, rank, world, ctx, a.steps, a.warmup, a.shard_config,
+                             dump=a.dump_outputs)
         if rank == 0:
             line = {"metric": METRIC, "value": sh["evals_per_s"], "unit": "evals/s",
                     "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -522,16 +565,19 @@ def main():
     y, X, Z, theta, std_y = make_problem(n, p, B, seed=1000 + rank)
     step, model = make_step(kernel, p, B, theta, std_y, ctx, y, X, Z)
     dt_max, stats = timed_steps(dist, step, a.steps, a.warmup, model, not a.no_profile)
-    upd_ms, upd_n, upd_work = model.kernel_time(0)
-    asm_ms, _, asm_work = model.kernel_time(1)
-    grad_ms, _, grad_work = model.kernel_time(2)
-    sweep_ms, sweep_n, sweep_work = model.kernel_time(3)
-    lead_ms, lead_n, _ = model.kernel_time(4)
-    span_ms, span_n, _ = model.kernel_time(5)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step, stats)
+    if a.full:
+        upd_ms, upd_n, upd_work = model.kernel_time(0)
+        asm_ms, _, asm_work = model.kernel_time(1)
+        grad_ms, _, grad_work = model.kernel_time(2)
+        sweep_ms, sweep_n, sweep_work = model.kernel_time(3)
+        lead_ms, lead_n, _ = model.kernel_time(4)
+        span_ms, span_n, _ = model.kernel_time(5)
     model.profile(False)
-    pred = predict_leg(step.kernel_object, model, p, B) if rank == 0 else None
+    pred = predict_leg(step.kernel_object, model, p, B) if a.full and rank == 0 else None
     r6 = None
-    if rank == 0 and world == 1 and not a.no_r6:
+    if a.full and rank == 0 and world == 1 and not a.no_r6:
         try:
             r6 = r6_leg(kernel, p, B, theta, std_y, ctx, y, X, Z)
             r6["vs_fused_ms_ratio"] = r6["ms_per_eval"] / (dt_max / a.steps * 1e3)
@@ -540,22 +586,8 @@ def main():
 
     line = None
     if rank == 0:
-        traffic, traffic_src = pmc_traffic("k_update_multi_bulk", a.config)
-        if traffic is None:  # a summary from before the multi-panel kernel
-            traffic, traffic_src = pmc_traffic("k_update_pair_bulk", a.config)
-        rp_ms, rp_src = rocprof_bulk_avg(a.config)
-        asm_rp_ms, asm_rp_src = rocprof_assembly_ms(a.config)
-        naug = -(-n // 256) * 256 + 128
-        nt = naug // 128
-        # sweep steps per bulk launch, from the launch count (steps / groups)
-        nsteps = -(-n // 256)
-        zst = max(1, round(nsteps / (upd_n / a.steps))) if upd_n else 4
-        # compulsory bytes of one bulk launch: every lower 128-tile of A read
-        # and written once, plus the Z steps' W and Pn panels
-        alg_bytes = nt * (nt + 1) // 2 * 128 * 128 * 8 * 2 + 2 * zst * naug * 256 * 8
         evals = a.steps * world
         value = evals / dt_max
-        achieved = upd_work / (upd_ms * 1e-3) / 1e12 if upd_ms > 0 else None
         line = {
             "metric": METRIC,
             "value": value,
@@ -576,6 +608,24 @@ def main():
                 "n": n, "p": p, "B": B, "kernel": kernel,
                 "parallelism": "single" if world == 1 else f"replicas x{world}",
             },
+            "last_stats": [float(stats[0]), float(stats[1])],
+        }
+    if line is not None and a.full:
+        traffic, traffic_src = pmc_traffic("k_update_multi_bulk", a.config)
+        if traffic is None:  # a summary from before the multi-panel kernel
+            traffic, traffic_src = pmc_traffic("k_update_pair_bulk", a.config)
+        rp_ms, rp_src = rocprof_bulk_avg(a.config)
+        asm_rp_ms, asm_rp_src = rocprof_assembly_ms(a.config)
+        naug = -(-n // 256) * 256 + 128
+        nt = naug // 128
+        # sweep steps per bulk launch, from the launch count (steps / groups)
+        nsteps = -(-n // 256)
+        zst = max(1, round(nsteps / (upd_n / a.steps))) if upd_n else 4
+        # compulsory bytes of one bulk launch: every lower 128-tile of A read
+        # and written once, plus the Z steps' W and Pn panels
+        alg_bytes = nt * (nt + 1) // 2 * 128 * 128 * 8 * 2 + 2 * zst * naug * 256 * 8
+        achieved = upd_work / (upd_ms * 1e-3) / 1e12 if upd_ms > 0 else None
+        line.update({
             "roofline": {
                 "kernel": (f"k_update_multi (bulk sweep update, {zst} Gauss-Jordan steps per launch, "
                            f"K = {256 * zst} per 128x128 tile, v_mfma_f64_16x16x4_f64)"),
@@ -622,15 +672,14 @@ def main():
                 "assembly_rocprof_source": asm_rp_src,
                 "gradient": grad_work / (grad_ms * 1e-3) / 1e12 if grad_ms else None},
             "pair_kernels_hbm_gbs": pair_hbm_gbs(asm_ms / a.steps, grad_ms / a.steps, a.config),
-            "last_stats": [float(stats[0]), float(stats[1])],
             "predict": pred,
             "r6_drop_in": r6,
-        }
+        })
         if world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.config)
 
     failed = False
-    if world > 1 and a.mode == "auto":
+    if a.full and world > 1 and a.mode == "auto":
         model.close()
 
         def leg():

@@ -39,6 +39,18 @@ def test_bench_world_size_mismatch_fails():
     assert "WORLD_SIZE=3" in r.stderr
 
 
+def test_bench_options_parse_and_steps_must_be_positive(tmp_path):
+    """--full and --dump-outputs are accepted; --steps 0 (no timed step, no
+    ms_per_step) is refused before anything runs."""
+    base = [sys.executable, BENCH, "--gpus", "1", "--full", "--dump-outputs", str(tmp_path / "d")]
+    r = subprocess.run(base + ["--launch-check"], env=_env(), capture_output=True, text=True,
+                       timeout=120, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run(base + ["--steps", "0"], env=_env(), capture_output=True, text=True,
+                       timeout=120, cwd=ROOT)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_bench_gpus1_runs_in_process():
     """--gpus 1 keeps the single-process path (no launcher, no process group)."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--launch-check"], env=_env(),

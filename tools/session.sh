@@ -10,8 +10,8 @@
 #                  measured-error log (ACE_ERROR_LOG -> errors.jsonl)
 #   tests:EXPR     the GPU tests selected by -k EXPR
 #   smoke          __graft_entry__.smoke()
-#   bench          bench.py (C2, CPU baseline included)
-#   bench_c1       bench.py --config C1 (no CPU baseline)
+#   bench          bench.py --full (C2, every leg, CPU baseline included)
+#   bench_c1       bench.py --full --config C1 (no CPU baseline)
 #   prof           rocprofv3 --kernel-trace --stats of the C2 bench + the
 #                  bulk-launch split (tools/kernel_stats_split.py)
 #   pmc            the FETCH_SIZE / WRITE_SIZE passes (tools/run_pmc.sh, CFG=C1|C2)
@@ -50,10 +50,10 @@ for step in "$@"; do
     smoke)
       run 200 $out/smoke.log python -c "import __graft_entry__ as g; g.smoke()"; cat $out/smoke.log ;;
     bench)
-      runj 400 $out/bench.json python bench.py --steps 10 --warmup 2
+      runj 400 $out/bench.json python bench.py --full --steps 10 --warmup 2
       cut -c1-400 $out/bench.json ;;
     bench_c1)
-      runj 300 $out/bench_c1.json python bench.py --config C1 --steps 20 --warmup 3 --no-cpu-baseline
+      runj 300 $out/bench_c1.json python bench.py --full --config C1 --steps 20 --warmup 3 --no-cpu-baseline
       cut -c1-300 $out/bench_c1.json ;;
     prof)
       bash tools/run_prof.sh $tag/prof --steps 5 --warmup 1 > /dev/null || exit 1
