@@ -21,6 +21,7 @@ KIND = {"SE": ACE_KERNEL_SE, "Matern32": ACE_KERNEL_MATERN32}
 
 _D = ctypes.POINTER(ctypes.c_double)
 _I64 = ctypes.c_int64
+_I32 = ctypes.POINTER(ctypes.c_int32)
 _vp = ctypes.c_void_p
 
 # name -> (restype, argtypes); must match include/ace_hip.h exactly
@@ -92,6 +93,13 @@ SIGNATURES = {
     "ace_model_predict_marginal": (ctypes.c_int, [_vp, _D, _I64, _D, _D, _D, ctypes.c_double,
                                                   ctypes.c_double, ctypes.c_int, _D, _D, _D,
                                                   _D]),
+    "ace_model_predict_marginal_groups": (ctypes.c_int, [_vp, _D, _I64, _D, _D, ctypes.c_double,
+                                                         ctypes.c_double, ctypes.c_int, _I32, _D,
+                                                         _D, _D, _D, ctypes.POINTER(_I64), _D]),
+    "ace_robust_levels": (ctypes.c_int, [_I64, _D, ctypes.c_int, _D, _I32]),
+    "ace_model_robust_treatment": (ctypes.c_int, [_vp, _D, _I64, _D, _D, _D, ctypes.c_double,
+                                                  ctypes.c_double, ctypes.c_int, _D, _D, _D, _D,
+                                                  _I32, _D, ctypes.POINTER(_I64)]),
     "ace_model_profile": (ctypes.c_int, [_vp, ctypes.c_int]),
     "ace_model_kernel_time": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                              ctypes.POINTER(_I64),

@@ -307,6 +307,28 @@ inline void finish_pred(int64_t nx, const double *a, const double *kd, const dou
   }
 }
 
+// ATE / ATT / ATU of pred_marginal_cpp (src/pred_cpp.cpp:89-126) from the sums
+// over the nx test points: sy = sum of map, syz = sum of map Z_x, sz = sum of
+// Z_x, post[j] the three posterior quadratic forms.  avg (12).
+inline void marginal_averages(int64_t nx, double std_y, double sy, double syz, double sz,
+                              const double *post, double *avg) {
+  const double ate = sy / (double)nx;
+  const double ate_sd = std_y * std::sqrt(post[0]) / (double)nx;
+  const unsigned int ntx = (unsigned int)sz;  // unsigned int in the reference
+  const double att = syz / ntx;
+  const double att_sd = std_y * std::sqrt(post[1]) / ntx;
+  const unsigned int nux = (unsigned int)nx - ntx;
+  const double atu = (ate * nx - att * ntx) / nux;
+  const double atu_sd = std_y * std::sqrt(post[2]) / nux;
+  const double m3[3] = {ate, att, atu}, s3[3] = {ate_sd, att_sd, atu_sd};
+  for (int j = 0; j < 3; ++j) {
+    avg[4 * j + 0] = m3[j];
+    avg[4 * j + 1] = m3[j] - 1.96 * s3[j];
+    avg[4 * j + 2] = m3[j] + 1.96 * s3[j];
+    avg[4 * j + 3] = std::pow(s3[j], 2);
+  }
+}
+
 // Host tail of pred_marginal_cpp (src/pred_cpp.cpp:69-126): a, kd, qd of the
 // marginal kernels; with zx != NULL also ATE / ATT / ATU from the posterior
 // quadratic forms post[j] = w_j^T (Km_xx - tmp Km_xX^T) w_j for w = 1, Z_x,
@@ -331,21 +353,7 @@ inline void finish_marginal(int64_t nx, const double *a, const double *kd, const
     syz += yx[(size_t)r] * zx[r];
     sz += zx[r];
   }
-  const double ate = sy / (double)nx;
-  const double ate_sd = std_y * std::sqrt(post[0]) / (double)nx;
-  const unsigned int ntx = (unsigned int)sz;  // unsigned int in the reference
-  const double att = syz / ntx;
-  const double att_sd = std_y * std::sqrt(post[1]) / ntx;
-  const unsigned int nux = (unsigned int)nx - ntx;
-  const double atu = (ate * nx - att * ntx) / nux;
-  const double atu_sd = std_y * std::sqrt(post[2]) / nux;
-  const double m3[3] = {ate, att, atu}, s3[3] = {ate_sd, att_sd, atu_sd};
-  for (int j = 0; j < 3; ++j) {
-    avg[4 * j + 0] = m3[j];
-    avg[4 * j + 1] = m3[j] - 1.96 * s3[j];
-    avg[4 * j + 2] = m3[j] + 1.96 * s3[j];
-    avg[4 * j + 3] = std::pow(s3[j], 2);
-  }
+  marginal_averages(nx, std_y, sy, syz, sz, post, avg);
 }
 
 }  // namespace ace_host

@@ -235,4 +235,34 @@ int ace_normalize_test(int64_t n, int px, int pz, double *X, double *Z, const do
   return ACE_OK;
 }
 
+// robust_treatment's discard levels (R/robust_treatment.R:83-84, 94):
+// quantile.list = seq(0, 1, 1 / n.steps), discard.steps = R's default
+// (type 7) quantile of var, idx[, t] = var <= discard.steps[t]
+int ace_robust_levels(int64_t nx, const double *var, int n_steps, double *thresholds,
+                      int32_t *level) {
+  if (nx < 1 || !var || !thresholds || !level || n_steps < 1 || n_steps > 31) return ACE_ERR_ARG;
+  if (!all_finite(nx, var)) return ACE_ERR_NONFINITE;
+  std::vector<double> x(var, var + nx);
+  std::sort(x.begin(), x.end());
+  const double by = 1.0 / n_steps;
+  for (int t = 0; t <= n_steps; ++t) {
+    const double p = std::min(t * by, 1.0);
+    const double index = 1 + (double)(nx - 1) * p;
+    const double lo = std::floor(index), hi = std::ceil(index);
+    double q = x[(size_t)lo - 1];
+    const double xh = x[(size_t)hi - 1];
+    if (index > lo && xh != q) {
+      const double h = index - lo;
+      q = (1 - h) * q + h * xh;
+    }
+    thresholds[t] = q;
+  }
+  for (int64_t i = 0; i < nx; ++i) {
+    int t = 0;
+    while (t < n_steps && !(var[i] <= thresholds[t])) ++t;
+    level[i] = t;
+  }
+  return ACE_OK;
+}
+
 }  // extern "C"

@@ -103,6 +103,16 @@ bool cross_mm_lds_ok(int PM, int B, int kind);
 // mode 2 without a cube on the MFMA r2 expansion (k_cross_mm): R.n x C.n, ld
 hipError_t launch_cross_mm(int kind, int PM, PairSide R, PairSide C, int B, int ZS, TabView tab,
                            int b0, int b1, double *out, int64_t ld, hipStream_t st);
+// Grouped test-kernel sums (k_group_mm): R (S.n x G, ld S.n) = Km E for the
+// marginal kernel Km of slices [b0, b1) on the points S and the indicator
+// E[c][h] = (label[c] == h), labels in [-1, G), 1 <= G <= 64; Km is never
+// stored.  part: group_sums_parts(S.n) * S.n * G doubles of partial sums,
+// reduced in a fixed order (bitwise reproducible).  The VALU form runs when
+// the MFMA kernel's staging does not fit in LDS or ACE_PAIRS=valu is set.
+int group_sums_parts(int64_t n);
+hipError_t launch_group_sums(int kind, int PM, PairSide S, int B, int ZS, TabView tab, int b0,
+                             int b1, const int *label, int G, double *part, double *R,
+                             hipStream_t st);
 hipError_t launch_grad_mm(int kind, int PM, PairSide S, int B, int ZS, TabView tab,
                           const double *A, int64_t ld, double sA, const double *alpha,
                           double *gpart, hipStream_t st, const Tile *tiles, int64_t ntiles, int G,
@@ -380,6 +390,15 @@ hipError_t launch_gemv_t(const double *M, int64_t ld, int64_t m, int64_t k,
 hipError_t launch_gemm_nn(int64_t m, int64_t n, int64_t k, const double *A,
                           int64_t lda, const double *B, int64_t ldb, double *C,
                           int64_t ldc, hipStream_t st);
+// C (m x n) = A^T B (+ C when accumulate) for A (k x m) and B (k x n),
+// col-major, fp64 MFMA, k split over workgroups and summed in a fixed order;
+// work: gemm_tn_work(m, n, k) doubles.
+int64_t gemm_tn_work(int64_t m, int64_t n, int64_t k);
+hipError_t launch_gemm_tn(int64_t m, int64_t n, int64_t k, const double *A, int64_t lda,
+                          const double *B, int64_t ldb, double *C, int64_t ldc, bool accumulate,
+                          double *work, hipStream_t st);
+// E (nx x G, ld nx): E[i][g] = (label[i] == g)
+hipError_t launch_label_matrix(const int *label, int64_t nx, int G, double *E, hipStream_t st);
 // Copies scale * A (lower) into a full symmetric n x n matrix (ld_out).
 hipError_t launch_sym_from_lower(const double *A, int64_t ld, int64_t n,
                                  double scale, double *out, int64_t ld_out,

@@ -180,10 +180,14 @@ __global__ __launch_bounds__(256) void k_grad(PairSide S, int B, int ZS, TabView
   __shared__ double sR[(KIND == 1 && !CUBE) ? NM : 1][256];  // r2_{b+1} per pair
   const int64_t t = blockIdx.x;
   int64_t I, J;
-  if (tiles) {  // sharded: the rank's own lower tiles
+  if (tiles) {  // the rank's own lower tiles, or the model's XCD-dealt order
     const Tile tt = tiles[t];
     I = tt.I;
     J = tt.J;
+    if (I < 0) {  // padding of an XCD-dealt list: an all-zero partial row
+      for (int64_t e = threadIdx.x; e < ldg; e += 256) gpart[t * ldg + e] = 0.0;
+      return;
+    }
     A += (lcol(J * AT, G) - J * AT) * ld;
   } else {
     I = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
@@ -409,10 +413,14 @@ __global__ __launch_bounds__(256) void k_grad2(PairSide S, int B, int ZS, TabVie
   __shared__ double sF[KIND == 1 ? NM : 1][256];      // Matern: 1 + sqrt3 t of slice b+1
   const int64_t t = blockIdx.x;
   int64_t I, J;
-  if (tiles) {  // sharded: the rank's own lower tiles
+  if (tiles) {  // the rank's own lower tiles, or the model's XCD-dealt order
     const Tile tt = tiles[t];
     I = tt.I;
     J = tt.J;
+    if (I < 0) {  // padding of an XCD-dealt list: an all-zero partial row
+      for (int64_t e = threadIdx.x; e < ldg; e += 256) gpart[t * ldg + e] = 0.0;
+      return;
+    }
     A += (lcol(J * AT, G) - J * AT) * ld;
   } else {
     I = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);

@@ -1635,6 +1635,296 @@ hipError_t launch_cross_mm(int kind, int PM, PairSide R, PairSide C, int B, int 
   }
 }
 
+// ---------------------------------------------------------------------------
+// Grouped test-kernel sums (robust_treatment's posterior block sums):
+// R = Km_xx E (n x G) for the points S, slices [b0, b1) and the group
+// indicator E[c][h] = (label[c] == h), labels in [-1, G), G <= 64.  Km_xx is
+// never stored: a workgroup owns the 64-row strip I and the column tiles
+// [js tpw, (js + 1) tpw); every tile is evaluated as by k_cross_mm with both
+// sides taken from S (the full square with the cross arithmetic), and the
+// lane's fragment kf[cb][v] = K[16 w + lr][16 cb + 4 v + lk] is, as it
+// stands, the first operand (index lr, k = lk) of a second
+// v_mfma_f64_16x16x4_f64 against E[16 cb + 4 v + lk][16 hb + lr], built from
+// the tile's labels in LDS.  The G / 16 result fragments are accumulated over
+// the workgroup's tiles: D register i of lane (lr, lk) is
+// R[16 w + lk + 4 i][16 hb + lr].  Column ranges write separate partial R's
+// (part + js ldp G), summed in ascending js by k_sum_parts: no atomics, the
+// same bits on every call.  Columns past S.n carry label -1.
+// ---------------------------------------------------------------------------
+template <int PM, int KIND>
+__global__ __launch_bounds__(256, 2) void k_group_mm(PairSide S, int B, int ZS, TabView tab, int b0,
+                                                    int b1, const int *__restrict__ label, int G,
+                                                    int tpw, double *__restrict__ part,
+                                                    int64_t ldp) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  constexpr int XP = xj_pitch(PM);
+  const int64_t I = blockIdx.y, js = blockIdx.x;
+  const int64_t nt = (S.n + AT - 1) / AT;
+  const int64_t J0 = js * tpw, J1 = (J0 + tpw < nt) ? J0 + tpw : nt;
+  const int64_t R0 = I * AT;
+  const int HB = (G + 15) / 16;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+  const MmLayout o = mm_layout(PM, B, KIND, false);
+  double *const E = lds + o.etab, *const XJ = lds + o.xj, *const Zc = lds + o.z + 64,
+               *const LZc = lds + o.lz + 64, *const Nc = lds + o.nc, *const Nr = lds + o.nr,
+               *const W = lds + o.w, *const XI = lds + o.total;
+  int *const Lab = (int *)(XI + 64 * XP);
+  // the strip's row side, the weights and the tables: staged once
+  for (int e = tid; e < 64 * PM; e += 256) {
+    const int c = e / PM, i = e - c * PM;
+    XI[c * XP + i] = (R0 + c < S.n) ? S.X[(R0 + c) * PM + i] : 0.0;
+  }
+  if (tid < 64) {  // slice 0: z = 1, log|z| = 0
+    Zc[tid - 64] = 1.0;
+    if (KIND == 0) LZc[tid - 64] = 0.0;
+    if (ACE_ASM_EXP == 2) E[tid] = kExp2Tab64[tid];
+    else if (tid < 32) E[tid] = kExp2Tab[tid];
+  }
+  for (int e = tid; e < B * PM; e += 256) W[e] = tab.wk[e];
+  __syncthreads();
+  for (int e = tid; e < B * 64; e += 256) {
+    const int sl = e >> 6, pt = e & 63;
+    const double *wv = W + sl * PM;
+    double s = 0.0;
+#pragma unroll 4
+    for (int i = 0; i < PM; ++i) {
+      const double x = XI[pt * XP + i];
+      s = fma(x * x, wv[i], s);
+    }
+    Nr[e] = s;
+  }
+  const int rl = 16 * w + lr;
+  const int64_t r = R0 + rl;
+  const bool rok = r < S.n;
+  RowX<PM> xr;
+  xr.load(XI + rl * XP, lk);
+  d4 racc[4];
+#pragma unroll
+  for (int hb = 0; hb < 4; ++hb) racc[hb] = d4{0.0, 0.0, 0.0, 0.0};
+  for (int64_t J = J0; J < J1; ++J) {
+    const int64_t C0 = J * AT;
+    if (J > J0) __syncthreads();  // the previous tile's readers are done
+    for (int e = tid; e < 64 * PM; e += 256) {
+      const int c = e / PM, i = e - c * PM;
+      XJ[c * XP + i] = (C0 + c < S.n) ? S.X[(C0 + c) * PM + i] : 0.0;
+    }
+    for (int e = tid; e < (B - 1) * 64; e += 256) {
+      const int bb = e >> 6, c = e & 63;
+      const bool ok = C0 + c < S.n;
+      Zc[e] = ok ? S.Z[(C0 + c) * ZS + bb] : 0.0;
+      if (KIND == 0) LZc[e] = ok ? S.LZ[(C0 + c) * ZS + bb] : 0.0;
+    }
+    if (tid < 64) Lab[tid] = (C0 + tid < S.n) ? label[C0 + tid] : -1;
+    __syncthreads();
+    for (int e = tid; e < B * 64; e += 256) {
+      const int sl = e >> 6, pt = e & 63;
+      const double *wv = W + sl * PM;
+      double s = 0.0;
+#pragma unroll 4
+      for (int i = 0; i < PM; ++i) {
+        const double x = XJ[pt * XP + i];
+        s = fma(x * x, wv[i], s);
+      }
+      Nc[e] = s;
+    }
+    __syncthreads();
+    double kf[4][4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) kf[cb][v] = 0.0;
+    for (int b = b0; b < b1; ++b) {
+      double zr = 1.0, lzr = 0.0;
+      if (b > 0) {
+        zr = rok ? S.Z[r * ZS + b - 1] : 0.0;
+        if (KIND == 0) lzr = rok ? S.LZ[r * ZS + b - 1] : 0.0;
+      }
+      d4 acc[4];
+      gemm1_mm<XP, 4>(XJ, xr, W + b * PM, lr, lk, acc, 0);
+      const double sr = Nr[b * 64 + rl];
+      const double *nc = Nc + b * 64;
+      const double *zcol = Zc + (b - 1) * 64, *lzcol = LZc + (b - 1) * 64;
+      const double lam = tab.lam[b];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int cl = 16 * cb + lk + 4 * v;
+          constexpr double R2MIN = KIND == 1 ? 1e-300 : 0.0;
+          const double r2 = fmax(fma(-2.0, acc[cb][v], sr + nc[cl]), R2MIN);
+          const double zc = zcol[cl];
+          const double lzc = KIND == 0 ? lzcol[cl] : 0.0;
+          kf[cb][v] += kval_nb<KIND>(r2, lam, zr, zc, lzr, lzc, E);
+          MM_PAIR_FENCE(cb, v);
+        }
+    }
+    // GEMM2: racc[hb] += K[rows][16 cb + 4 v + lk] E[16 cb + 4 v + lk][16 hb + lr]
+    int lb[4][4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) lb[cb][v] = Lab[16 * cb + 4 * v + lk];
+#pragma unroll
+    for (int hb = 0; hb < 4; ++hb)
+      if (hb < HB) {
+        const int h = 16 * hb + lr;
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+          for (int v = 0; v < 4; ++v)
+            racc[hb] = __builtin_amdgcn_mfma_f64_16x16x4f64(kf[cb][v], lb[cb][v] == h ? 1.0 : 0.0,
+                                                            racc[hb], 0, 0, 0);
+      }
+  }
+  double *const P = part + js * ldp * G;
+#pragma unroll
+  for (int hb = 0; hb < 4; ++hb) {
+    const int h = 16 * hb + lr;
+    if (hb < HB && h < G) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int64_t row = R0 + 16 * w + lk + 4 * i;
+        if (row < S.n) P[row + (int64_t)h * ldp] = racc[hb][i];
+      }
+    }
+  }
+}
+
+// The same reduction on the VALU alone (the staging of k_group_mm does not
+// fit in LDS, or ACE_PAIRS=valu): one thread per row of the strip, r2 as the
+// plain weighted sum of squared differences, the row's G sums in LDS.
+template <int KIND>
+__global__ __launch_bounds__(64) void k_group_valu(PairSide S, int PM, int B, int ZS, TabView tab,
+                                                  int b0, int b1, const int *__restrict__ label,
+                                                  int G, int tpw, double *__restrict__ part,
+                                                  int64_t ldp) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  double *const E = lds, *const sR = lds + 64;
+  const int tid = threadIdx.x;
+  const int64_t js = blockIdx.x, r = (int64_t)blockIdx.y * AT + tid;
+  const int64_t c0 = js * tpw * AT;
+  const int64_t c1 = (c0 + (int64_t)tpw * AT < S.n) ? c0 + (int64_t)tpw * AT : S.n;
+  if (ACE_ASM_EXP == 2) E[tid] = kExp2Tab64[tid];
+  else if (tid < 32) E[tid] = kExp2Tab[tid];
+  for (int h = 0; h < G; ++h) sR[tid * G + h] = 0.0;
+  __syncthreads();
+  if (r >= S.n) return;
+  const double *xr = S.X + r * PM;
+  for (int64_t c = c0; c < c1; ++c) {
+    const int lab = label[c];
+    if (lab < 0) continue;
+    const double *xc = S.X + c * PM;
+    double k = 0.0;
+    for (int b = b0; b < b1; ++b) {
+      const double *wv = tab.wk + b * PM;
+      double r2 = 0.0;
+      for (int i = 0; i < PM; ++i) {
+        const double d = xr[i] - xc[i];
+        r2 = fma(d * d, wv[i], r2);
+      }
+      if (KIND == 1) r2 = fmax(r2, 1e-300);
+      double zr = 1.0, zc = 1.0, lzr = 0.0, lzc = 0.0;
+      if (b > 0) {
+        zr = S.Z[r * ZS + b - 1];
+        zc = S.Z[c * ZS + b - 1];
+        if (KIND == 0) {
+          lzr = S.LZ[r * ZS + b - 1];
+          lzc = S.LZ[c * ZS + b - 1];
+        }
+      }
+      k += kval_nb<KIND>(r2, tab.lam[b], zr, zc, lzr, lzc, E);
+    }
+    sR[tid * G + lab] += k;
+  }
+  double *const P = part + js * ldp * G;
+  for (int h = 0; h < G; ++h) P[r + (int64_t)h * ldp] = sR[tid * G + h];
+}
+
+// out[e] = sum over s < nparts of part[s count + e], s ascending
+__global__ __launch_bounds__(256) void k_sum_parts(const double *__restrict__ part, int nparts,
+                                                   int64_t count, double *__restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= count) return;
+  double s = part[e];
+  for (int p = 1; p < nparts; ++p) s += part[(int64_t)p * count + e];
+  out[e] = s;
+}
+
+// k_group_mm's LDS: k_cross_mm's plus the tile's 64 labels
+static size_t group_mm_lds(int PM, int B, int kind) {
+  return cross_mm_lds(PM, B, kind) + 64 * sizeof(int);
+}
+
+// column tiles per workgroup: about 1024 workgroups over the strips
+static int group_tpw(int64_t n) {
+  const int64_t nt = (n + AT - 1) / AT;
+  const int64_t want = (1024 + nt - 1) / nt;  // column ranges per strip
+  const int64_t ns = want < nt ? want : nt;
+  return (int)((nt + ns - 1) / ns);
+}
+
+int group_sums_parts(int64_t n) {
+  const int64_t nt = (n + AT - 1) / AT;
+  const int tpw = group_tpw(n);
+  return (int)((nt + tpw - 1) / tpw);
+}
+
+template <int PM>
+static hipError_t group_mm_pm(int kind, PairSide S, int B, int ZS, TabView tab, int b0, int b1,
+                              const int *label, int G, int tpw, dim3 grid, double *part,
+                              hipStream_t st) {
+  const size_t lds = group_mm_lds(PM, B, kind);
+  const void *f = kind == 0 ? (const void *)k_group_mm<PM, 0> : (const void *)k_group_mm<PM, 1>;
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  if (kind == 0)
+    hipLaunchKernelGGL((k_group_mm<PM, 0>), grid, dim3(256), lds, st, S, B, ZS, tab, b0, b1, label,
+                       G, tpw, part, S.n);
+  else
+    hipLaunchKernelGGL((k_group_mm<PM, 1>), grid, dim3(256), lds, st, S, B, ZS, tab, b0, b1, label,
+                       G, tpw, part, S.n);
+  return hipGetLastError();
+}
+
+hipError_t launch_group_sums(int kind, int PM, PairSide S, int B, int ZS, TabView tab, int b0,
+                             int b1, const int *label, int G, double *part, double *R,
+                             hipStream_t st) {
+  if (S.n <= 0 || G < 1 || G > 64 || b1 <= b0) return hipErrorInvalidValue;
+  const int64_t nt = (S.n + AT - 1) / AT;
+  const int tpw = group_tpw(S.n);
+  const int nparts = group_sums_parts(S.n);
+  const dim3 grid((unsigned)nparts, (unsigned)nt);
+  hipError_t e = hipSuccess;
+  if (pairs_use_mm(PM, false) && group_mm_lds(PM, B, kind) <= 160 * 1024) {
+    switch (PM) {
+#define ACE_CASE(P) \
+  case P: e = group_mm_pm<P>(kind, S, B, ZS, tab, b0, b1, label, G, tpw, grid, part, st); break;
+      ACE_CASE(4) ACE_CASE(8) ACE_CASE(12) ACE_CASE(16) ACE_CASE(20) ACE_CASE(24)
+      ACE_CASE(32) ACE_CASE(48) ACE_CASE(64)
+#undef ACE_CASE
+      default: return hipErrorInvalidValue;
+    }
+  } else {
+    const size_t lds = (size_t)(64 + 64 * G) * sizeof(double);
+    if (kind == 0)
+      hipLaunchKernelGGL((k_group_valu<0>), grid, dim3(64), lds, st, S, PM, B, ZS, tab, b0, b1,
+                         label, G, tpw, part, S.n);
+    else
+      hipLaunchKernelGGL((k_group_valu<1>), grid, dim3(64), lds, st, S, PM, B, ZS, tab, b0, b1,
+                         label, G, tpw, part, S.n);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) return e;
+  const int64_t count = S.n * G;
+  hipLaunchKernelGGL(k_sum_parts, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, part,
+                     nparts, count, R);
+  return hipGetLastError();
+}
+
 hipError_t launch_assembly_mm(int kind, int PM, PairSide S, int64_t npad, int B, int ZS,
                               TabView tab, double sig, double *out, int64_t ld, double *kcopy,
                               hipStream_t st, const Tile *tiles, int64_t ntiles, int G, int part) {

@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cmath>
+#include <functional>
 #include <vector>
 
 #include "../../include/ace_hip.h"
@@ -238,9 +239,21 @@ namespace {
 
 // ace_model_predict (marginal = false) / ace_model_predict_marginal: the
 // model's resident inverse, K_xX assembled from the resident training side.
+// The grouped pass after the marginal pipeline (ace_model_predict_marginal_groups,
+// ace_model_robust_treatment): gcov = E^T (Km_xx - Km_xX A^-1 Km_xX^T) E for
+// the indicator E of `label`; prepare (optional) runs after map / ci / var
+// are final and before the labels are read.
+struct GroupReq {
+  int G = 0;
+  const int32_t *label = nullptr;
+  double *gcov = nullptr;
+  std::function<void()> prepare;
+};
+
 void predict_impl(ace_model *m, const double *theta, int64_t nx, const double *X2,
                   const double *Zt, bool marginal, const double *Z_x, int ate, double mean_y,
-                  double std_y, double std_Z, double *map, double *ci, double *var, double *avg) {
+                  double std_y, double std_Z, double *map, double *ci, double *var, double *avg,
+                  const GroupReq *grp = nullptr) {
   ace_ctx *ctx = m->ctx;
   hipStream_t st = ctx->stream;
   const Shape &s = m->s;
@@ -289,8 +302,14 @@ void predict_impl(ace_model *m, const double *theta, int64_t nx, const double *X
     };
   }
   if (m->shard) op.allreduce = [&](double *b, int64_t c) { shard_allreduce_sum(m->shard, b, c); };
+  // the chunk K_xX's scratch holds after the pipeline (the grouped pass reuses it)
+  int64_t last_c0 = -1, last_nc = 0;
+  const double *last_K = nullptr;
   op.cross = [&](int64_t c0, int64_t nc, int64_t *ld, DBuf &scratch) -> const double * {
     alloc(ctx, scratch, (size_t)(nc * n) * sizeof(double), "alloc K_xX");
+    last_c0 = c0;
+    last_nc = nc;
+    last_K = scratch.d();
     PairSide tc = test.view(nc);
     tc.X += c0 * s.PM;
     tc.Z += c0 * s.ZS;
@@ -314,6 +333,87 @@ void predict_impl(ace_model *m, const double *theta, int64_t nx, const double *X
     return scratch.d();
   };
   pred_pipeline(op, nx, marginal, Z_x, ate, theta[0], mu, mean_y, std_y, std_Z, map, ci, var, avg);
+  if (!grp) return;
+  if (grp->prepare) grp->prepare();
+  const int G = grp->G;
+  // like the pipeline: an allocation failure frees the retained scratch and
+  // the pass runs once more (gcov is written only at its end)
+  auto groups_once = [&]() {
+  // S = Km_xX^T E (n x G), chunk by chunk from the last one down: that one is
+  // still in the scratch when the pipeline kept it, the others are assembled
+  // again; the order does not depend on which, so neither do the sums
+  std::shared_ptr<PredScratch> ps = std::static_pointer_cast<PredScratch>(ctx->pred_state);
+  if (!ps) {
+    ps = std::make_shared<PredScratch>();
+    ctx->pred_state = ps;
+    last_K = nullptr;
+  }
+  const int64_t chunk = std::min<int64_t>(NXC, nx);
+  DBuf dlab, dE, dS, dU, dtmp, dwork, dpart, dR, dQ;
+  alloc(ctx, dlab, (size_t)nx * sizeof(int32_t), "alloc labels");
+  upload_bytes(ctx, dlab.p, grp->label, (size_t)nx * sizeof(int32_t), "upload labels");
+  alloc(ctx, dE, (size_t)(nx * G) * sizeof(double), "alloc E");
+  ck(ctx, launch_label_matrix(dlab.i(), nx, G, dE.d(), st), "label matrix");
+  alloc(ctx, dS, (size_t)(n * G) * sizeof(double), "alloc S");
+  alloc(ctx, dU, (size_t)(n * G) * sizeof(double), "alloc U");
+  alloc(ctx, dQ, (size_t)(2 * G * G) * sizeof(double), "alloc Q");
+  const int64_t nwork = std::max(gemm_tn_work(n, G, chunk),
+                                 std::max(gemm_tn_work(G, G, nx), gemm_tn_work(G, G, n)));
+  alloc(ctx, dwork, (size_t)nwork * sizeof(double), "alloc gemm partials");
+  bool first = true;
+  for (int64_t c0 = (nx - 1) / chunk * chunk; c0 >= 0; c0 -= chunk) {
+    const int64_t nc = std::min<int64_t>(chunk, nx - c0);
+    int64_t ldk = nc;
+    const double *Kc = (last_K && last_K == ps->K.d() && last_c0 == c0 && last_nc == nc)
+                           ? last_K
+                           : op.cross(c0, nc, &ldk, ps->K);
+    ck(ctx, launch_gemm_tn(n, G, nc, Kc, ldk, dE.d() + c0, nx, dS.d(), n, !first, dwork.d(), st),
+       "S += K^T E");
+    first = false;
+  }
+  // U = A^-1 S (this rank's share when sharded), Q_inv = S^T U
+  symm_resident(m, dS.d(), n, false, G, dU.d(), dtmp);
+  double *Qinv = dQ.d(), *Qxx = dQ.d() + G * G;
+  ck(ctx, launch_gemm_tn(G, G, n, dS.d(), n, dU.d(), n, Qinv, G, false, dwork.d(), st), "S^T U");
+  if (m->shard) shard_allreduce_sum(m->shard, Qinv, (int64_t)G * G);
+  // R = Km_xx E without Km_xx, Q_xx = E^T R
+  alloc(ctx, dpart, (size_t)(group_sums_parts(nx) * nx * G) * sizeof(double), "alloc R partials");
+  alloc(ctx, dR, (size_t)(nx * G) * sizeof(double), "alloc R");
+  ck(ctx, launch_group_sums(s.kind, s.PM, test.view(nx), B, s.ZS, tv, b0, b1, dlab.i(), G,
+                            dpart.d(), dR.d(), st),
+     "grouped kernel sums");
+  ck(ctx, launch_gemm_tn(G, G, nx, dE.d(), nx, dR.d(), nx, Qxx, G, false, dwork.d(), st), "E^T R");
+  std::vector<double> q((size_t)(2 * G * G));
+  download(ctx, q.data(), dQ.d(), q.size(), "download group sums");
+  sync(ctx);
+  for (int e = 0; e < G * G; ++e) grp->gcov[e] = q[(size_t)(G * G + e)] - q[(size_t)e];
+  };
+  try {
+    groups_once();
+  } catch (const Fail &f) {
+    if (f.code != ACE_ERR_OOM) throw;
+    (void)hipGetLastError();
+    sync(ctx);  // the failed pass's launches may still read the scratch
+    release_pred_state(ctx);
+    ctx->sweep_pool.clear();
+    groups_once();
+  }
+  if (auto ps = std::static_pointer_cast<PredScratch>(ctx->pred_state))
+    if (ps->K.bytes + ps->T.bytes + ps->Kxx.bytes > PRED_KEEP_BYTES) release_pred_state(ctx);
+}
+
+// gsum / gcount of ace_model_predict_marginal_groups from the final map
+void group_sums_host(int64_t nx, int G, const int32_t *label, const double *map, double *gsum,
+                     int64_t *gcount) {
+  for (int g = 0; g < G; ++g) {
+    gsum[g] = 0.0;
+    gcount[g] = 0;
+  }
+  for (int64_t i = 0; i < nx; ++i)
+    if (label[i] >= 0) {
+      gsum[label[i]] += map[i];
+      ++gcount[label[i]];
+    }
 }
 
 }  // namespace
@@ -368,6 +468,96 @@ int ace_model_predict_marginal(ace_model *m, const double *theta, int64_t nx, co
   require_inverse(m);
   predict_impl(m, theta, nx, X2, dZ2, true, Z_x, calculate_ate, 0.0, std_y, std_Z, map, ci, var,
                avg);
+  return ACE_OK;
+  ACE_CATCH
+}
+
+int ace_model_predict_marginal_groups(ace_model *m, const double *theta, int64_t nx,
+                                      const double *X2, const double *dZ2, double std_y,
+                                      double std_Z, int G, const int32_t *label, double *map,
+                                      double *ci, double *var, double *gsum, int64_t *gcount,
+                                      double *gcov) {
+  if (!m) return ACE_ERR_ARG;
+  ace_ctx *ctx = m->ctx;
+  ACE_TRY
+  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+  arg(ctx, nx >= 1 && theta && map && ci && var && (m->s.p == 0 || X2) && (m->s.B == 1 || dZ2),
+      "bad shape / null argument");
+  arg(ctx, label && gsum && gcount && gcov, "null argument");
+  arg(ctx, G >= 1 && G <= 64, "G must be in [1, 64]");
+  for (int64_t i = 0; i < nx; ++i) arg(ctx, label[i] >= -1 && label[i] < G, "label outside [-1, G)");
+  require_inverse(m);
+  GroupReq grp;
+  grp.G = G;
+  grp.label = label;
+  grp.gcov = gcov;
+  predict_impl(m, theta, nx, X2, dZ2, true, nullptr, 0, 0.0, std_y, std_Z, map, ci, var, nullptr,
+               &grp);
+  group_sums_host(nx, G, label, map, gsum, gcount);
+  return ACE_OK;
+  ACE_CATCH
+}
+
+int ace_model_robust_treatment(ace_model *m, const double *theta, int64_t nx, const double *X2,
+                               const double *dZ2, const double *Z_x, double std_y, double std_Z,
+                               int n_steps, double *map, double *ci, double *var,
+                               double *thresholds, int32_t *level, double *avg, int64_t *counts) {
+  if (!m) return ACE_ERR_ARG;
+  ace_ctx *ctx = m->ctx;
+  ACE_TRY
+  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+  arg(ctx, nx >= 1 && theta && map && ci && var && (m->s.p == 0 || X2) && (m->s.B == 1 || dZ2),
+      "bad shape / null argument");
+  arg(ctx, Z_x && thresholds && level && avg && counts, "null argument");
+  arg(ctx, n_steps >= 1 && n_steps <= 31, "n_steps must be in [1, 31]");
+  for (int64_t i = 0; i < nx; ++i)
+    arg(ctx, Z_x[i] == 0.0 || Z_x[i] == 1.0, "Z_x must be 0 or 1 (binary treatment)");
+  require_inverse(m);
+  const int T = n_steps + 1, G = 2 * T;
+  std::vector<int32_t> label((size_t)nx);
+  std::vector<double> gcov((size_t)(G * G));
+  GroupReq grp;
+  grp.G = G;
+  grp.label = label.data();
+  grp.gcov = gcov.data();
+  grp.prepare = [&]() {
+    const int st = ace_robust_levels(nx, var, n_steps, thresholds, level);
+    if (st != ACE_OK) {
+      ctx->err = "robust_treatment: non-finite posterior variance";
+      throw Fail{st};
+    }
+    for (int64_t i = 0; i < nx; ++i) label[(size_t)i] = 2 * level[i] + (Z_x[i] == 1.0 ? 1 : 0);
+  };
+  predict_impl(m, theta, nx, X2, dZ2, true, nullptr, 0, 0.0, std_y, std_Z, map, ci, var, nullptr,
+               &grp);
+  std::vector<double> gsum((size_t)G);
+  std::vector<int64_t> gcount((size_t)G);
+  group_sums_host(nx, G, label.data(), map, gsum.data(), gcount.data());
+  // step t keeps the groups of levels <= t: prefix sums of gsum, gcount, gcov
+  for (int t = 0; t < T; ++t) {
+    const int g1 = 2 * (t + 1);
+    double sy = 0.0, syz = 0.0, post[3] = {0.0, 0.0, 0.0};
+    int64_t kept = 0, treated = 0;
+    for (int g = 0; g < g1; ++g) {
+      sy += gsum[(size_t)g];
+      kept += gcount[(size_t)g];
+      if (g & 1) {
+        syz += gsum[(size_t)g];
+        treated += gcount[(size_t)g];
+      }
+    }
+    for (int h = 0; h < g1; ++h)
+      for (int g = 0; g < g1; ++g) {
+        const double c = gcov[(size_t)(g + h * G)];
+        post[0] += c;
+        if ((g & 1) && (h & 1)) post[1] += c;
+        if (!(g & 1) && !(h & 1)) post[2] += c;
+      }
+    marginal_averages(kept, std_y, sy, syz, (double)treated, post, avg + 12 * t);
+    counts[3 * t + 0] = kept;
+    counts[3 * t + 1] = treated;
+    counts[3 * t + 2] = kept - treated;
+  }
   return ACE_OK;
   ACE_CATCH
 }

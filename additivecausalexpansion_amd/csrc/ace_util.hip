@@ -400,6 +400,117 @@ hipError_t launch_gemm_nn(int64_t m, int64_t n, int64_t k, const double *A, int6
   return hipGetLastError();
 }
 
+// C (m x n) = A^T B for A (k x m, lda) and B (k x n, ldb), col-major: both
+// operands run along k in memory.  Made for a small output and a long k
+// (the grouped posterior sums: n <= 64 columns): a workgroup owns a 64 x 64
+// tile of C and the k range [z ks, (z + 1) ks), wave w the tile's rows
+// 16 w .. 16 w + 15 as four v_mfma_f64_16x16x4_f64 fragments (first operand
+// B's column, second A's column: D register j of lane (lr, lk) is
+// C[16 w + lr][16 ci + lk + 4 j], as in k_gemm_nn; only the ceil(n / 16)
+// fragments with live columns are staged and multiplied); zero-filled edges.  The
+// k ranges write separate partials (work + z m n), which k_gemm_tn_sum adds
+// in ascending z -- on top of C when accumulate is set.
+constexpr int TLD = 65;
+
+__global__ __launch_bounds__(256) void k_gemm_tn(int64_t m, int64_t n, int64_t k, int64_t ks,
+                                                 const double *__restrict__ A, int64_t lda,
+                                                 const double *__restrict__ B, int64_t ldb,
+                                                 double *__restrict__ work) {
+  __shared__ double sA[GBK][TLD];
+  __shared__ double sB[GBK][TLD];
+  const int64_t R0 = (int64_t)blockIdx.y * 64, C0 = (int64_t)blockIdx.x * 64;
+  const int64_t z = blockIdx.z;
+  const int64_t kb = z * ks, ke = (kb + ks < k) ? kb + ks : k;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+  const int sk = tid & 15, sm = tid >> 4;  // stage: one k, columns sm + 16 e
+  // live 16-column fragments of this tile (n = 12 groups: one of four)
+  const int nf = (n - C0 >= 64) ? 4 : (int)((n - C0 + 15) / 16);
+  d4 acc[4];
+#pragma unroll
+  for (int ci = 0; ci < 4; ++ci) acc[ci] = d4{0.0, 0.0, 0.0, 0.0};
+  for (int64_t k0 = kb; k0 < ke; k0 += GBK) {
+    const int64_t kk = k0 + sk;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int64_t r = R0 + sm + 16 * e, c = C0 + sm + 16 * e;
+      sA[sk][sm + 16 * e] = (r < m && kk < ke) ? A[kk + r * lda] : 0.0;
+      if (e < nf) sB[sk][sm + 16 * e] = (c < n && kk < ke) ? B[kk + c * ldb] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < GBK / 4; ++q) {
+      const double b = sA[4 * q + lk][16 * wv + lr];
+#pragma unroll
+      for (int ci = 0; ci < 4; ++ci)
+        if (ci < nf)
+          acc[ci] = __builtin_amdgcn_mfma_f64_16x16x4f64(sB[4 * q + lk][16 * ci + lr], b, acc[ci],
+                                                         0, 0, 0);
+    }
+    __syncthreads();
+  }
+  double *const P = work + z * m * n;
+  const int64_t r = R0 + 16 * wv + lr;
+#pragma unroll
+  for (int ci = 0; ci < 4; ++ci)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t c = C0 + 16 * ci + lk + 4 * j;
+      if (r < m && c < n) P[r + c * m] = acc[ci][j];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_gemm_tn_sum(const double *__restrict__ work, int nz,
+                                                     int64_t m, int64_t n, double *__restrict__ C,
+                                                     int64_t ldc, int accumulate) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= m * n) return;
+  const int64_t r = e % m, c = e / m;
+  double s = accumulate ? C[r + c * ldc] : 0.0;
+  for (int z = 0; z < nz; ++z) s += work[(int64_t)z * m * n + e];
+  C[r + c * ldc] = s;
+}
+
+// k ranges of launch_gemm_tn: about 1024 workgroups, at least 256 of k each
+static int gemm_tn_splits(int64_t m, int64_t n, int64_t k) {
+  const int64_t tiles = ((m + 63) / 64) * ((n + 63) / 64);
+  int64_t nz = (1024 + tiles - 1) / tiles;
+  const int64_t most = (k + 255) / 256;
+  if (nz > most) nz = most;
+  return (int)(nz < 1 ? 1 : nz);
+}
+
+int64_t gemm_tn_work(int64_t m, int64_t n, int64_t k) { return gemm_tn_splits(m, n, k) * m * n; }
+
+hipError_t launch_gemm_tn(int64_t m, int64_t n, int64_t k, const double *A, int64_t lda,
+                          const double *B, int64_t ldb, double *C, int64_t ldc, bool accumulate,
+                          double *work, hipStream_t st) {
+  if (m <= 0 || n <= 0 || k <= 0) return hipErrorInvalidValue;
+  const int nz = gemm_tn_splits(m, n, k);
+  const int64_t ks = ((k + nz - 1) / nz + GBK - 1) / GBK * GBK;
+  const dim3 grid((unsigned)((n + 63) / 64), (unsigned)((m + 63) / 64), (unsigned)nz);
+  hipLaunchKernelGGL(k_gemm_tn, grid, dim3(256), 0, st, m, n, k, ks, A, lda, B, ldb, work);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_gemm_tn_sum, dim3((unsigned)((m * n + 255) / 256)), dim3(256), 0, st, work,
+                     nz, m, n, C, ldc, accumulate ? 1 : 0);
+  return hipGetLastError();
+}
+
+// E (nx x G, ld nx) = the group indicator of the labels: E[i][g] = (label[i] == g)
+__global__ __launch_bounds__(256) void k_label_matrix(const int *__restrict__ label, int64_t nx,
+                                                      int G, double *__restrict__ E) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= nx * G) return;
+  E[e] = (label[e % nx] == (int)(e / nx)) ? 1.0 : 0.0;
+}
+
+hipError_t launch_label_matrix(const int *label, int64_t nx, int G, double *E, hipStream_t st) {
+  hipLaunchKernelGGL(k_label_matrix, dim3((unsigned)((nx * G + 255) / 256)), dim3(256), 0, st,
+                     label, nx, G, E);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- copies
 // out (full n x n) = scale * sym(A lower); tile-transposed through LDS.
 // G > 1: A is block-cyclic column storage (launch_sym_from_cyclic).

@@ -142,6 +142,64 @@ class DeviceModel:
                 out[key] = {"map": a[0], "ci": np.array([a[1], a[2]]), "var": a[3]}
         return out
 
+    def _test_side(self, theta, X2, dZ2):
+        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
+        X2f = fmat(X2)
+        nx = X2f.shape[0]
+        dZf = np.asfortranarray(np.asarray(dZ2, dtype=np.float64).reshape(nx, -1))
+        return th, X2f, dZf, nx
+
+    def predict_marginal_groups(self, theta, X2, dZ2, std_y, std_Z, G, label):
+        """ace_model_predict_marginal_groups: predict_marginal's map / ci / var
+        plus, for the G groups of `label` (int, -1 = no group), gsum (the sum
+        of map), gcount and gcov = E^T C E (G x G) with C the unscaled
+        marginal posterior covariance; the nx x nx test kernel is never built."""
+        th, X2f, dZf, nx = self._test_side(theta, X2, dZ2)
+        lab = np.ascontiguousarray(np.ravel(label), dtype=np.int32)
+        if lab.size != nx:
+            raise AceError("label must have one entry per test point")
+        G = int(G)
+        mp, var = np.empty(nx), np.empty(nx)
+        ci = np.empty((nx, 2), order="F")
+        gsum = np.empty(max(G, 1))
+        gcount = np.zeros(max(G, 1), dtype=np.int64)
+        gcov = np.empty((max(G, 1), max(G, 1)), order="F")
+        check(lib().ace_model_predict_marginal_groups(
+            self.handle, ptr(th), nx, ptr(X2f), ptr(dZf), float(std_y),
+            float(np.ravel([std_Z])[0]), G, lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(mp), ptr(ci), ptr(var),
+            ptr(gsum), gcount.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ptr(gcov)),
+            self.ctx.handle)
+        return {"map": mp, "ci": ci, "var": var, "gsum": gsum, "gcount": gcount, "gcov": gcov}
+
+    def robust_treatment(self, theta, X2, dZ2, Z_x, std_y, std_Z, n_steps=5):
+        """ace_model_robust_treatment: the ATE / ATT / ATU of every discard step
+        of R/robust_treatment.R from one marginal pass and one grouped pass.
+        avg is 12 x (n_steps + 1) (column t as predict_marginal's averages on
+        step t's subset), counts 3 x (n_steps + 1) (retained, treated,
+        untreated); "ate" / "att" / "atu" hold the per-step map, ci, var."""
+        th, X2f, dZf, nx = self._test_side(theta, X2, dZ2)
+        zx = np.ascontiguousarray(np.ravel(Z_x), dtype=np.float64)
+        if zx.size != nx:
+            raise AceError("Z_x must have one entry per test point")
+        n_steps = int(n_steps)
+        T = max(n_steps, 0) + 1
+        mp, var = np.empty(nx), np.empty(nx)
+        ci = np.empty((nx, 2), order="F")
+        thr = np.empty(T)
+        level = np.empty(nx, dtype=np.int32)
+        avg = np.empty((12, T), order="F")
+        counts = np.zeros((3, T), dtype=np.int64, order="F")
+        check(lib().ace_model_robust_treatment(
+            self.handle, ptr(th), nx, ptr(X2f), ptr(dZf), ptr(zx), float(std_y),
+            float(np.ravel([std_Z])[0]), n_steps, ptr(mp), ptr(ci), ptr(var), ptr(thr),
+            level.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(avg),
+            counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), self.ctx.handle)
+        out = {"map": mp, "ci": ci, "var": var, "thresholds": thr, "level": level, "avg": avg,
+               "counts": counts}
+        for j, key in enumerate(("ate", "att", "atu")):
+            out[key] = {"map": avg[4 * j], "ci": avg[4 * j + 1:4 * j + 3].T, "var": avg[4 * j + 3]}
+        return out
+
     def comm_calls(self):
         """ace_model_comm_calls: collectives this rank issued since creation,
         {"broadcast", "allgather", "allreduce", "groups"} (zeros when simulated)."""
@@ -326,6 +384,14 @@ class _KernelClass:
         return native.pred_marginal_cpp(y, Z2, self.parameters[0], self.parameters[1],
                                         self.invKmatn, Km_xX, Km_xx, mean_y, std_y, std_Z,
                                         calculate_ate, ctx=self.ctx)
+
+    def robust_treatment(self, y, X, Z, X2, Z2, dZ2, std_y, std_Z, n_steps=5):
+        """R/robust_treatment.R:83-128 on the fit's device model: Z2 is the
+        binary treatment of the test points, dZ2 their derivative basis."""
+        if not self._resident(y, X, Z):
+            raise AceError("robust_treatment needs the fit's device-resident inverse "
+                           "(para_update on the same data)")
+        return self._model.robust_treatment(self.parameters, X2, dZ2, Z2, std_y, std_Z, n_steps)
 
     def mean_solution(self, y):
         """R/kernel_SE_R6.R:99-102 (private in the SE class)."""

@@ -405,3 +405,15 @@ def normalize_test(X, Z, moments):
     mom = fmat(moments)
     check(lib().ace_normalize_test(X.shape[0], X.shape[1], Z.shape[1], ptr(X), ptr(Z), ptr(mom),
                                    mom.shape[0]))
+
+
+def robust_levels(var, n_steps):
+    """ace_robust_levels (R/robust_treatment.R:83-84, 94): the type-7 quantile
+    thresholds of var at seq(0, 1, 1 / n_steps) and, per point, the first step
+    at which it is retained.  Returns (thresholds (n_steps + 1), level (int32))."""
+    v = np.ascontiguousarray(np.ravel(var), dtype=np.float64)
+    thr = np.empty(max(int(n_steps), 0) + 1)
+    level = np.empty(v.size, dtype=np.int32)
+    check(lib().ace_robust_levels(v.size, ptr(v), int(n_steps), ptr(thr),
+                                  level.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return thr, level

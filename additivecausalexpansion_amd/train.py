@@ -267,3 +267,51 @@ def predict_ace(obj, newX=None, newZ=None, marginal=False, return_average_treatm
     return K.predict_marginal(y, X, Btr, Xn, tb["B"], tb["dB"], mom[0, 0], mom[0, 1],
                               mom[1 + px:1 + px + pz, 1],
                               bool(np.all(isbinary)) and return_average_treatments)
+
+
+def robust_treatment(obj, newX=None, n_steps=5):
+    """R/robust_treatment.R:67-128 without the plots: ATE (in-sample also ATT
+    and ATU) while the points with the largest posterior variance of the
+    marginal effect are discarded, n_steps + 1 nested subsets cut at the
+    type-7 quantiles of that variance.  In-sample (newX None) the training X
+    and Z are the test points (the reference's normalize=FALSE calls);
+    out-of-sample newX is taken with newZ = 1.  One marginal pass and one
+    grouped pass on the device replace the reference's n_steps + 2
+    predictions.  Returns {"idx": n_pred x (n_steps + 1) bool (the reference's
+    return value), "ate": its ate_results table (map, ci0, ci1, var, retained;
+    in-sample also treated, untreated), "thresholds"} and in-sample "att" /
+    "atu" (map, ci0, ci1, var; NaN rows where the group is empty)."""
+    if not np.all(obj["train_data"]["Zbinary"]):
+        raise AceError("Average treatment effect requires binary treatment indicator.")
+    X = obj["train_data"]["X"]
+    px = X.shape[1]
+    pz = obj["train_data"]["Z"].shape[1]
+    mom = obj["moments"]
+    insample = newX is None
+    if insample:
+        Xn, Zn = X, obj["train_data"]["Z"]
+    else:
+        Xn = np.array(newX, dtype=np.float64, order="F", copy=True)
+        if Xn.ndim != 2 or Xn.shape[1] != px:
+            raise AceError("Dimension mismatch of X with newX")
+        Zn = np.full((Xn.shape[0], 1), 1.0, order="F")
+        native.normalize_test(Xn, Zn, mom)
+    tb = obj["Basis"].testbasis(Zn)
+    r = obj["Kernel"].robust_treatment(obj["train_data"]["y"], X, obj["Basis"].B, Xn, tb["B"],
+                                       tb["dB"], mom[0, 1], mom[1 + px:1 + px + pz, 1], n_steps)
+    T = int(n_steps) + 1
+    avg, counts = r["avg"], r["counts"]
+    out = {"idx": r["level"][:, None] <= np.arange(T)[None, :], "thresholds": r["thresholds"]}
+    ate = np.full((T, 5 + 2 * insample), np.nan)
+    ate[:, :4] = avg[0:4].T
+    ate[:, 4] = counts[0]
+    out["ate"] = ate
+    if insample:
+        ate[:, 5] = counts[1]
+        ate[:, 6] = counts[2]
+        for j, key in ((1, "att"), (2, "atu")):
+            tab = np.full((T, 4), np.nan)
+            keep = counts[j] > 0
+            tab[keep] = avg[4 * j:4 * j + 4].T[keep]
+            out[key] = tab
+    return out

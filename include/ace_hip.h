@@ -45,7 +45,9 @@ enum ace_status {
   ACE_ERR_HIP = 2,         /* HIP runtime failure (no device, launch failure)   */
   ACE_ERR_OOM = 3,         /* device allocation failed                          */
   ACE_ERR_UNSUPPORTED = 4, /* shape outside the compiled range (p > 64, B > 32) */
-  ACE_ERR_NONFINITE = 5,   /* non-finite gradient in ace_model_train (R's stop()) */
+  ACE_ERR_NONFINITE = 5,   /* non-finite gradient in ace_model_train (R's stop());
+                              non-finite variance in ace_robust_levels (R's
+                              quantile() stops there)                           */
   ACE_ERR_INTERRUPTED = 6, /* the interrupt poll asked to stop                  */
   ACE_ERR_TIMEOUT = 7      /* device work did not drain within ACE_SYNC_TIMEOUT
                               seconds (default 600): a stalled queue or a hung
@@ -291,6 +293,49 @@ int ace_model_predict_marginal(ace_model *m, const double *theta, int64_t nx, co
                                const double *dZ2, const double *Z_x, double std_y, double std_Z,
                                int calculate_ate, double *map, double *ci, double *var,
                                double *avg);
+/* ace_model_predict_marginal plus grouped posterior sums.  label (nx) puts
+ * every test point in one of G groups (1 <= G <= 64) or, with -1, in none.
+ * map, ci, var: exactly ace_model_predict_marginal's (calculate_ate = 0).
+ * gsum (G): the sum of map over each group; gcount (G): its size; gcov
+ * (G x G, column-major): E^T C E with E the nx x G group indicator and
+ * C = Km_xx - Km_xX A^-1 Km_xX^T the unscaled marginal posterior covariance
+ * (Kmarg_xx after src/pred_cpp.cpp:72), so any ATE / ATT / ATU variance over
+ * a union of groups is a sum of gcov entries.  Km_xx is never stored: its
+ * group sums are reduced while the pair tiles are evaluated, and the second
+ * term is G right-hand sides through the resident inverse (sharded models:
+ * one all-reduce of G x G).  gcov is bitwise reproducible from call to call.
+ * ACE_ERR_ARG for G outside [1, 64], a label outside [-1, G), or before the
+ * first para_update. */
+int ace_model_predict_marginal_groups(ace_model *m, const double *theta, int64_t nx,
+                                      const double *X2, const double *dZ2, double std_y,
+                                      double std_Z, int G, const int32_t *label, double *map,
+                                      double *ci, double *var, double *gsum, int64_t *gcount,
+                                      double *gcov);
+/* The discard levels of robust_treatment (R/robust_treatment.R:83-84, 94;
+ * host only, no context): thresholds[t], t = 0 .. n_steps, is R's default
+ * (type 7) quantile of var at probability min(t * (1.0 / n_steps), 1), and
+ * level[i] the first step t with var[i] <= thresholds[t], i.e. point i is
+ * retained at steps t >= level[i].  1 <= n_steps <= 31.  A non-finite var
+ * returns ACE_ERR_NONFINITE. */
+int ace_robust_levels(int64_t nx, const double *var, int n_steps, double *thresholds,
+                      int32_t *level);
+/* robust_treatment (R/robust_treatment.R:67-128 without the plots): the
+ * ATE / ATT / ATU sequence while the test points with the largest posterior
+ * variance are discarded.  One marginal pass gives map, ci and var;
+ * ace_robust_levels gives thresholds (n_steps + 1) and level (nx); one
+ * grouped pass with label = 2 level + Z_x gives every step's sums.  avg
+ * (12 x (n_steps + 1), column-major): column t is what ace_pred_marginal's
+ * avg holds for the subset retained at step t (the reference's
+ * predict.ace(..., return_average_treatments = TRUE) on that subset), with
+ * the same C semantics for empty groups (0/0 = NaN, a NaN ATT propagating
+ * into ATU).  counts (3 x (n_steps + 1)): retained, treated, untreated.
+ * Z_x (nx) must be exactly 0 or 1 (ACE_ERR_ARG otherwise): the reference
+ * requires a binary treatment; a fit with propensity scores `pi`, whose
+ * weights would be Z - pi, is not supported.  Works on sharded models. */
+int ace_model_robust_treatment(ace_model *m, const double *theta, int64_t nx, const double *X2,
+                               const double *dZ2, const double *Z_x, double std_y, double std_Z,
+                               int n_steps, double *map, double *ci, double *var,
+                               double *thresholds, int32_t *level, double *avg, int64_t *counts);
 /* Per-kernel device timing for the roofline report: when enabled, HIP
  * events bracket every launch of the dense update kernel (`which` = 0),
  * the assembly kernel (1) and the gradient kernel (2) on the model's

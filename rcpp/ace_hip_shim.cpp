@@ -556,3 +556,35 @@ List ace_model_predict_r(SEXP model, NumericVector parameters, NumericMatrix X2,
                        map.begin(), ci.begin(), var.begin()));
   return List::create(_["map"] = map, _["ci"] = ci, _["var"] = var);
 }
+
+// robust_treatment's loop (R/robust_treatment.R:93-128) in one call on the
+// fused model: one marginal pass, the type-7 quantile levels and one grouped
+// pass (ace_model_robust_treatment).  Z_x is the binary treatment of the test
+// points, dZ2 their derivative basis.  Returns the per-point prediction, the
+// thresholds (discard.steps), idx (n.pred x (n.steps + 1) logical, the
+// reference's return value), avg (12 x (n.steps + 1): ATE / ATT / ATU map,
+// ci, var per step) and counts (3 x (n.steps + 1): retained, treated,
+// untreated).  Like the rest of this file it is not compiled here.
+// [[Rcpp::export]]
+List ace_model_robust_treatment_r(SEXP model, NumericVector parameters, NumericMatrix X2, SEXP dZ2,
+                                  NumericVector Z_x, double std_y, double std_Z, int n_steps) {
+  XPtr<ace_model, PreserveStorage, ace_model_destroy, true> m(model);
+  const int64_t nx = X2.nrow();
+  if (n_steps < 1 || n_steps > 31) Rcpp::stop("ace: n.steps must be in 1..31");
+  if (Z_x.size() != nx) Rcpp::stop("ace: Z_x needs one entry per test point");
+  NumericVector map(nx), var(nx), thr(n_steps + 1);
+  NumericMatrix ci(nx, 2), avg(12, n_steps + 1);
+  std::vector<int32_t> level((size_t)nx);
+  std::vector<int64_t> counts((size_t)(3 * (n_steps + 1)));
+  ok(ace_model_robust_treatment(m.get(), parameters.begin(), nx, X2.begin(), REAL(dZ2),
+                                Z_x.begin(), std_y, std_Z, n_steps, map.begin(), ci.begin(),
+                                var.begin(), thr.begin(), level.data(), avg.begin(),
+                                counts.data()));
+  LogicalMatrix idx(nx, n_steps + 1);
+  for (int t = 0; t <= n_steps; ++t)
+    for (int64_t i = 0; i < nx; ++i) idx(i, t) = level[(size_t)i] <= t;
+  NumericMatrix cnt(3, n_steps + 1);
+  for (size_t e = 0; e < counts.size(); ++e) cnt[e] = (double)counts[e];
+  return List::create(_["map"] = map, _["ci"] = ci, _["var"] = var, _["thresholds"] = thr,
+                      _["idx"] = idx, _["avg"] = avg, _["counts"] = cnt);
+}
