@@ -11,7 +11,11 @@
 // no longer depends on p, so large-p tiles (C3: p = 32, C4: p = 50) keep
 // 3-4 waves per SIMD instead of one with scratch spills.  The cancellation
 // in the expansion is bounded by eps * (s_b(r) + s_b(c)); r2 is clamped at 0
-// and forced to 0 on the diagonal.
+// and forced to 0 on the diagonal.  (Held, with its constant 2 (PM + 4) and
+// per element of K, by tests/test_regimes_gpu.py
+// test_mfma_pair_arithmetic_within_bound on duplicated rows, offsets, short
+// and long length scales and underflowing arguments; the bound's derivation
+// is in tests/regimes.py.)
 //
 // Tile ownership (64 x 64 pairs, 256 threads): wave w, lane (lr, lk) owns
 // row r = R0 + 16 w + lr and the 16 columns c = C0 + 16 cb + lk + 4 v
