@@ -26,11 +26,10 @@ std::string g_create_err;
 
 namespace {
 double sync_timeout_s() {
-  static double v = -1.0;
-  if (v < 0.0) {
+  static const double v = [] {  // seconds, fractions allowed: not an env_int
     const char *e = getenv("ACE_SYNC_TIMEOUT");
-    v = e ? std::max(0.0, atof(e)) : 600.0;
-  }
+    return e ? std::max(0.0, atof(e)) : 600.0;
+  }();
   return v;
 }
 }  // namespace
@@ -106,8 +105,7 @@ int ace_create(int device, ace_ctx **out) {
   // panel chain + tail path (default), 2 = the tail path on the panel
   // stream, 1 = everything on the main stream (no lookahead overlap).  The
   // results are bit-identical for every value.
-  const char *vs = getenv("ACE_STREAMS");
-  const int nstr = vs ? std::min(3, std::max(1, atoi(vs))) : 3;
+  const int nstr = std::min(3, std::max(1, env_int("ACE_STREAMS", 3)));
   e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) c->nstreams = 1;
   if (e == hipSuccess && nstr >= 2) {
@@ -477,11 +475,7 @@ int ace_pred_marginal(ace_ctx *ctx, int64_t nX, int64_t nx, int B, const double 
 // CUs per shader engine the assembly's second part leaves to the first sweep group's
 // head path (ACE_ASM_PERSIST, default 1; 0: the plain grid)
 static int asm_persist_reserve() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_ASM_PERSIST");
-    v = e ? std::max(0, std::min(2, atoi(e))) : 1;
-  }
+  static const int v = std::max(0, std::min(2, env_int("ACE_ASM_PERSIST", 1)));
   return v;
 }
 
@@ -490,16 +484,12 @@ static int asm_persist_reserve() {
 // whole assembly); ACE_ASM_FILL=1 (default) hands
 // the reserved CUs back to the assembly's queue once group 0's lookahead is
 // done (a filler launch on side2)
-static int env_flag(const char *name, int dflt) {
-  const char *e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
 static int asm_tail_mode() {
-  static const int v = env_flag("ACE_ASM_TAIL", 1);
+  static const int v = env_int("ACE_ASM_TAIL", 1);
   return v;
 }
 static bool asm_fill_on() {
-  static const bool v = env_flag("ACE_ASM_FILL", 1) != 0;
+  static const bool v = env_int("ACE_ASM_FILL", 1) != 0;
   return v;
 }
 
@@ -601,12 +591,8 @@ void build_grad_tiles(ace_ctx *ctx, int64_t n, DBuf &tiles, int64_t *ntiles, int
 // ACE_NORMS=0: every pair tile computes its own slice norms (A/B switch;
 // the table is bit-identical)
 static bool slice_norms_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_NORMS");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_NORMS", 1) != 0;
+  return v;
 }
 
 namespace {
@@ -719,11 +705,7 @@ void model_collect_timing(ace_model *m, int ts) {
 // stopping iteration's evaluation is re-run once at its saved theta.  A fit
 // spends at most ACE_TRAIN_SYNC extra evaluations.
 int train_sync_every() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_TRAIN_SYNC");
-    v = e ? std::max(1, atoi(e)) : 4;
-  }
+  static const int v = std::max(1, env_int("ACE_TRAIN_SYNC", 4));
   return v;
 }
 

@@ -191,10 +191,7 @@ ace_dmat *as(const ace_dmat *h) { return const_cast<ace_dmat *>(h); }
 // ACE_DMAT_DIRECT=0: invkernel_dev of a virtual Kfull materialises it and
 // copies it into the sweep buffer (the round-2 path; A/B switch)
 bool dmat_direct() {
-  static const bool v = [] {
-    const char *e = getenv("ACE_DMAT_DIRECT");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool v = env_int("ACE_DMAT_DIRECT", 1) != 0;
   return v;
 }
 

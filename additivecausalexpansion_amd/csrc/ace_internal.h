@@ -5,8 +5,20 @@
 #include <vector>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 namespace ace {
+
+// Environment switches (ACE_*): the integer value of `name`, dflt when unset.
+// Every switch is read once per process, as
+//   static const T v = <expression of env_int("ACE_X", dflt)>;
+// (the initialisation of a function-local static is thread-safe).
+inline int env_int(const char *name, int dflt) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+// whether `name` is set at all (switches whose default depends on the size)
+inline bool env_set(const char *name) { return getenv(name) != nullptr; }
 
 // Sweep (Gauss-Jordan SPD inversion) blocking; see DESIGN.md §3.
 #ifndef ACE_NB

@@ -663,11 +663,10 @@ static hipError_t asm_pm(int mode, int kind, PairSide R, PairSide C, int64_t npa
 // assembly 3.4 vs 3.96 ms; C4 p=50 gradient 372 vs 1534 ms).  ACE_PAIRS=valu
 // forces the VALU family (diagnostic A/B switch).
 bool pairs_use_mm(int PM, bool grad) {
-  static int v = -1;
-  if (v < 0) {
+  static const int v = [] {  // a word (mm / valu), not an env_int
     const char *e = getenv("ACE_PAIRS");
-    v = !e ? 2 : (e[0] == 'm' ? 1 : (e[0] == 'v' ? 0 : 2));
-  }
+    return !e ? 2 : (e[0] == 'm' ? 1 : (e[0] == 'v' ? 0 : 2));
+  }();
   (void)grad;
   return v != 0;
 }
@@ -723,14 +722,10 @@ static hipError_t grad_pm(int kind, PairSide S, int B, int ZS, TabView tab, cons
 }
 
 int grad_order_block() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_GRAD_ORDER");
-    // 4: gradient HBM reads 1.52 -> 1.21 GB per C2 evaluation against the
-    // 1.07 GB lower triangle (the per-tile X / Z staging stays in each XCD's
-    // L2), time-neutral (profiles/r02_grad_ab.txt)
-    v = e ? std::max(0, atoi(e)) : 4;
-  }
+  // 4: gradient HBM reads 1.52 -> 1.21 GB per C2 evaluation against the
+  // 1.07 GB lower triangle (the per-tile X / Z staging stays in each XCD's
+  // L2), time-neutral (profiles/r02_grad_ab.txt)
+  static const int v = std::max(0, env_int("ACE_GRAD_ORDER", 4));
   return v;
 }
 

@@ -74,12 +74,8 @@ void symm_resident(ace_model *m, const double *V, int64_t ldv, bool vt, int64_t 
 // quadratic form through the strictly lower triangle of A^-1 (half the
 // MFMA work of the full symmetric product; 0 = the full product, A/B)
 bool pred_tri() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_PRED_TRI");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_PRED_TRI", 1) != 0;
+  return v;
 }
 
 void require_inverse(ace_model *m) {

@@ -370,10 +370,7 @@ void build_head_lists(ace_ctx *ctx, RankState &R, int64_t naug, int steps, int G
 // ACE_SHARD_HEADS=0: the sharded sweep keeps the group schedule without the
 // head / tail split (run_sweep_sharded); default on
 bool shard_heads_on() {
-  static const bool v = [] {
-    const char *e = getenv("ACE_SHARD_HEADS");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool v = env_int("ACE_SHARD_HEADS", 1) != 0;
   return v;
 }
 
@@ -581,10 +578,7 @@ void rccl_warmup(ShardModel &m) {
 
 // ---- the sharded sweep -------------------------------------------------------
 bool fuse_pack() {
-  static const bool v = [] {
-    const char *e = getenv("ACE_FUSE_PACK");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool v = env_int("ACE_FUSE_PACK", 1) != 0;
   return v;
 }
 

@@ -1747,21 +1747,14 @@ __global__ __launch_bounds__(UTHREADS, 2) void k_update_multi_r(double *__restri
 // n = ACE_BULK_RESERVE_N, none above (there the bulk launches are the
 // critical path and need every CU).
 bool q_first(int64_t naug) {
-  static int v = -2;
-  if (v == -2) {
-    const char *e = getenv("ACE_QFIRST");
-    v = e ? (atoi(e) != 0) : -1;
-  }
+  static const int v = env_set("ACE_QFIRST") ? env_int("ACE_QFIRST", 0) != 0 : -1;
   if (v >= 0) return v != 0;
   return naug <= ACE_BULK_RESERVE_N + AUG;
 }
 
 int bulk_reserve(int64_t naug) {
-  static int v = -2;
-  if (v == -2) {
-    const char *e = getenv("ACE_BULK_RESERVE");
-    v = e ? std::max(0, std::min(2, atoi(e))) : -1;
-  }
+  static const int v =
+      env_set("ACE_BULK_RESERVE") ? std::max(0, std::min(2, env_int("ACE_BULK_RESERVE", 0))) : -1;
   if (v >= 0) return v;
   return naug <= ACE_BULK_RESERVE_N + AUG ? 1 : 0;
 }
@@ -1892,113 +1885,183 @@ __global__ __launch_bounds__(256) void k_update_x(double *__restrict__ A, int64_
     }
 }
 
-// Latency-critical lookahead updates of the head path (run_sweep_heads): npan
-// panels from ps on a list of 128-tiles none of which lies in a panel's
-// block (so no copies), as 64 x 64 quarters (blockIdx.x = 4 t + quarter;
-// the upper quarter of a diagonal tile too, as k_update computes it) with
-// k_update_x's 4-wave MFMA chain per panel and the accumulators kept across
-// panels: per element the same chain as k_update / k_update_multi, a quarter
-// of a 128-tile's work per workgroup.  go: the gather fused into the launch.
-__global__ __launch_bounds__(256, 4) void k_update_q(double *__restrict__ A, int64_t ld, PanelSet ps,
-                                                  int npan, int64_t ldp,
-                                                  const Tile *__restrict__ tiles, GatherOut go,
-                                                  double *__restrict__ pivSW,
-                                                  double *__restrict__ piv,
-                                                  int *__restrict__ flag) {
-  ACE_WGT(4, true);
-  // sW and sP in one buffer: the fused pivot below reuses it as its matrix
-  __shared__ __attribute__((aligned(16))) double sbuf[2][2][BK][XL];
-  static_assert(sizeof(sbuf) >= SUB * (SUB + 2) * sizeof(double), "pivot matrix fits the staging");
-  double (*sW)[BK][XL] = sbuf[0];
-  double (*sP)[BK][XL] = sbuf[1];
-  const Tile tt = tiles[blockIdx.x >> 2];
-  if (tt.I < 0) return;  // padding of the XCD order
-  const int q = blockIdx.x & 3;
-  const int64_t R0 = (int64_t)tt.I * UT + XT * (q & 1), C0 = (int64_t)tt.J * UT + XT * (q >> 1);
+// ---------------------------------------------------------------- head path
+// The latency-critical launches of the head path (run_sweep_heads) work on
+// QT x QT pieces of the 128-tiles, one per 256-thread workgroup: QT = 64, a
+// quarter (each wave 32 x 32, k_update_x's MFMA chain), or QT = 32
+// (ACE_QSPLIT, small n), a quarter of a quarter (each wave one 16 x 16 MFMA
+// block): four times the workgroups, a quarter of each one's K loop.  Every
+// element's MFMA chain (operands, k order, accumulator start) is that of the
+// 128-tile kernels at either width: bit-identical.
+//
+// Staging registers of one BK x QT chunk of both operands: each thread moves
+// QT / 32 double2 of a chunk row (SM64 / SH64 above).  Held, returned and
+// passed by value: as arrays, or by reference into a helper, they were kept
+// in scratch.
+template <int QT>
+struct QChunk {
+  double2 w[QT / 32], p[QT / 32];
+};
+template <int QT>
+__device__ __forceinline__ QChunk<QT> q_load(const double *gW, const double *gP) {
+  QChunk<QT> c;
+#pragma unroll
+  for (int e = 0; e < QT / 32; ++e) c.w[e] = *reinterpret_cast<const double2 *>(gW + QT / 2 * e);
+#pragma unroll
+  for (int e = 0; e < QT / 32; ++e) c.p[e] = *reinterpret_cast<const double2 *>(gP + QT / 2 * e);
+  return c;
+}
+// fn(R0 + a, C0 + c, v) for every accumulator element v = piece(a, c) of the thread
+template <int QT, class F>
+__device__ __forceinline__ void q_each(const d4 (&acc)[QT / 32][QT / 32], int64_t R0, int64_t C0,
+                                       F fn) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int wr = wv & 1, wc = wv >> 1;  // rows QT/2 * wr.., cols QT/2 * wc..
+  const int lr = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int ci = 0; ci < QT / 32; ++ci)
+#pragma unroll
+    for (int ri = 0; ri < QT / 32; ++ri) {
+      const int64_t r = R0 + QT / 2 * wr + 16 * ri + lr;
+      const int64_t c = C0 + QT / 2 * wc + 16 * ci + lk;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) fn(r, c + 4 * j, acc[ci][ri][j]);
+    }
+}
+
+// The K loop: T chunks (load(t): chunk t's QChunk) as one sequence with two
+// chunks of loads in flight (round 5): chunk t is loaded into one of two
+// register sets two chunks before it is staged, so its latency overlaps two
+// chunks' MFMAs.  A head-path launch is latency-bound (C1 trace: 33 us per
+// one-panel launch).  Ends with a barrier: the staging buffers are free.
+// primed(): called once between the prologue's barrier and the loop (a
+// workgroup-timeline mark; nothing in a normal build).
+template <int QT, class Load, class Primed>
+__device__ __forceinline__ void q_pipeline(d4 (&acc)[QT / 32][QT / 32], double (*sW)[BK][QT + 8],
+                                           double (*sP)[BK][QT + 8], int T, Load load,
+                                           Primed primed) {
+  static_assert(NCH % 2 == 0 && NCH >= 4, "two chunks per pipeline turn");
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
-  const int wr = wv & 1, wc = wv >> 1;  // rows 32*wr.., cols 32*wc..
+  const int wr = wv & 1, wc = wv >> 1;
   const int lr = lane & 15, lk = lane >> 4;
-  d4 acc[2][2];
+  const int sk = tid >> 4, sm = (tid & 15) * SM64;  // 2nd half (QT = 64) at sm + SH64
+  auto stage = [&](QChunk<QT> c, int buf) {
 #pragma unroll
-  for (int ci = 0; ci < 2; ++ci)
+    for (int e = 0; e < QT / 32; ++e)
+      *reinterpret_cast<double2 *>(&sW[buf][sk][sm + QT / 2 * e]) = c.w[e];
 #pragma unroll
-    for (int ri = 0; ri < 2; ++ri) {
-      const int64_t r = R0 + 32 * wr + 16 * ri + lr;
-      const int64_t c = C0 + 32 * wc + 16 * ci + lk;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[ci][ri][j] = A[r + (c + 4 * j) * ld];
-    }
-  const int sk = tid >> 4, sm = (tid & 15) * SM64;  // 2nd half at sm + SH64
-  // The npan panels' NCH chunks as one sequence with two chunks of loads in
-  // flight (round 5): chunk t is loaded into one of two register sets two
-  // chunks before it is staged, so its latency overlaps two chunks' MFMAs.
-  // A head-path launch is latency-bound (C1 trace: 33 us per one-panel
-  // launch); the MFMA chain and its k order are unchanged: bit-identical.
-  // Staging registers as named values (an array here was kept in scratch).
-  double2 w00, w01, p00, p01, w10, w11, p10, p11;
-  const int T = npan * NCH;
-#define UQ_LOAD(W0, W1, P0, P1, TT)                                               \
-  do {                                                                            \
-    const int pj_ = (TT) / NCH, ch_ = (TT) - pj_ * NCH;                           \
-    const int64_t off_ = (int64_t)ch_ * BK * ldp;                                 \
-    const double *gW_ = psel(ps.R, pj_) + (R0 + sm) + (int64_t)sk * ldp + off_;   \
-    const double *gP_ = psel(ps.C, pj_) + (C0 + sm) + (int64_t)sk * ldp + off_;   \
-    W0 = *reinterpret_cast<const double2 *>(gW_);                                 \
-    W1 = *reinterpret_cast<const double2 *>(gW_ + SH64);                          \
-    P0 = *reinterpret_cast<const double2 *>(gP_);                                 \
-    P1 = *reinterpret_cast<const double2 *>(gP_ + SH64);                          \
-  } while (0)
-#define UQ_STAGE(W0, W1, P0, P1, BUF)                                             \
-  do {                                                                            \
-    *reinterpret_cast<double2 *>(&sW[BUF][sk][sm]) = W0;                          \
-    *reinterpret_cast<double2 *>(&sW[BUF][sk][sm + SH64]) = W1;                   \
-    *reinterpret_cast<double2 *>(&sP[BUF][sk][sm]) = P0;                          \
-    *reinterpret_cast<double2 *>(&sP[BUF][sk][sm + SH64]) = P1;                   \
-  } while (0)
+    for (int e = 0; e < QT / 32; ++e)
+      *reinterpret_cast<double2 *>(&sP[buf][sk][sm + QT / 2 * e]) = c.p[e];
+  };
   auto mma = [&](int cur) {
 #pragma unroll
     for (int kk = 0; kk < BK / 4; ++kk) {
-      double a[2], b[2];
+      double a[QT / 32], b[QT / 32];
 #pragma unroll
-      for (int ci = 0; ci < 2; ++ci) a[ci] = sP[cur][4 * kk + lk][32 * wc + 16 * ci + lr];
+      for (int ci = 0; ci < QT / 32; ++ci) a[ci] = sP[cur][4 * kk + lk][QT / 2 * wc + 16 * ci + lr];
 #pragma unroll
-      for (int ri = 0; ri < 2; ++ri) b[ri] = sW[cur][4 * kk + lk][32 * wr + 16 * ri + lr];
+      for (int ri = 0; ri < QT / 32; ++ri) b[ri] = sW[cur][4 * kk + lk][QT / 2 * wr + 16 * ri + lr];
 #pragma unroll
-      for (int ci = 0; ci < 2; ++ci)
+      for (int ci = 0; ci < QT / 32; ++ci)
 #pragma unroll
-        for (int ri = 0; ri < 2; ++ri)
+        for (int ri = 0; ri < QT / 32; ++ri)
           acc[ci][ri] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ci], b[ri], acc[ci][ri], 0, 0, 0);
     }
   };
-  static_assert(NCH % 2 == 0 && NCH >= 4, "two chunks per pipeline turn");
-  UQ_LOAD(w00, w01, p00, p01, 0);
-  UQ_STAGE(w00, w01, p00, p01, 0);
-  UQ_LOAD(w10, w11, p10, p11, 1);
-  UQ_LOAD(w00, w01, p00, p01, 2);
+  QChunk<QT> c0 = load(0);
+  stage(c0, 0);
+  QChunk<QT> c1 = load(1);
+  c0 = load(2);
   __syncthreads();
+  primed();
 #pragma unroll 1
   for (int t = 0; t < T; t += 2) {
     mma(0);
-    UQ_STAGE(w10, w11, p10, p11, 1);
-    if (t + 3 < T) UQ_LOAD(w10, w11, p10, p11, t + 3);
+    stage(c1, 1);
+    if (t + 3 < T) c1 = load(t + 3);
     __syncthreads();
     mma(1);
     if (t + 2 < T) {
-      UQ_STAGE(w00, w01, p00, p01, 0);
-      if (t + 4 < T) UQ_LOAD(w00, w01, p00, p01, t + 4);
+      stage(c0, 0);
+      if (t + 4 < T) c0 = load(t + 4);
     }
     __syncthreads();
   }
-#undef UQ_LOAD
-#undef UQ_STAGE
+}
+
+// Lookahead updates of the head path: npan panels from ps on a list of
+// 128-tiles none of which lies in a panel's block (so no copies), the
+// accumulators kept across panels: per element the same chain as k_update /
+// k_update_multi.  blockIdx.x = (4 t + quarter) (XT / QT)^2 + piece; the
+// upper quarter of a diagonal tile too, as k_update computes it.  go: the
+// gather fused into the launch.
+// pivSW: this launch gathers a panel, and the quarter holding that panel's
+// first 64 x 64 diagonal block D_0 also runs its sub-sweep (k_pivot's, into
+// pivSW / piv / flag), one head-path launch less per panel.  QT = 64: from
+// the registers -- the lower values just stored, mirrored, i.e. exactly the
+// S0 snapshot k_pivot would read: bit-identical.  QT = 32: the quarter is
+// finished by its last piece: each piece stores (and gathers) its part,
+// releases it at agent scope and counts into *qctr; the piece that counts
+// last acquires, reads D_0 back from the gathered snapshot S0 -- the same
+// values -- runs the sub-sweep and resets *qctr.  No workgroup waits for
+// another.
+template <int QT>
+__device__ __forceinline__ void update_q(double *__restrict__ A, int64_t ld, const PanelSet &ps,
+                                         int npan, int64_t ldp, const Tile *__restrict__ tiles,
+                                         const GatherOut &go, double *__restrict__ pivSW,
+                                         double *__restrict__ piv, int *__restrict__ flag,
+                                         int *__restrict__ qctr) {
+  ACE_WGT(4, true);
+  constexpr int QL = QT + 8;                   // LDS pitch
+  constexpr int NPC = (XT / QT) * (XT / QT);   // pieces per quarter
+  // sW and sP in one buffer: the D_0 sub-sweep reuses it as its matrix
+  constexpr int NS = 2 * 2 * BK * QL > SUB * (SUB + 2) ? 2 * 2 * BK * QL : SUB * (SUB + 2);
+  __shared__ __attribute__((aligned(16))) double sbuf[NS];
+  double (*sW)[BK][QL] = reinterpret_cast<double (*)[BK][QL]>(sbuf);
+  double (*sP)[BK][QL] = reinterpret_cast<double (*)[BK][QL]>(sbuf + 2 * BK * QL);
+  const Tile tt = tiles[blockIdx.x / (4 * NPC)];
+  if (tt.I < 0) return;  // padding of the XCD order
+  const int q = (blockIdx.x / NPC) & 3, pc = blockIdx.x % NPC;
+  const int64_t Rq = (int64_t)tt.I * UT + XT * (q & 1), Cq = (int64_t)tt.J * UT + XT * (q >> 1);
+  const int64_t R0 = Rq + QT * (pc & 1), C0 = Cq + QT * (pc >> 1);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wv = tid >> 6;
+  const int wr = wv & 1, wc = wv >> 1;
+  const int lr = lane & 15, lk = lane >> 4;
+  d4 acc[QT / 32][QT / 32];
+#pragma unroll
+  for (int ci = 0; ci < QT / 32; ++ci)
+#pragma unroll
+    for (int ri = 0; ri < QT / 32; ++ri) {
+      const int64_t r = R0 + QT / 2 * wr + 16 * ri + lr;
+      const int64_t c = C0 + QT / 2 * wc + 16 * ci + lk;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[ci][ri][j] = A[r + (c + 4 * j) * ld];
+    }
+  const int sk = tid >> 4, sm = (tid & 15) * SM64;
+  // the npan panels' NCH chunks as one sequence.  R0 and C0 are captured by
+  // value and the store loop below is spelled out (no q_each): gput takes
+  // them as 64-bit arguments, and behind a closure's reference their range
+  // (a 32-bit tile index times UT) is hidden from the interprocedural
+  // constant propagation, which then gives every gput user -- k_update,
+  // k_update_pair, k_update_multi* -- the 64-bit form of lcol's division
+  q_pipeline<QT>(
+      acc, sW, sP, npan * NCH,
+      [=](int t) {
+        const int pj = t / NCH, ch = t - pj * NCH;
+        const int64_t off = (int64_t)ch * BK * ldp;
+        return q_load<QT>(psel(ps.R, pj) + (R0 + sm) + (int64_t)sk * ldp + off,
+                          psel(ps.C, pj) + (C0 + sm) + (int64_t)sk * ldp + off);
+      },
+      [] {});
   ACE_WGT_MARK(0);
 #pragma unroll
-  for (int ci = 0; ci < 2; ++ci)
+  for (int ci = 0; ci < QT / 32; ++ci)
 #pragma unroll
-    for (int ri = 0; ri < 2; ++ri) {
-      const int64_t r = R0 + 32 * wr + 16 * ri + lr;
-      const int64_t c = C0 + 32 * wc + 16 * ci + lk;
+    for (int ri = 0; ri < QT / 32; ++ri) {
+      const int64_t r = R0 + QT / 2 * wr + 16 * ri + lr;
+      const int64_t c = C0 + QT / 2 * wc + 16 * ci + lk;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const double v = acc[ci][ri][j];
@@ -2006,323 +2069,105 @@ __global__ __launch_bounds__(256, 4) void k_update_q(double *__restrict__ A, int
         if (go.k0 >= 0) gput(go, r, c + 4 * j, v);
       }
     }
-  // pivSW: this launch gathers a panel, and the quarter holding that panel's
-  // first 64 x 64 diagonal block D_0 also runs its sub-sweep (k_pivot's,
-  // into pivSW / piv / flag) -- the input is the lower values just stored,
-  // mirrored, i.e. exactly the S0 snapshot k_pivot would read: bit-identical,
-  // one head-path launch less per panel
-  if (pivSW && go.k0 >= 0 && R0 == go.k0 && C0 == go.k0) {
-    __shared__ double pv[SUB];
-    double(*M)[SUB + 2] = reinterpret_cast<double(*)[SUB + 2]>(&sbuf[0][0][0][0]);
-    // (the chunk loop ended with a barrier: the staging buffers are free)
-#pragma unroll
-    for (int ci = 0; ci < 2; ++ci)
-#pragma unroll
-      for (int ri = 0; ri < 2; ++ri) {
-        const int a = 32 * wr + 16 * ri + lr;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int c = 32 * wc + 16 * ci + lk + 4 * j;
-          if (a >= c) {
-            M[a][c] = acc[ci][ri][j];
-            M[c][a] = acc[ci][ri][j];
-          }
-        }
+  if (!(pivSW && go.k0 >= 0 && Rq == go.k0 && Cq == go.k0)) return;
+  __shared__ double pv[SUB];
+  double(*M)[SUB + 2] = reinterpret_cast<double(*)[SUB + 2]>(sbuf);
+  double v[SUB / 4];
+  if constexpr (QT == XT) {
+    q_each<QT>(acc, 0, 0, [&](int64_t a, int64_t c, double x) {
+      if (a >= c) {
+        M[a][c] = x;
+        M[c][a] = x;
       }
+    });
     __syncthreads();
-    double v[SUB / 4];
 #pragma unroll
-    for (int q = 0; q < SUB / 4; ++q) v[q] = M[lane][16 * wv + q];
-    ACE_WGT_MARK(1);
-    pivot_sweep_blk<SUB + 2>(v, M, pv, tid);
-    ACE_WGT_MARK(2);
-    pivot_store<4>(v, pv, tid, pivSW, piv, go.k0, flag);
+    for (int qq = 0; qq < SUB / 4; ++qq) v[qq] = M[lane][16 * wv + qq];
+  } else {
+    // the last of the quarter's four pieces runs the sub-sweep
+    __shared__ int last;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      last = __hip_atomic_fetch_add(qctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == NPC - 1;
+      if (last) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        __hip_atomic_store(qctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    __syncthreads();
+    if (!last) return;
+    // D_0 = S0[0:64, 0:64] (row a, column c at a + c SUB), as k_pivot reads it
+#pragma unroll
+    for (int qq = 0; qq < SUB / 4; ++qq)
+      v[qq] = __hip_atomic_load(go.S0 + lane + (16 * wv + qq) * SUB, __ATOMIC_RELAXED,
+                                __HIP_MEMORY_SCOPE_AGENT);
   }
+  ACE_WGT_MARK(1);
+  pivot_sweep_blk<SUB + 2>(v, M, pv, tid);
+  ACE_WGT_MARK(2);
+  pivot_store<4>(v, pv, tid, pivSW, piv, go.k0, flag);
 }
-
-// k_update_q with every 64 x 64 quarter split into four 32 x 32 pieces,
-// one per 256-thread workgroup (each wave one 16 x 16 MFMA block), for the
-// latency-critical head launches of small n (ACE_QSPLIT): four times the
-// workgroups, a quarter of each one's K loop.  Every element's MFMA chain
-// (operands, k order, accumulator start) is k_update_q's: bit-identical.
-// The quarter holding D_0 of a gathered panel is finished by its last
-// piece: each piece stores (and gathers) its part, releases it at agent
-// scope and counts into *qctr; the piece that counts last acquires, reads
-// D_0 back from the gathered snapshot S0 -- the values k_update_q's fused
-// sweep reads from its registers -- runs the sub-sweep and resets *qctr.
-// No workgroup waits for another.
+__global__ __launch_bounds__(256, 4) void k_update_q(double *__restrict__ A, int64_t ld, PanelSet ps,
+                                                  int npan, int64_t ldp,
+                                                  const Tile *__restrict__ tiles, GatherOut go,
+                                                  double *__restrict__ pivSW,
+                                                  double *__restrict__ piv,
+                                                  int *__restrict__ flag) {
+  update_q<XT>(A, ld, ps, npan, ldp, tiles, go, pivSW, piv, flag, nullptr);
+}
 __global__ __launch_bounds__(256, 4) void k_update_q4(double *__restrict__ A, int64_t ld, PanelSet ps,
                                                    int npan, int64_t ldp,
                                                    const Tile *__restrict__ tiles, GatherOut go,
                                                    double *__restrict__ pivSW,
                                                    double *__restrict__ piv,
                                                    int *__restrict__ flag, int *__restrict__ qctr) {
-  ACE_WGT(4, true);
-  constexpr int QT = XT / 2;        // 32: the piece
-  constexpr int QL = QT + 8;        // LDS pitch
-  __shared__ __attribute__((aligned(16))) double sbuf[SUB * (SUB + 2)];  // staging, then D_0
-  static_assert(2 * 2 * BK * QL <= SUB * (SUB + 2), "staging fits");
-  double (*sW)[BK][QL] = reinterpret_cast<double (*)[BK][QL]>(sbuf);
-  double (*sP)[BK][QL] = reinterpret_cast<double (*)[BK][QL]>(sbuf + 2 * BK * QL);
-  __shared__ int last;
-  const Tile tt = tiles[blockIdx.x >> 4];
-  if (tt.I < 0) return;  // padding of the XCD order
-  const int q = (blockIdx.x >> 2) & 3, pc = blockIdx.x & 3;
-  const int64_t Rq = (int64_t)tt.I * UT + XT * (q & 1), Cq = (int64_t)tt.J * UT + XT * (q >> 1);
-  const int64_t R0 = Rq + QT * (pc & 1), C0 = Cq + QT * (pc >> 1);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wv = tid >> 6;
-  const int wr = wv & 1, wc = wv >> 1;  // rows 16*wr.., cols 16*wc.. of the piece
-  const int lr = lane & 15, lk = lane >> 4;
-  d4 acc;
-  {
-    const int64_t r = R0 + 16 * wr + lr;
-    const int64_t c = C0 + 16 * wc + lk;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = A[r + (c + 4 * j) * ld];
-  }
-  const int sk = tid >> 4, sm = (tid & 15) * 2;  // one double2 of each operand per chunk
-  double2 w0, p0, w1, p1;
-  const int T = npan * NCH;
-#define UQ4_LOAD(W, P, TT)                                                         \
-  do {                                                                             \
-    const int pj_ = (TT) / NCH, ch_ = (TT) - pj_ * NCH;                            \
-    const int64_t off_ = (int64_t)ch_ * BK * ldp;                                  \
-    W = *reinterpret_cast<const double2 *>(psel(ps.R, pj_) + (R0 + sm) + (int64_t)sk * ldp + off_); \
-    P = *reinterpret_cast<const double2 *>(psel(ps.C, pj_) + (C0 + sm) + (int64_t)sk * ldp + off_); \
-  } while (0)
-#define UQ4_STAGE(W, P, BUF)                                                       \
-  do {                                                                             \
-    *reinterpret_cast<double2 *>(&sW[BUF][sk][sm]) = W;                            \
-    *reinterpret_cast<double2 *>(&sP[BUF][sk][sm]) = P;                            \
-  } while (0)
-  auto mma = [&](int cur) {
-#pragma unroll
-    for (int kk = 0; kk < BK / 4; ++kk) {
-      const double a = sP[cur][4 * kk + lk][16 * wc + lr];
-      const double b = sW[cur][4 * kk + lk][16 * wr + lr];
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-    }
-  };
-  static_assert(NCH % 2 == 0 && NCH >= 4, "two chunks per pipeline turn");
-  UQ4_LOAD(w0, p0, 0);
-  UQ4_STAGE(w0, p0, 0);
-  UQ4_LOAD(w1, p1, 1);
-  UQ4_LOAD(w0, p0, 2);
-  __syncthreads();
-#pragma unroll 1
-  for (int t = 0; t < T; t += 2) {
-    mma(0);
-    UQ4_STAGE(w1, p1, 1);
-    if (t + 3 < T) UQ4_LOAD(w1, p1, t + 3);
-    __syncthreads();
-    mma(1);
-    if (t + 2 < T) {
-      UQ4_STAGE(w0, p0, 0);
-      if (t + 4 < T) UQ4_LOAD(w0, p0, t + 4);
-    }
-    __syncthreads();
-  }
-#undef UQ4_LOAD
-#undef UQ4_STAGE
-  ACE_WGT_MARK(0);
-  {
-    const int64_t r = R0 + 16 * wr + lr;
-    const int64_t c = C0 + 16 * wc + lk;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      A[r + (c + 4 * j) * ld] = acc[j];
-      if (go.k0 >= 0) gput(go, r, c + 4 * j, acc[j]);
-    }
-  }
-  if (!(pivSW && go.k0 >= 0 && Rq == go.k0 && Cq == go.k0)) return;
-  // the D_0 quarter: the last of its four pieces runs the sub-sweep
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    last = __hip_atomic_fetch_add(qctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 3;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      __hip_atomic_store(qctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  __syncthreads();
-  if (!last) return;
-  __shared__ double pv[SUB];
-  double(*M)[SUB + 2] = reinterpret_cast<double(*)[SUB + 2]>(sbuf);
-  double v[SUB / 4];
-  // D_0 = S0[0:64, 0:64] (row a, column c at a + c SUB), as k_pivot reads it
-#pragma unroll
-  for (int qq = 0; qq < SUB / 4; ++qq)
-    v[qq] = __hip_atomic_load(go.S0 + lane + (16 * wv + qq) * SUB, __ATOMIC_RELAXED,
-                              __HIP_MEMORY_SCOPE_AGENT);
-  ACE_WGT_MARK(1);
-  pivot_sweep_blk<SUB + 2>(v, M, pv, tid);
-  ACE_WGT_MARK(2);
-  pivot_store<4>(v, pv, tid, pivSW, piv, go.k0, flag);
+  update_q<XT / 2>(A, ld, ps, npan, ldp, tiles, go, pivSW, piv, flag, qctr);
 }
 
-// The head path's panel GEMM (run_sweep_heads) on 64 x 64 quarters of the
-// 128-tiles: W_I,J = Pn_I W_kk[:, J] as k_panel_gemm_t, a quarter of its work
-// per 256-thread workgroup.  The head launches hold few tiles (the rows of
-// the next group's blocks) and k_panel_gemm_t's 8.4 MFLOP per workgroup is a
-// CU's MFMA peak for ~27 us (C1 marks: K loop 32 us); quartered, four times
-// the CUs share it.  Operand roles (A from W_kk, B from Pn), k order and the
-// zero start are k_panel_gemm_t's: bit-identical.  Grid: (64-row blocks of
-// row tiles [rt0, rt1), NB / 64 column blocks); k_update_q's two-deep load
-// pipeline.
+// The head path's panel GEMM: W_I,J = Pn_I W_kk[:, J] as k_panel_gemm_t, on
+// QT x QT pieces.  The head launches hold few tiles (the rows of the next
+// group's blocks) and k_panel_gemm_t's 8.4 MFLOP per workgroup is a CU's
+// MFMA peak for ~27 us (C1 marks: K loop 32 us); quartered, four times the
+// CUs share it.  Operand roles (A from W_kk, B from Pn), k order and the
+// zero start are k_panel_gemm_t's: bit-identical.  Grid: (QT-row blocks of
+// row tiles [rt0, rt1), NB / QT column blocks).
+template <int QT>
+__device__ __forceinline__ void panel_gemm_q(double *__restrict__ W, const double *__restrict__ Pn,
+                                             int64_t ldp, int64_t k0, int rt0) {
+  ACE_WGT(3, true);
+  __shared__ __attribute__((aligned(16))) double sW[2][BK][QT + 8];  // Pn rows of the piece
+  __shared__ __attribute__((aligned(16))) double sP[2][BK][QT + 8];  // W_kk rows c
+  const int64_t R0 = (int64_t)rt0 * UT + (int64_t)blockIdx.x * QT, C0 = (int64_t)blockIdx.y * QT;
+  if (R0 >= k0 && R0 < k0 + NB) return;  // pivot rows are already final
+  const int sk = threadIdx.x >> 4, sm = (threadIdx.x & 15) * SM64;
+  const double *gW = Pn + (R0 + sm) + (int64_t)sk * ldp;
+  const double *gP = W + (k0 + C0 + sm) + (int64_t)sk * ldp;  // W_kk(c, k) = W[k0 + c, k]
+  d4 acc[QT / 32][QT / 32];
+#pragma unroll
+  for (int ci = 0; ci < QT / 32; ++ci)
+#pragma unroll
+    for (int ri = 0; ri < QT / 32; ++ri) acc[ci][ri] = d4{0.0, 0.0, 0.0, 0.0};
+  q_pipeline<QT>(
+      acc, sW, sP, NCH,
+      [&](int ch) {
+        const int64_t off = (int64_t)ch * BK * ldp;
+        return q_load<QT>(gW + off, gP + off);
+      },
+      [&] { ACE_WGT_MARK(0); });
+  ACE_WGT_MARK(1);
+  q_each<QT>(acc, R0, C0, [&](int64_t r, int64_t c, double v) { W[r + c * ldp] = v; });
+}
 __global__ __launch_bounds__(256, 4) void k_panel_gemm_q(double *__restrict__ W,
                                                        const double *__restrict__ Pn,
                                                        int64_t ldp, int64_t k0, int rt0) {
-  ACE_WGT(3, true);
-  __shared__ __attribute__((aligned(16))) double sW[2][BK][XL];  // Pn rows of the quarter
-  __shared__ __attribute__((aligned(16))) double sP[2][BK][XL];  // W_kk rows c
-  const int64_t R0 = (int64_t)rt0 * UT + (int64_t)blockIdx.x * XT, C0 = (int64_t)blockIdx.y * XT;
-  if (R0 >= k0 && R0 < k0 + NB) return;  // pivot rows are already final
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wv = tid >> 6;
-  const int wr = wv & 1, wc = wv >> 1;  // rows 32*wr.., cols 32*wc..
-  const int lr = lane & 15, lk = lane >> 4;
-  const int sk = tid >> 4, sm = (tid & 15) * SM64;  // 2nd half at sm + SH64
-  const double *gW = Pn + (R0 + sm) + (int64_t)sk * ldp;
-  const double *gP = W + (k0 + C0 + sm) + (int64_t)sk * ldp;  // W_kk(c, k) = W[k0 + c, k]
-  d4 acc[2][2];
-#pragma unroll
-  for (int ci = 0; ci < 2; ++ci)
-#pragma unroll
-    for (int ri = 0; ri < 2; ++ri) acc[ci][ri] = d4{0.0, 0.0, 0.0, 0.0};
-  double2 w00, w01, p00, p01, w10, w11, p10, p11;
-#define PQ_LOAD(W0, W1, P0, P1, CH)                                               \
-  do {                                                                            \
-    const int64_t off_ = (int64_t)(CH) * BK * ldp;                                \
-    W0 = *reinterpret_cast<const double2 *>(gW + off_);                           \
-    W1 = *reinterpret_cast<const double2 *>(gW + off_ + SH64);                    \
-    P0 = *reinterpret_cast<const double2 *>(gP + off_);                           \
-    P1 = *reinterpret_cast<const double2 *>(gP + off_ + SH64);                    \
-  } while (0)
-#define PQ_STAGE(W0, W1, P0, P1, BUF)                                             \
-  do {                                                                            \
-    *reinterpret_cast<double2 *>(&sW[BUF][sk][sm]) = W0;                          \
-    *reinterpret_cast<double2 *>(&sW[BUF][sk][sm + SH64]) = W1;                   \
-    *reinterpret_cast<double2 *>(&sP[BUF][sk][sm]) = P0;                          \
-    *reinterpret_cast<double2 *>(&sP[BUF][sk][sm + SH64]) = P1;                   \
-  } while (0)
-  auto mma = [&](int cur) {
-#pragma unroll
-    for (int kk = 0; kk < BK / 4; ++kk) {
-      double a[2], b[2];
-#pragma unroll
-      for (int ci = 0; ci < 2; ++ci) a[ci] = sP[cur][4 * kk + lk][32 * wc + 16 * ci + lr];
-#pragma unroll
-      for (int ri = 0; ri < 2; ++ri) b[ri] = sW[cur][4 * kk + lk][32 * wr + 16 * ri + lr];
-#pragma unroll
-      for (int ci = 0; ci < 2; ++ci)
-#pragma unroll
-        for (int ri = 0; ri < 2; ++ri)
-          acc[ci][ri] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ci], b[ri], acc[ci][ri], 0, 0, 0);
-    }
-  };
-  static_assert(NCH % 2 == 0 && NCH >= 4, "two chunks per pipeline turn");
-  PQ_LOAD(w00, w01, p00, p01, 0);
-  PQ_STAGE(w00, w01, p00, p01, 0);
-  PQ_LOAD(w10, w11, p10, p11, 1);
-  PQ_LOAD(w00, w01, p00, p01, 2);
-  __syncthreads();
-  ACE_WGT_MARK(0);
-#pragma unroll 1
-  for (int ch = 0; ch < NCH; ch += 2) {
-    mma(0);
-    PQ_STAGE(w10, w11, p10, p11, 1);
-    if (ch + 3 < NCH) PQ_LOAD(w10, w11, p10, p11, ch + 3);
-    __syncthreads();
-    mma(1);
-    if (ch + 2 < NCH) {
-      PQ_STAGE(w00, w01, p00, p01, 0);
-      if (ch + 4 < NCH) PQ_LOAD(w00, w01, p00, p01, ch + 4);
-    }
-    __syncthreads();
-  }
-#undef PQ_LOAD
-#undef PQ_STAGE
-  ACE_WGT_MARK(1);
-#pragma unroll
-  for (int ci = 0; ci < 2; ++ci)
-#pragma unroll
-    for (int ri = 0; ri < 2; ++ri) {
-      const int64_t rr = R0 + 32 * wr + 16 * ri + lr;
-      const int64_t c = C0 + 32 * wc + 16 * ci + lk;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) W[rr + (c + 4 * j) * ldp] = acc[ci][ri][j];
-    }
+  panel_gemm_q<XT>(W, Pn, ldp, k0, rt0);
 }
-
-// k_panel_gemm_q on 32 x 32 pieces (ACE_QSPLIT, small n): each wave one
-// 16 x 16 MFMA block, four times the workgroups; every element's chain is
-// k_panel_gemm_q's (bit-identical).  Grid: (2 x 64-row blocks, 2 NB / 64).
 __global__ __launch_bounds__(256, 4) void k_panel_gemm_q4(double *__restrict__ W,
                                                         const double *__restrict__ Pn,
                                                         int64_t ldp, int64_t k0, int rt0) {
-  ACE_WGT(3, true);
-  constexpr int QT = XT / 2, QL = QT + 8;
-  __shared__ __attribute__((aligned(16))) double sW[2][BK][QL];  // Pn rows of the piece
-  __shared__ __attribute__((aligned(16))) double sP[2][BK][QL];  // W_kk rows c
-  const int64_t R0 = (int64_t)rt0 * UT + (int64_t)blockIdx.x * QT, C0 = (int64_t)blockIdx.y * QT;
-  if (R0 >= k0 && R0 < k0 + NB) return;  // pivot rows are already final
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wv = tid >> 6;
-  const int wr = wv & 1, wc = wv >> 1;  // rows 16*wr.., cols 16*wc..
-  const int lr = lane & 15, lk = lane >> 4;
-  const int sk = tid >> 4, sm = (tid & 15) * 2;
-  const double *gW = Pn + (R0 + sm) + (int64_t)sk * ldp;
-  const double *gP = W + (k0 + C0 + sm) + (int64_t)sk * ldp;  // W_kk(c, k) = W[k0 + c, k]
-  d4 acc = d4{0.0, 0.0, 0.0, 0.0};
-  double2 w0, p0, w1, p1;
-#define PQ4_LOAD(WW, PP, CH)                                                        \
-  do {                                                                              \
-    const int64_t off_ = (int64_t)(CH) * BK * ldp;                                  \
-    WW = *reinterpret_cast<const double2 *>(gW + off_);                             \
-    PP = *reinterpret_cast<const double2 *>(gP + off_);                             \
-  } while (0)
-#define PQ4_STAGE(WW, PP, BUF)                                                      \
-  do {                                                                              \
-    *reinterpret_cast<double2 *>(&sW[BUF][sk][sm]) = WW;                            \
-    *reinterpret_cast<double2 *>(&sP[BUF][sk][sm]) = PP;                            \
-  } while (0)
-  auto mma = [&](int cur) {
-#pragma unroll
-    for (int kk = 0; kk < BK / 4; ++kk) {
-      const double a = sP[cur][4 * kk + lk][16 * wc + lr];
-      const double b = sW[cur][4 * kk + lk][16 * wr + lr];
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-    }
-  };
-  PQ4_LOAD(w0, p0, 0);
-  PQ4_STAGE(w0, p0, 0);
-  PQ4_LOAD(w1, p1, 1);
-  PQ4_LOAD(w0, p0, 2);
-  __syncthreads();
-  ACE_WGT_MARK(0);
-#pragma unroll 1
-  for (int ch = 0; ch < NCH; ch += 2) {
-    mma(0);
-    PQ4_STAGE(w1, p1, 1);
-    if (ch + 3 < NCH) PQ4_LOAD(w1, p1, ch + 3);
-    __syncthreads();
-    mma(1);
-    if (ch + 2 < NCH) {
-      PQ4_STAGE(w0, p0, 0);
-      if (ch + 4 < NCH) PQ4_LOAD(w0, p0, ch + 4);
-    }
-    __syncthreads();
-  }
-#undef PQ4_LOAD
-#undef PQ4_STAGE
-  ACE_WGT_MARK(1);
-  const int64_t rr = R0 + 16 * wr + lr;
-  const int64_t c = C0 + 16 * wc + lk;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) W[rr + (c + 4 * j) * ldp] = acc[j];
+  panel_gemm_q<XT / 2>(W, Pn, ldp, k0, rt0);
 }
 
 // ---------------------------------------------------------------- sharded panel
@@ -2424,12 +2269,8 @@ __global__ __launch_bounds__(256) void k_unpack_panel(const double *__restrict__
 // ACE_CHAIN=0 selects the row-group k_panel (A/B switch; k_panel_split is
 // the default and bit-identical).
 static bool panel_split() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_CHAIN");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_CHAIN", 1) != 0;
+  return v;
 }
 
 // ACE_CHAIN_FUSE=1 (default): at small n (the bulk-reserve schedule) each
@@ -2437,23 +2278,15 @@ static bool panel_split() {
 // (bit-identical; C1 3.60 -> 3.52 ms, profiles/r06_chain_fuse_ab.txt); 0: four
 // k_panel_split launches
 static bool chain_fuse() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_CHAIN_FUSE");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_CHAIN_FUSE", 1) != 0;
+  return v;
 }
 
 // ACE_PGEMM_TILES=0 selects the 64-row k_panel_gemm (A/B switch; the tile
 // form k_panel_gemm_t is the default and bit-identical)
 static bool pgemm_tiles() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_PGEMM_TILES");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_PGEMM_TILES", 1) != 0;
+  return v;
 }
 
 // ACE_DIAG_SKIP (compile-time, timing diagnostics only -- the results are
@@ -2506,12 +2339,8 @@ static void panel_chain(const double *Pn, double *W, int64_t ld, int64_t k0, dou
 // ACE_XGATHER: pair steps fuse each panel's gather into the lookahead cross
 // launch that writes its column block (GatherOut; default 1)
 static bool xgather() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_XGATHER");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_XGATHER", 1) != 0;
+  return v;
 }
 
 // gathered: P, W and S[0] of this panel were written by the cross launch
@@ -2558,26 +2387,18 @@ double sweep_flops(int64_t naug, int64_t npad) {
 }
 
 int update_order_block() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_UPD_ORDER");
-    // 2 with two steps per launch (K = 512 panels per tile): 78.7-78.9 ms
-    // per C2 evaluation against 79.1-79.2 at 4, 79.6-79.7 at 3, 81.1-81.2
-    // at 8, 79.1-79.5 at 1 and at 0 (row-major); profiles/r02_chain_ab.txt
-    v = e ? std::max(0, atoi(e)) : 2;
-  }
+  // 2 with two steps per launch (K = 512 panels per tile): 78.7-78.9 ms
+  // per C2 evaluation against 79.1-79.2 at 4, 79.6-79.7 at 3, 81.1-81.2
+  // at 8, 79.1-79.5 at 1 and at 0 (row-major); profiles/r02_chain_ab.txt
+  static const int v = std::max(0, env_int("ACE_UPD_ORDER", 2));
   return v;
 }
 
 bool cross_update_on_tiles() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_XUPD");
-    // 1: -0.2 ms per C2 evaluation against k_update_x (same box, 2 rounds:
-    // 81.03 / 81.26 vs 81.25 / 81.49 ms); bit-identical
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  // 1: -0.2 ms per C2 evaluation against k_update_x (same box, 2 rounds:
+  // 81.03 / 81.26 vs 81.25 / 81.49 ms); bit-identical
+  static const bool v = env_int("ACE_XUPD", 1) != 0;
+  return v;
 }
 
 std::vector<Tile> cross_update_tiles(int64_t naug, int steps, std::vector<int64_t> &off) {
@@ -2604,12 +2425,8 @@ std::vector<Tile> cross_update_tiles(int64_t naug, int steps, std::vector<int64_
 // -0.15 ms per C2 evaluation once the side chain is off the critical path
 // (profiles/r02_chain_ab.txt)
 bool tail_sort() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_TAIL_SORT");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_TAIL_SORT", 1) != 0;
+  return v;
 }
 
 std::vector<Tile> pair_bulk_orders(int64_t naug, int steps, int64_t *len, int G, int r, int Z) {
@@ -2653,14 +2470,10 @@ std::vector<Tile> pair_bulk_orders(int64_t naug, int steps, int64_t *len, int G,
 }
 
 int sweep_group() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_GROUP");
-    // 4 with the head / tail lookahead (run_sweep_heads, default): 75.9
-    // against 76.6 ms per C2 evaluation at 2 (same box, 4 runs each,
-    // profiles/r03_v5_heads_ab.txt)
-    v = e ? std::min(4, std::max(2, atoi(e))) : 4;
-  }
+  // 4 with the head / tail lookahead (run_sweep_heads, default): 75.9
+  // against 76.6 ms per C2 evaluation at 2 (same box, 4 runs each,
+  // profiles/r03_v5_heads_ab.txt)
+  static const int v = std::min(4, std::max(2, env_int("ACE_GROUP", 4)));
   return v;
 }
 
@@ -2669,29 +2482,22 @@ int sweep_group() {
 // 3.87 at Z = 2 -- a shorter last bulk launch and an earlier first one,
 // profiles/r05_v11_ab_c1_group.txt), 4 above
 int sweep_group_n(int64_t naug) {
-  if (getenv("ACE_GROUP")) return sweep_group();
+  static const bool set = env_set("ACE_GROUP");
+  if (set) return sweep_group();
   return naug <= ACE_BULK_RESERVE_N + AUG ? 3 : 4;
 }
 
 bool pair_steps() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_PAIR");
-    // 1: 81.4 -> 79.5 ms per C2 evaluation (profiles/r02_chain_ab.txt)
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  // 1: 81.4 -> 79.5 ms per C2 evaluation (profiles/r02_chain_ab.txt)
+  static const bool v = env_int("ACE_PAIR", 1) != 0;
+  return v;
 }
 
 // ACE_SIDE2: pair steps run the second block's lookahead cross on a second
 // side stream, concurrently with the first block's panel chain (default 1)
 static bool side2_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_SIDE2");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_SIDE2", 1) != 0;
+  return v;
 }
 
 std::vector<Tile> pair_cross_tiles(int64_t naug, int steps, std::vector<int64_t> &off, int Z) {
@@ -2851,12 +2657,8 @@ static int64_t hilbert_index(int64_t n, int64_t x, int64_t y) {
 }
 
 bool bulk_curve() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_BULK_CURVE");
-    v = e ? (atoi(e) != 0) : 0;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_BULK_CURVE", 0) != 0;
+  return v;
 }
 
 std::vector<Tile> curve_update_order(const std::vector<Tile> &tl,
@@ -2899,12 +2701,8 @@ std::vector<Tile> curve_update_order(const std::vector<Tile> &tl,
 
 // Two-panel launches on k_update_multi (default; ACE_MULTI2=0: k_update_pair)
 static bool multi2_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_MULTI2");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_MULTI2", 1) != 0;
+  return v;
 }
 
 // Z = b.Z sweep steps per bulk launch (Z = 2 is the round-2 pair form).
@@ -3039,12 +2837,8 @@ static hipError_t run_sweep_groups(const SweepBufs &b, hipStream_t st, const Swe
 // ACE_HEADS=1: the group schedule with its lookahead split into a head path
 // and a tail path (run_sweep_heads)
 bool heads_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_HEADS");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_HEADS", 1) != 0;
+  return v;
 }
 
 // The group schedule with the lookahead split by what the next chain needs
@@ -3117,10 +2911,7 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
   };
   // head-path launches on Q lists: 64 x 64 quarters (k_update_q, ACE_HEADQ=1,
   // default) or the 128-tile kernels
-  static const bool hq = [] {
-    const char *e = getenv("ACE_HEADQ");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool hq = env_int("ACE_HEADQ", 1) != 0;
   // panels k >= 1 are gathered by k_update_q launches, which sweep their D_0
   // (the blocked pivot only: the same code as k_pivot's, bit-identical)
   const bool fused_pivot = hq && ACE_PIVOT_BLK;
@@ -3131,10 +2922,7 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
   // them, 3 the Q launches only, 2 the group-boundary Q only, 0 none.  One
   // D_0 counter per panel after the chain counters (zero when allocated,
   // reset by the last piece).
-  static const int qsplit = [] {
-    const char *e = getenv("ACE_QSPLIT");
-    return e ? atoi(e) : 1;
-  }();
+  static const int qsplit = env_int("ACE_QSPLIT", 1);
   int *const qctr = (qsplit > 0 && b.bq && b.breserve > 0)
                         ? b.bq + (int64_t)((steps + Z - 1) / Z) * BQ_INTS + 2 * steps
                         : nullptr;
@@ -3202,18 +2990,9 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
   // Placement only: bit-identical.  ACE_CHAIN_XLDS=B overrides the bytes (0:
   // off), ACE_CHAIN_XLDS_J the panel mask within a group (default all),
   // ACE_CHAIN_XLDS_G0=0 leaves group 0's chains (beside the assembly) as they were.
-  static const unsigned xlds = [] {
-    const char *e = getenv("ACE_CHAIN_XLDS");
-    return e ? (unsigned)std::max(0, atoi(e)) : 13312u;
-  }();
-  static const int xlds_j = [] {
-    const char *e = getenv("ACE_CHAIN_XLDS_J");
-    return e ? atoi(e) : -1;
-  }();
-  static const bool xlds_g0 = [] {
-    const char *e = getenv("ACE_CHAIN_XLDS_G0");
-    return !(e && atoi(e) == 0);
-  }();
+  static const unsigned xlds = (unsigned)std::max(0, env_int("ACE_CHAIN_XLDS", 13312));
+  static const int xlds_j = env_int("ACE_CHAIN_XLDS_J", -1);
+  static const bool xlds_g0 = env_int("ACE_CHAIN_XLDS_G0", 1) != 0;
   auto chain = [&](int k, hipStream_t s_) {  // [pivot +] sub-steps of panel k (gathered)
     const int j = k % Z, G = k / Z;
     panel_chain(b.P[slot(k)], b.W[slot(k)], b.ld, (int64_t)k * NB, b.SW, b.S, b.piv, b.flag, 1, 0,
@@ -3247,10 +3026,7 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
   // after the tail path's last T update (Et(G), an event slot the direct-wait
   // schedule leaves free); the next group's Q then follows it in stream order
   // and waits for the tail path through Et(G) instead of E2(G)
-  static const bool tail_last_on = [] {
-    const char *e = getenv("ACE_TAIL_LAST");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool tail_last_on = env_int("ACE_TAIL_LAST", 1) != 0;
   // (small n: the chain-bound schedule with the bulk queue)
   auto tlast = [&](int G) {
     return tail_last_on && qdirect && b.bq && b.breserve > 0 && zsize(G) >= 2 &&
@@ -3427,10 +3203,7 @@ hipError_t run_sweep(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
   const int steps = (int)(b.npad / NB);
   // ACE_LOOKAHEAD=0: one stream, no lookahead (diagnostic: the chain
   // kernels then run alone, uncontended)
-  static const int look = [] {
-    const char *e = getenv("ACE_LOOKAHEAD");
-    return e ? atoi(e) : 1;
-  }();
+  static const int look = env_int("ACE_LOOKAHEAD", 1);
   const bool two = look && sy && sy->side && sy->nev >= 2 * steps + 1;
   hipStream_t side = two ? sy->side : st;
   int used = 0;

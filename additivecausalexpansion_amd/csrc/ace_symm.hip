@@ -280,12 +280,8 @@ __global__ __launch_bounds__(512, 2) void k_trmm_lower(const double *__restrict_
 }
 
 static bool trmm_big() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("ACE_TRMM_BIG");
-    v = e ? (atoi(e) != 0) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("ACE_TRMM_BIG", 1) != 0;
+  return v;
 }
 
 hipError_t launch_trmm_lower(const double *A, int64_t ld, int64_t n, const double *V, int64_t ldv,
