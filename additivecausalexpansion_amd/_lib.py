@@ -100,6 +100,14 @@ SIGNATURES = {
     "ace_model_robust_treatment": (ctypes.c_int, [_vp, _D, _I64, _D, _D, _D, ctypes.c_double,
                                                   ctypes.c_double, ctypes.c_int, _D, _D, _D, _D,
                                                   _I32, _D, ctypes.POINTER(_I64)]),
+    "ace_model_coef_posterior": (ctypes.c_int, [_vp, _D, _I64, _D, _D, _D]),
+    "ace_model_coef_cross": (ctypes.c_int, [_vp, _D, _I64, _D, _D]),
+    "ace_coef_contract": (ctypes.c_int, [_I64, ctypes.c_int, _I64, _D, _D, _D, ctypes.c_double,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, _D, _D,
+                                         _D]),
+    "ace_model_predict_surface": (ctypes.c_int, [_vp, _D, _I64, _D, _I64, _D, ctypes.c_int,
+                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                 _D, _D, _D]),
     "ace_model_profile": (ctypes.c_int, [_vp, ctypes.c_int]),
     "ace_model_kernel_time": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                              ctypes.POINTER(_I64),

@@ -265,4 +265,35 @@ int ace_robust_levels(int64_t nx, const double *var, int n_steps, double *thresh
   return ACE_OK;
 }
 
+// A coefficient posterior contracted with nz weight rows: the tails of
+// pred_cpp / pred_marginal_cpp (src/pred_cpp.cpp:20-29, 70-78) at every
+// (point c, row j), output index c + nx j
+int ace_coef_contract(int64_t nx, int B, int64_t nz, const double *mean, const double *cov,
+                      const double *W, double offset, double scale, double shift, double noise,
+                      double *map, double *ci, double *var) {
+  if (nx < 1 || nz < 1 || B < 1 || !mean || !cov || !W || !map || !ci || !var) return ACE_ERR_ARG;
+  const int64_t N = nx * nz;
+  std::vector<double> wj((size_t)B);
+  for (int64_t j = 0; j < nz; ++j) {
+    for (int b = 0; b < B; ++b) wj[(size_t)b] = W[j + nz * b];
+    for (int64_t c = 0; c < nx; ++c) {
+      double a = 0.0, q = 0.0;
+      for (int b = 0; b < B; ++b) a += wj[(size_t)b] * mean[c + nx * b];
+      for (int b2 = 0; b2 < B; ++b2) {
+        double t = 0.0;
+        for (int b = 0; b < B; ++b) t += wj[(size_t)b] * cov[c + nx * (b + (int64_t)B * b2)];
+        q += t * wj[(size_t)b2];
+      }
+      const int64_t e = c + nx * j;
+      const double yx = offset + scale * (a + shift);
+      const double sd = scale * std::sqrt(std::fabs(q + noise));
+      map[e] = yx;
+      ci[e] = yx - 1.96 * sd;
+      ci[e + N] = yx + 1.96 * sd;
+      var[e] = std::pow(sd, 2);
+    }
+  }
+  return ACE_OK;
+}
+
 }  // extern "C"

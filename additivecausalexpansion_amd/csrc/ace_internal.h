@@ -115,6 +115,12 @@ bool cross_mm_lds_ok(int PM, int B, int kind);
 // mode 2 without a cube on the MFMA r2 expansion (k_cross_mm): R.n x C.n, ld
 hipError_t launch_cross_mm(int kind, int PM, PairSide R, PairSide C, int B, int ZS, TabView tab,
                            int b0, int b1, double *out, int64_t ld, hipStream_t st);
+// Per-slice cross kernels without the row side's basis factor
+// (k_cross_slices_mm): slice b of row r at out[(r + R.n b) + c ld], b < B;
+// each element as launch_cross_mm gives it for slices [b, b + 1) and a row
+// side of ones.  R.Z / R.LZ are not read.
+hipError_t launch_cross_slices_mm(int kind, int PM, PairSide R, PairSide C, int B, int ZS,
+                                  TabView tab, double *out, int64_t ld, hipStream_t st);
 // Grouped test-kernel sums (k_group_mm): R (S.n x G, ld S.n) = Km E for the
 // marginal kernel Km of slices [b0, b1) on the points S and the indicator
 // E[c][h] = (label[c] == h), labels in [-1, G), 1 <= G <= 64; Km is never
@@ -456,6 +462,18 @@ hipError_t launch_trmm_lower(const double *A, int64_t ld, int64_t n, const doubl
 hipError_t launch_pred_cols_tri(const double *Y, int64_t ldt, const double *K, int64_t ldk,
                                 int64_t n, int64_t nx, const double *sv, const double *D, double *a,
                                 double *d, hipStream_t st);
+// Coefficient Gram sums of a chunk of ncx test points (k_coef_gram): Kc the
+// (ncx B) x n per-slice cross kernels (row c + ncx b, ld ldk), W the n x
+// (ncx B) product with the inverse (ld ldw): Y = L Kc^T with D, vec = S w
+// (tri), or T' = S Kc^T with vec = w.  res (ncx B (B + 1)):
+// res[c + ncx (b + B b')] = (Kc_c S Kc_c^T)[b][b'], exactly symmetric, then
+// res[ncx B B + c + ncx b] = Kc_c S w.  part: coef_gram_work(n, ncx, B)
+// doubles.  The training points are split by n alone and the partials added
+// in a fixed order: bitwise reproducible, whatever the chunking.
+int64_t coef_gram_work(int64_t n, int64_t ncx, int B);
+hipError_t launch_coef_gram(bool tri, const double *Kc, int64_t ldk, const double *W, int64_t ldw,
+                            int64_t n, int64_t ncx, int B, const double *vec, const double *D,
+                            double *part, double *res, hipStream_t st);
 // D[q] = scale * A[q + q ld], q < n
 hipError_t launch_diag_scaled(const double *A, int64_t ld, int64_t n, double scale, double *D,
                               hipStream_t st);

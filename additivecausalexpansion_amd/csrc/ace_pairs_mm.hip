@@ -1640,6 +1640,140 @@ hipError_t launch_cross_mm(int kind, int PM, PairSide R, PairSide C, int B, int 
 }
 
 // ---------------------------------------------------------------------------
+// Per-slice cross kernels without the row side's basis factor (the
+// coefficient posterior, ace_predict.cpp): Kc_b(x_r, X_c) = k_b(x_r, X_c)
+// beta_b(Z_c) for every slice b < B, slice b of row r at out[(r + R.n b) +
+// c ld] -- the (R.n B) x C.n matrix whose row block b is slice b.  The tile
+// of k_cross_mm with z_r = 1, log|z_r| = 0 for every slice (kval_nb's form of
+// slice 0), so each element has the bits k_cross_mm gives for slices
+// [b, b + 1) and a row side of ones (0 + k included); the tile's points,
+// weights and all B slice norms are staged once, not once per slice.  R.Z /
+// R.LZ are not read.
+// ---------------------------------------------------------------------------
+template <int PM, int KIND>
+__global__ __launch_bounds__(256, PM <= 32 ? 4 : 2) void k_cross_slices_mm(
+    PairSide R, PairSide C, int B, int ZS, TabView tab, double *__restrict__ out, int64_t ld) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  constexpr int XP = xj_pitch(PM);
+  const int64_t J = blockIdx.x, I = blockIdx.y;
+  const int64_t R0 = I * AT, C0 = J * AT;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+  const MmLayout o = mm_layout(PM, B, KIND, false);
+  double *const E = lds + o.etab, *const XJ = lds + o.xj, *const Zc = lds + o.z + 64,
+               *const LZc = lds + o.lz + 64, *const Nc = lds + o.nc, *const Nr = lds + o.nr,
+               *const W = lds + o.w, *const XI = lds + o.total;
+  for (int e = tid; e < 64 * PM; e += 256) {
+    const int c = e / PM, i = e - c * PM;
+    XJ[c * XP + i] = (C0 + c < C.n) ? C.X[(C0 + c) * PM + i] : 0.0;
+    XI[c * XP + i] = (R0 + c < R.n) ? R.X[(R0 + c) * PM + i] : 0.0;
+  }
+  for (int e = tid; e < (B - 1) * 64; e += 256) {
+    const int bb = e >> 6, c = e & 63;
+    const bool ok = C0 + c < C.n;
+    Zc[e] = ok ? C.Z[(C0 + c) * ZS + bb] : 0.0;
+    if (KIND == 0) LZc[e] = ok ? C.LZ[(C0 + c) * ZS + bb] : 0.0;
+  }
+  if (tid < 64) {  // slice 0: z = 1, log|z| = 0
+    Zc[tid - 64] = 1.0;
+    if (KIND == 0) LZc[tid - 64] = 0.0;
+    if (ACE_ASM_EXP == 2) E[tid] = kExp2Tab64[tid];
+    else if (tid < 32) E[tid] = kExp2Tab[tid];
+  }
+  for (int e = tid; e < B * PM; e += 256) W[e] = tab.wk[e];
+  __syncthreads();
+  for (int e = tid; e < 2 * B * 64; e += 256) {
+    const int side = e / (B * 64), rem = e - side * B * 64;
+    const int sl = rem >> 6, pt = rem & 63;
+    const double *wv = W + sl * PM;
+    const double *x = (side == 0 ? XJ : XI) + pt * XP;
+    double s = 0.0;
+#pragma unroll 4
+    for (int i = 0; i < PM; ++i) s = fma(x[i] * x[i], wv[i], s);
+    (side == 0 ? Nc : Nr)[rem] = s;
+  }
+  __syncthreads();
+  const int rl = 16 * w + lr;
+  const int64_t r = R0 + rl;
+  const bool rok = r < R.n;
+  RowX<PM> xr;
+  xr.load(XI + rl * XP, lk);
+  for (int b = 0; b < B; ++b) {
+    d4 acc[4];
+    gemm1_mm<XP, 4>(XJ, xr, W + b * PM, lr, lk, acc, 0);
+    const double sr = Nr[b * 64 + rl];
+    const double *nc = Nc + b * 64;
+    const double *zcol = Zc + (b - 1) * 64, *lzcol = LZc + (b - 1) * 64;
+    const double lam = tab.lam[b];
+    // every pair of the slice in one basic block (see kval_nb); the stores
+    // follow the loop
+    double kf[4][4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int cl = 16 * cb + lk + 4 * v;
+        constexpr double R2MIN = KIND == 1 ? 1e-300 : 0.0;
+        const double r2 = fmax(fma(-2.0, acc[cb][v], sr + nc[cl]), R2MIN);
+        const double zc = zcol[cl];
+        const double lzc = KIND == 0 ? lzcol[cl] : 0.0;
+        kf[cb][v] = 0.0 + kval_nb<KIND>(r2, lam, 1.0, zc, 0.0, lzc, E);
+        MM_PAIR_FENCE(cb, v);
+      }
+    // the values are pinned here: used only under the stores' conditions,
+    // each pair's math would otherwise sink into its store's block (a block
+    // per pair again: 128 VGPRs with 73 - 126 spills at PM <= 32)
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) asm volatile("" : "+v"(kf[cb][v]));
+    if (rok) {
+      double *const ob = out + r + R.n * b;
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int64_t c = C0 + 16 * cb + lk + 4 * v;
+          if (c < C.n) ob[c * ld] = kf[cb][v];
+        }
+    }
+  }
+}
+
+template <int PM>
+static hipError_t cross_slices_mm_pm(int kind, PairSide R, PairSide C, int B, int ZS, TabView tab,
+                                     double *out, int64_t ld, hipStream_t st) {
+  if (R.n <= 0 || C.n <= 0) return hipSuccess;
+  const size_t lds = cross_mm_lds(PM, B, kind);
+  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  const void *f = kind == 0 ? (const void *)k_cross_slices_mm<PM, 0>
+                            : (const void *)k_cross_slices_mm<PM, 1>;
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  const dim3 grid((unsigned)((C.n + AT - 1) / AT), (unsigned)((R.n + AT - 1) / AT));
+  if (kind == 0)
+    hipLaunchKernelGGL((k_cross_slices_mm<PM, 0>), grid, dim3(256), lds, st, R, C, B, ZS, tab, out, ld);
+  else
+    hipLaunchKernelGGL((k_cross_slices_mm<PM, 1>), grid, dim3(256), lds, st, R, C, B, ZS, tab, out, ld);
+  return hipGetLastError();
+}
+
+hipError_t launch_cross_slices_mm(int kind, int PM, PairSide R, PairSide C, int B, int ZS,
+                                  TabView tab, double *out, int64_t ld, hipStream_t st) {
+  switch (PM) {
+#define ACE_CASE(P) \
+  case P: return cross_slices_mm_pm<P>(kind, R, C, B, ZS, tab, out, ld, st);
+    ACE_CASE(4) ACE_CASE(8) ACE_CASE(12) ACE_CASE(16) ACE_CASE(20) ACE_CASE(24)
+    ACE_CASE(32) ACE_CASE(48) ACE_CASE(64)
+#undef ACE_CASE
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Grouped test-kernel sums (robust_treatment's posterior block sums):
 // R = Km_xx E (n x G) for the points S, slices [b0, b1) and the group
 // indicator E[c][h] = (label[c] == h), labels in [-1, G), G <= 64.  Km_xx is

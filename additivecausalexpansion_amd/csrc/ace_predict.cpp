@@ -398,6 +398,174 @@ void predict_impl(ace_model *m, const double *theta, int64_t nx, const double *X
     if (ps->K.bytes + ps->T.bytes + ps->Kxx.bytes > PRED_KEEP_BYTES) release_pred_state(ctx);
 }
 
+// ACE_COEF_CHUNK: test points per chunk of the coefficient pass (default and
+// upper limit NXC / B: the scratch of an NXC-point prediction chunk)
+int64_t coef_chunk(int B) {
+  static const int v = env_int("ACE_COEF_CHUNK", 0);
+  const int64_t hi = NXC / B;
+  return v < 1 ? hi : std::min<int64_t>(v, hi);
+}
+
+// Kc ((tc.n B) x n, ld tc.n B): slice b of the chunk's test point c in row
+// c + tc.n b.  tc carries a basis of ones: k_cross_slices_mm ignores it, the
+// all-VALU form (ACE_PAIRS=valu, or staging beyond LDS) is mode 2 one slice
+// at a time, which multiplies by it.
+void slice_assembly(ace_ctx *ctx, const Shape &s, PairSide tc, PairSide train, TabView tv,
+                    double *Kc) {
+  const int64_t ldk = tc.n * s.B;
+  if (pairs_use_mm(s.PM, false) && cross_mm_lds_ok(s.PM, s.B, s.kind)) {
+    ck(ctx, launch_cross_slices_mm(s.kind, s.PM, tc, train, s.B, s.ZS, tv, Kc, ldk, ctx->stream),
+       "slice assembly");
+    return;
+  }
+  for (int b = 0; b < s.B; ++b)
+    ck(ctx, launch_assembly(2, s.kind, s.PM, tc, train, 0, s.B, s.ZS, tv, 0.0, Kc + tc.n * b, ldk,
+                            nullptr, ctx->stream, nullptr, 0, 1, 0, b, b + 1),
+       "slice assembly");
+}
+
+// ace_model_coef_cross: the cube Kc (nx x n x B), chunked like the pass
+void coef_cross(ace_model *m, const double *theta, int64_t nx, const double *X2, double *out) {
+  ace_ctx *ctx = m->ctx;
+  const Shape &s = m->s;
+  const int64_t n = m->n;
+  const int B = s.B;
+  std::vector<double> tab = make_tab(theta, s, false);
+  DBuf dtab, dK;
+  upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
+  const TabView tv = tab_view(dtab, s);
+  SideBufs test;
+  std::vector<double> ones((size_t)(nx * s.ZS), 1.0);
+  upload_side(ctx, test, s, X2, ones.data(), nx, nx);
+  const PairSide train = m->shard ? shard_train_side(m->shard) : m->side.view(n);
+  const int64_t chunk = std::min<int64_t>(coef_chunk(B), nx);
+  alloc(ctx, dK, (size_t)(chunk * B * n) * sizeof(double), "alloc Kc");
+  std::vector<double> h((size_t)(chunk * B * n));
+  for (int64_t c0 = 0; c0 < nx; c0 += chunk) {
+    const int64_t nc = std::min<int64_t>(chunk, nx - c0), ldk = nc * B;
+    PairSide tc = test.view(nc);
+    tc.X += c0 * s.PM;
+    tc.Z += c0 * s.ZS;
+    tc.LZ += c0 * s.ZS;
+    slice_assembly(ctx, s, tc, train, tv, dK.d());
+    download(ctx, h.data(), dK.d(), (size_t)(ldk * n), "download Kc");
+    sync(ctx);
+    for (int b = 0; b < B; ++b)
+      for (int64_t q = 0; q < n; ++q)
+        for (int64_t c = 0; c < nc; ++c)
+          out[c0 + c + nx * (q + n * b)] = h[(size_t)(c + nc * b + q * ldk)];
+  }
+}
+
+// ace_model_coef_posterior: m_c = Kc_c A^-1 (y - mu) into mean (nx x B) and
+// P_c = Kc_c A^-1 Kc_c^T into P (nx x B x B), Kc_c the B per-slice cross
+// kernels of point c without a test basis factor.  Per chunk of ncx points:
+// the slices as an (ncx B) x n matrix (k_cross_slices_mm), its product with
+// the inverse as predict_impl takes it (strictly lower triangle on one GPU,
+// the full symmetric product otherwise), and the B x B Gram sums per point
+// (k_coef_gram).  Outputs are written only at the end.
+void coef_once(ace_model *m, const double *theta, int64_t nx, const double *X2, double *mean,
+               double *P) {
+  ace_ctx *ctx = m->ctx;
+  hipStream_t st = ctx->stream;
+  const Shape &s = m->s;
+  const int64_t n = m->n;
+  const int B = s.B;
+  const double mu = theta[1];
+  std::vector<double> tab = make_tab(theta, s, false);
+  DBuf dtab, dw, dsv, ddiag, dscal, dtmp, dpart, dres;
+  upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
+  const TabView tv = tab_view(dtab, s);
+  // a test side of ones: the slice kernel ignores it, the all-VALU fallback
+  // (mode 2 one slice at a time) multiplies by it
+  SideBufs test;
+  std::vector<double> ones((size_t)(nx * s.ZS), 1.0);
+  upload_side(ctx, test, s, X2, ones.data(), nx, nx);
+  const PairSide train = m->shard ? shard_train_side(m->shard) : m->side.view(n);
+  alloc(ctx, dw, (size_t)n * sizeof(double), "alloc w");
+  ck(ctx, launch_center(m->shard ? shard_train_y(m->shard) : m->y.d(), n, mu, dw.d(), st),
+     "center y");
+  const bool tri = !m->shard && pred_tri();
+  if (tri) {  // -A^-1 is stored: scale -1
+    alloc(ctx, ddiag, (size_t)n * sizeof(double), "alloc diag");
+    ck(ctx, launch_diag_scaled(m->sw.A.d(), m->naug, n, -1.0, ddiag.d(), st), "diag");
+    alloc(ctx, dsv, (size_t)n * sizeof(double), "alloc s");
+    alloc(ctx, dscal, 8 * sizeof(double), "alloc scalars");
+    ck(ctx, launch_alpha_from_aug(m->sw.A.d(), m->naug, m->npad, n, mu, 0, dsv.d(), dscal.d(), st,
+                                  nullptr),
+       "A^-1 w");
+  }
+  std::shared_ptr<PredScratch> ps = std::static_pointer_cast<PredScratch>(ctx->pred_state);
+  if (!ps) {
+    ps = std::make_shared<PredScratch>();
+    ctx->pred_state = ps;
+  }
+  const int64_t chunk = std::min<int64_t>(coef_chunk(B), nx);
+  const int64_t per = (int64_t)B * (B + 1);  // results per point
+  alloc(ctx, ps->K, (size_t)(chunk * B * n) * sizeof(double), "alloc Kc");
+  alloc(ctx, ps->T, (size_t)(chunk * B * n) * sizeof(double), "alloc T");
+  alloc(ctx, dpart, (size_t)coef_gram_work(n, chunk, B) * sizeof(double), "alloc Gram partials");
+  alloc(ctx, dres, (size_t)(nx * per) * sizeof(double), "alloc Gram sums");
+  for (int64_t c0 = 0; c0 < nx; c0 += chunk) {
+    const int64_t nc = std::min<int64_t>(chunk, nx - c0), ldk = nc * B;
+    PairSide tc = test.view(nc);
+    tc.X += c0 * s.PM;
+    tc.Z += c0 * s.ZS;
+    tc.LZ += c0 * s.ZS;
+    double *Kc = ps->K.d(), *T = ps->T.d(), *res = dres.d() + c0 * per;
+    slice_assembly(ctx, s, tc, train, tv, Kc);
+    if (tri) {
+      ck(ctx, launch_trmm_lower(m->sw.A.d(), m->naug, n, Kc, ldk, ldk, -1.0, T, n, st), "trmm");
+      ck(ctx, launch_coef_gram(true, Kc, ldk, T, n, n, nc, B, dsv.d(), ddiag.d(), dpart.d(), res,
+                               st),
+         "coefficient Gram");
+    } else {
+      symm_resident(m, Kc, ldk, true, ldk, T, dtmp);
+      ck(ctx, launch_coef_gram(false, Kc, ldk, T, n, n, nc, B, dw.d(), nullptr, dpart.d(), res,
+                               st),
+         "coefficient Gram");
+      if (m->shard) shard_allreduce_sum(m->shard, res, nc * per);
+    }
+  }
+  std::vector<double> h((size_t)(nx * per));
+  download(ctx, h.data(), dres.d(), h.size(), "download Gram sums");
+  sync(ctx);
+  for (int64_t c0 = 0; c0 < nx; c0 += chunk) {
+    const int64_t nc = std::min<int64_t>(chunk, nx - c0);
+    const double *r = h.data() + c0 * per;
+    for (int64_t e = 0; e < nc * B * B; ++e) P[c0 + e % nc + nx * (e / nc)] = r[e];
+    for (int64_t e = 0; e < nc * B; ++e) mean[c0 + e % nc + nx * (e / nc)] = r[nc * B * B + e];
+  }
+}
+
+void coef_impl(ace_model *m, const double *theta, int64_t nx, const double *X2, double *mean,
+               double *P) {
+  ace_ctx *ctx = m->ctx;
+  try {
+    coef_once(m, theta, nx, X2, mean, P);
+  } catch (const Fail &f) {
+    if (f.code != ACE_ERR_OOM) throw;
+    (void)hipGetLastError();
+    sync(ctx);  // the failed pass's launches may still read the scratch
+    release_pred_state(ctx);
+    ctx->sweep_pool.clear();
+    coef_once(m, theta, nx, X2, mean, P);
+  }
+  if (auto ps = std::static_pointer_cast<PredScratch>(ctx->pred_state))
+    if (ps->K.bytes + ps->T.bytes + ps->Kxx.bytes > PRED_KEEP_BYTES) release_pred_state(ctx);
+}
+
+// cov_c = diag(exp(lambda_b)) - P_c in place: the prior of g(x_c) is
+// diagonal, k_b(x, x) = exp(lambda_b), lambda_b = theta[2 + b] (make_tab)
+void coef_cov_from_gram(const double *theta, int64_t nx, int B, double *cov) {
+  for (int b2 = 0; b2 < B; ++b2)
+    for (int b = 0; b < B; ++b) {
+      double *e = cov + nx * (b + (int64_t)B * b2);
+      const double prior = b == b2 ? std::exp(theta[2 + b]) : 0.0;
+      for (int64_t c = 0; c < nx; ++c) e[c] = prior - e[c];
+    }
+}
+
 // gsum / gcount of ace_model_predict_marginal_groups from the final map
 void group_sums_host(int64_t nx, int G, const int32_t *label, const double *map, double *gsum,
                      int64_t *gcount) {
@@ -554,6 +722,62 @@ int ace_model_robust_treatment(ace_model *m, const double *theta, int64_t nx, co
     counts[3 * t + 1] = treated;
     counts[3 * t + 2] = kept - treated;
   }
+  return ACE_OK;
+  ACE_CATCH
+}
+
+int ace_model_coef_posterior(ace_model *m, const double *theta, int64_t nx, const double *X2,
+                             double *mean, double *cov) {
+  if (!m) return ACE_ERR_ARG;
+  ace_ctx *ctx = m->ctx;
+  ACE_TRY
+  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+  arg(ctx, nx >= 1 && theta && mean && cov && (m->s.p == 0 || X2), "bad shape / null argument");
+  require_inverse(m);
+  coef_impl(m, theta, nx, X2, mean, cov);
+  coef_cov_from_gram(theta, nx, m->s.B, cov);
+  return ACE_OK;
+  ACE_CATCH
+}
+
+int ace_model_coef_cross(ace_model *m, const double *theta, int64_t nx, const double *X2,
+                         double *Kc) {
+  if (!m) return ACE_ERR_ARG;
+  ace_ctx *ctx = m->ctx;
+  ACE_TRY
+  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+  arg(ctx, nx >= 1 && theta && Kc && (m->s.p == 0 || X2), "bad shape / null argument");
+  arg(ctx, m->has_data, "ace_model_set_data() not called");
+  coef_cross(m, theta, nx, X2, Kc);
+  return ACE_OK;
+  ACE_CATCH
+}
+
+int ace_model_predict_surface(ace_model *m, const double *theta, int64_t nx, const double *X2,
+                              int64_t nz, const double *Zb, int marginal, double mean_y,
+                              double std_y, double std_Z, double *map, double *ci, double *var) {
+  if (!m) return ACE_ERR_ARG;
+  ace_ctx *ctx = m->ctx;
+  ACE_TRY
+  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+  const int B = m->s.B;
+  arg(ctx, nx >= 1 && nz >= 1 && theta && map && ci && var && (m->s.p == 0 || X2) && (B == 1 || Zb),
+      "bad shape / null argument");
+  require_inverse(m);
+  std::vector<double> mean((size_t)(nx * B)), cov((size_t)(nx * B * B));
+  coef_impl(m, theta, nx, X2, mean.data(), cov.data());
+  coef_cov_from_gram(theta, nx, B, cov.data());
+  // beta = (1, B(z)); marginal: (0, dB(z)), (1) for B == 1 (src/pred_cpp.cpp:55-67)
+  std::vector<double> W((size_t)(nz * B));
+  for (int64_t j = 0; j < nz; ++j) {
+    W[(size_t)j] = (marginal && B > 1) ? 0.0 : 1.0;
+    for (int b = 1; b < B; ++b) W[(size_t)(j + nz * b)] = Zb[j + nz * (b - 1)];
+  }
+  const int rc = marginal ? ace_coef_contract(nx, B, nz, mean.data(), cov.data(), W.data(), 0.0,
+                                              std_y / std_Z, 0.0, 0.0, map, ci, var)
+                          : ace_coef_contract(nx, B, nz, mean.data(), cov.data(), W.data(), mean_y,
+                                              std_y, theta[1], std::exp(theta[0]), map, ci, var);
+  if (rc != ACE_OK) throw Fail{rc};
   return ACE_OK;
   ACE_CATCH
 }

@@ -24,6 +24,7 @@
 // 256 threads, 128 (rows) x 64 (columns) output tile, 4 waves of 32 x 64
 // (2 x 4 v_mfma_f64_16x16x4_f64 fragments), BK = 16 k-chunks staged
 // through LDS with a register prefetch of the next chunk.
+#include <algorithm>
 #include <cstdlib>
 
 #include "ace_internal.h"
@@ -383,6 +384,212 @@ hipError_t launch_pred_cols_tri(const double *Y, int64_t ldt, const double *K, i
   if (nx <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_pred_cols_tri, dim3((unsigned)nx), dim3(256), 0, st, Y, ldt, K, ldk, n, sv,
                      D, a, d);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- coefficient Gram
+// Per test point c of a chunk of ncx (the coefficient posterior,
+// ace_predict.cpp): with Kc the (ncx B) x n per-slice cross kernels (row
+// c + ncx b, ld ldk) and W the n x (ncx B) product with the resident inverse
+// (column c + ncx b, ld ldw),
+//   M_c[b][b'] = sum_q Kc[c,b][q] Wt[q][c,b'],  m_c[b] = sum_q (..)[q] v[q]
+// TRI:  Wt = Y + 1/2 D o Kc^T (Y = L Kc^T, L strictly lower), v = S w summed
+//       against Kc; then P_c = M_c + M_c^T = Kc_c S Kc_c^T -- k_pred_cols_tri's
+//       identity for b != b'
+// full: Wt = T' = S Kc^T, v = w summed against T'; P_c = (M_c + M_c^T) / 2
+// A batched tall-skinny GEMM (M = N = B, K = n) on v_mfma_f64_16x16x4_f64:
+// B padded to 16 NBK with zeros, NBK^2 accumulator blocks per point.  A
+// workgroup takes GC = 16 adjacent test points (wave w the points 4 w ..
+// 4 w + 3) and the training points [js qs, (js + 1) qs); each GQ = 8 step
+// stages Kc as runs of 16 adjacent c and W as runs of 8 adjacent q in LDS,
+// so no load strides by a leading dimension (k_pred_cols reads K[c + q ld]).
+// qs and the number of ranges depend on n alone (coef_gram_split), the
+// ranges' partials are added in ascending js by k_coef_finish: no atomics,
+// and a point's bits do not depend on the chunk it arrives in.
+// Memory-bound by construction: Kc and W are read once, 2 ncx B n doubles,
+// for 2 ncx B^2 n flops (DESIGN §13 has the measured rate).
+// ----------------------------------------------------------------
+constexpr int GC = 16, GQ = 8, GKP = GQ * GC + 1, GWP = GQ + 1;
+
+template <bool TRI, int NBK>
+__global__ __launch_bounds__(256) void k_coef_gram(const double *__restrict__ Kc, int64_t ldk,
+                                                   const double *__restrict__ W, int64_t ldw,
+                                                   int64_t n, int64_t ncx, int B, int64_t qs,
+                                                   const double *__restrict__ vec,
+                                                   const double *__restrict__ D,
+                                                   double *__restrict__ part, int64_t pstride) {
+  extern __shared__ __attribute__((aligned(16))) double glds[];
+  constexpr int BP = 16 * NBK;
+  double *const sK = glds;                 // [b][q][c]: b GKP + q GC + c
+  double *const sW = sK + BP * GKP;        // [c][b][q]: (c BP + b) GWP + q
+  double *const sV = sW + GC * BP * GWP;   // v[q]
+  double *const sD = sV + GQ;              // D[q] / 2
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+  const int64_t c0 = (int64_t)blockIdx.x * GC, js = blockIdx.y;
+  const int64_t q0 = js * qs, qend = q0 + qs < n ? q0 + qs : n;
+  const int mc = tid & 15, mb = tid >> 4;  // the mean's (point, slice mb + 16 bi)
+  d4 acc[4][NBK][NBK];
+  double macc[NBK];
+#pragma unroll
+  for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+    for (int bi = 0; bi < NBK; ++bi)
+#pragma unroll
+      for (int bj = 0; bj < NBK; ++bj) acc[pt][bi][bj] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int bi = 0; bi < NBK; ++bi) macc[bi] = 0.0;
+  for (int64_t qq = q0; qq < qend; qq += GQ) {
+    for (int e = tid; e < BP * GQ * GC; e += 256) {
+      const int c = e & (GC - 1), q = (e >> 4) & (GQ - 1), b = e >> 7;
+      const bool ok = b < B && c0 + c < ncx && qq + q < qend;
+      sK[b * GKP + q * GC + c] = ok ? Kc[(c0 + c) + ncx * b + (qq + q) * ldk] : 0.0;
+    }
+    for (int e = tid; e < GC * BP * GQ; e += 256) {
+      const int q = e & (GQ - 1), cb = e >> 3, b = cb % BP, c = cb / BP;
+      const bool ok = b < B && c0 + c < ncx && qq + q < qend;
+      sW[cb * GWP + q] = ok ? W[(qq + q) + ((c0 + c) + ncx * b) * ldw] : 0.0;
+    }
+    if (tid < GQ) {
+      const bool ok = qq + tid < qend;
+      sV[tid] = ok ? vec[qq + tid] : 0.0;
+      sD[tid] = (TRI && ok) ? 0.5 * D[qq + tid] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int bi = 0; bi < NBK; ++bi) {
+      const int b = mb + 16 * bi;
+#pragma unroll
+      for (int q = 0; q < GQ; ++q) {
+        const double x = TRI ? sK[b * GKP + q * GC + mc] : sW[(mc * BP + b) * GWP + q];
+        macc[bi] = fma(x, sV[q], macc[bi]);
+      }
+    }
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt) {
+      const int c = 4 * w + pt;
+#pragma unroll
+      for (int ks = 0; ks < GQ / 4; ++ks) {
+        const int q = 4 * ks + lk;
+        double a[NBK], bop[NBK];
+#pragma unroll
+        for (int bi = 0; bi < NBK; ++bi) {
+          a[bi] = sK[(16 * bi + lr) * GKP + q * GC + c];
+          const double y = sW[(c * BP + 16 * bi + lr) * GWP + q];
+          bop[bi] = TRI ? fma(sD[q], a[bi], y) : y;
+        }
+#pragma unroll
+        for (int bi = 0; bi < NBK; ++bi)
+#pragma unroll
+          for (int bj = 0; bj < NBK; ++bj)
+            acc[pt][bi][bj] =
+                __builtin_amdgcn_mfma_f64_16x16x4f64(a[bi], bop[bj], acc[pt][bi][bj], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  // D register v of lane (lr, lk): M[16 bi + lk + 4 v][16 bj + lr]
+  double *const pj = part + js * pstride;
+#pragma unroll
+  for (int pt = 0; pt < 4; ++pt) {
+    const int64_t c = c0 + 4 * w + pt;
+    if (c >= ncx) continue;
+#pragma unroll
+    for (int bi = 0; bi < NBK; ++bi)
+#pragma unroll
+      for (int bj = 0; bj < NBK; ++bj)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int b = 16 * bi + lk + 4 * v, b2 = 16 * bj + lr;
+          if (b < B && b2 < B) pj[c + ncx * (b + (int64_t)B * b2)] = acc[pt][bi][bj][v];
+        }
+  }
+  if (c0 + mc < ncx) {
+#pragma unroll
+    for (int bi = 0; bi < NBK; ++bi) {
+      const int b = mb + 16 * bi;
+      if (b < B) pj[ncx * B * B + (c0 + mc) + ncx * b] = macc[bi];
+    }
+  }
+}
+
+// res = the ranges' partials in ascending js, symmetrised: res[c + ncx (b +
+// B b')] = M[b][b'] + M[b'][b] (TRI) or half of it, the same bits for (b, b')
+// and (b', b); res[ncx B B + c + ncx b] = m_c[b]
+__global__ __launch_bounds__(256) void k_coef_finish(const double *__restrict__ part, int nparts,
+                                                     int64_t pstride, int64_t ncx, int B, int tri,
+                                                     double *__restrict__ res) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t ncov = ncx * B * B;
+  if (e >= ncov + ncx * B) return;
+  if (e >= ncov) {
+    double s = 0.0;
+    for (int j = 0; j < nparts; ++j) s += part[j * pstride + e];
+    res[e] = s;
+    return;
+  }
+  const int64_t c = e % ncx, bb = e / ncx;
+  const int b = (int)(bb % B), b2 = (int)(bb / B);
+  const int64_t et = c + ncx * (b2 + (int64_t)B * b);
+  double s1 = 0.0, s2 = 0.0;
+  for (int j = 0; j < nparts; ++j) {
+    s1 += part[j * pstride + e];
+    s2 += part[j * pstride + et];
+  }
+  res[e] = tri ? s1 + s2 : 0.5 * (s1 + s2);
+}
+
+// training points per range and the number of ranges: from n alone
+int64_t coef_gram_split(int64_t n, int *nparts) {
+  const int64_t np = std::min<int64_t>(64, (n + 255) / 256);
+  const int64_t qs = ((n + np - 1) / np + GQ - 1) / GQ * GQ;
+  *nparts = (int)((n + qs - 1) / qs);
+  return qs;
+}
+
+int64_t coef_gram_work(int64_t n, int64_t ncx, int B) {
+  int np = 0;
+  (void)coef_gram_split(n, &np);
+  return (int64_t)np * ncx * B * (B + 1);
+}
+
+template <bool TRI, int NBK>
+static hipError_t coef_gram_launch(const double *Kc, int64_t ldk, const double *W, int64_t ldw,
+                                   int64_t n, int64_t ncx, int B, const double *vec,
+                                   const double *D, double *part, hipStream_t st) {
+  constexpr int BP = 16 * NBK;
+  const size_t lds = (size_t)(BP * GKP + GC * BP * GWP + 2 * GQ) * sizeof(double);
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute((const void *)k_coef_gram<TRI, NBK>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  int np = 0;
+  const int64_t qs = coef_gram_split(n, &np);
+  const dim3 grid((unsigned)((ncx + GC - 1) / GC), (unsigned)np);
+  hipLaunchKernelGGL((k_coef_gram<TRI, NBK>), grid, dim3(256), lds, st, Kc, ldk, W, ldw, n, ncx, B,
+                     qs, vec, D, part, ncx * B * (B + 1));
+  return hipGetLastError();
+}
+
+hipError_t launch_coef_gram(bool tri, const double *Kc, int64_t ldk, const double *W, int64_t ldw,
+                            int64_t n, int64_t ncx, int B, const double *vec, const double *D,
+                            double *part, double *res, hipStream_t st) {
+  if (ncx <= 0 || n <= 0) return hipSuccess;
+  if (B < 1 || B > 32) return hipErrorInvalidValue;
+  hipError_t e;
+  if (B <= 16)
+    e = tri ? coef_gram_launch<true, 1>(Kc, ldk, W, ldw, n, ncx, B, vec, D, part, st)
+            : coef_gram_launch<false, 1>(Kc, ldk, W, ldw, n, ncx, B, vec, D, part, st);
+  else
+    e = tri ? coef_gram_launch<true, 2>(Kc, ldk, W, ldw, n, ncx, B, vec, D, part, st)
+            : coef_gram_launch<false, 2>(Kc, ldk, W, ldw, n, ncx, B, vec, D, part, st);
+  if (e != hipSuccess) return e;
+  int np = 0;
+  (void)coef_gram_split(n, &np);
+  const int64_t tot = ncx * B * (B + 1);
+  hipLaunchKernelGGL(k_coef_finish, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, part, np,
+                     tot, ncx, B, tri ? 1 : 0, res);
   return hipGetLastError();
 }
 

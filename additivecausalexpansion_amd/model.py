@@ -200,6 +200,52 @@ class DeviceModel:
             out[key] = {"map": avg[4 * j], "ci": avg[4 * j + 1:4 * j + 3].T, "var": avg[4 * j + 3]}
         return out
 
+    def coef_posterior(self, theta, X2):
+        """ace_model_coef_posterior: the posterior of the coefficient vector
+        g(x) at every row of X2 -- {"mean": (nx, B), "cov": (nx, B, B)} in
+        normalised-y units, without mu and without the noise term."""
+        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
+        X2f = fmat(X2)
+        nx = X2f.shape[0]
+        mean = np.empty((nx, self.B), order="F")
+        cov = np.empty((nx, self.B, self.B), order="F")
+        check(lib().ace_model_coef_posterior(self.handle, ptr(th), nx, ptr(X2f), ptr(mean),
+                                             cov.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+              self.ctx.handle)
+        return {"mean": mean, "cov": cov}
+
+    def coef_cross(self, theta, X2):
+        """ace_model_coef_cross: the per-slice cross kernels (nx, n, B) the
+        coefficient posterior is formed from (a test basis of ones)."""
+        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
+        X2f = fmat(X2)
+        nx = X2f.shape[0]
+        Kc = np.empty((nx, self.n, self.B), order="F")
+        check(lib().ace_model_coef_cross(self.handle, ptr(th), nx, ptr(X2f), ptr(Kc)),
+              self.ctx.handle)
+        return Kc
+
+    def predict_surface(self, theta, X2, Zb, marginal, mean_y, std_y, std_Z):
+        """ace_model_predict_surface: pred_cpp (marginal false; Zb the test
+        basis, nz x (B-1)) or pred_marginal_cpp (Zb its derivative) on the
+        grid of every row of X2 with every row of Zb, from one coefficient
+        pass: {"map": (nx, nz), "ci": (nx, nz, 2), "var": (nx, nz)}."""
+        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
+        X2f = fmat(X2)
+        nx = X2f.shape[0]
+        Zf = np.asarray(Zb, dtype=np.float64)
+        Zf = np.asfortranarray(Zf.reshape((-1, max(self.B - 1, 1)), order="F") if Zf.ndim != 2
+                               else Zf)
+        nz = Zf.shape[0]
+        mp = np.empty((nx, nz), order="F")
+        var = np.empty((nx, nz), order="F")
+        ci = np.empty((nx, nz, 2), order="F")
+        check(lib().ace_model_predict_surface(
+            self.handle, ptr(th), nx, ptr(X2f), nz, ptr(Zf), 1 if marginal else 0, float(mean_y),
+            float(std_y), float(np.ravel([std_Z])[0]), ptr(mp),
+            ci.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ptr(var)), self.ctx.handle)
+        return {"map": mp, "ci": ci, "var": var}
+
     def comm_calls(self):
         """ace_model_comm_calls: collectives this rank issued since creation,
         {"broadcast", "allgather", "allreduce", "groups"} (zeros when simulated)."""
@@ -392,6 +438,24 @@ class _KernelClass:
             raise AceError("robust_treatment needs the fit's device-resident inverse "
                            "(para_update on the same data)")
         return self._model.robust_treatment(self.parameters, X2, dZ2, Z2, std_y, std_Z, n_steps)
+
+    def coef_posterior(self, y, X, Z, X2):
+        """The posterior of the coefficient functions at the rows of X2, on
+        the fit's device model (DeviceModel.coef_posterior)."""
+        if not self._resident(y, X, Z):
+            raise AceError("coef_posterior needs the fit's device-resident inverse "
+                           "(para_update on the same data)")
+        return self._model.coef_posterior(self.parameters, X2)
+
+    def predict_surface(self, y, X, Z, X2, Zb, marginal, mean_y, std_y, std_Z):
+        """predict / predict_marginal on the grid of the rows of X2 and of Zb
+        (the test basis, or its derivative when marginal), on the fit's device
+        model (DeviceModel.predict_surface)."""
+        if not self._resident(y, X, Z):
+            raise AceError("predict_surface needs the fit's device-resident inverse "
+                           "(para_update on the same data)")
+        return self._model.predict_surface(self.parameters, X2, Zb, marginal, mean_y, std_y,
+                                           std_Z)
 
     def mean_solution(self, y):
         """R/kernel_SE_R6.R:99-102 (private in the SE class)."""

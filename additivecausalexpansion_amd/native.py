@@ -417,3 +417,27 @@ def robust_levels(var, n_steps):
     check(lib().ace_robust_levels(v.size, ptr(v), int(n_steps), ptr(thr),
                                   level.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
     return thr, level
+
+
+def coef_contract(mean, cov, W, offset=0.0, scale=1.0, shift=0.0, noise=0.0):
+    """ace_coef_contract: a coefficient posterior (mean nx x B, cov nx x B x B)
+    contracted with the nz weight rows W (nz x B), the tails of pred_cpp /
+    pred_marginal_cpp (src/pred_cpp.cpp:20-29, 70-78):
+    map = offset + scale (W_j . mean_c + shift), var = scale^2 |W_j^T cov_c W_j
+    + noise|.  Returns {"map": (nx, nz), "ci": (nx, nz, 2), "var": (nx, nz)};
+    raveled in Fortran order the first two axes are expand.grid(X, Z)."""
+    mf = fmat(mean)
+    if mf.ndim != 2:
+        raise AceError("mean must be nx x B")
+    nx, B = mf.shape
+    cf = np.asfortranarray(np.asarray(cov, dtype=np.float64).reshape((nx, B, B), order="F"))
+    Wf = np.asfortranarray(np.asarray(W, dtype=np.float64).reshape((-1, B), order="F"))
+    nz = Wf.shape[0]
+    mp = np.empty((nx, nz), order="F")
+    var = np.empty((nx, nz), order="F")
+    ci = np.empty((nx, nz, 2), order="F")
+    check(lib().ace_coef_contract(nx, B, nz, ptr(mf), cf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                  ptr(Wf), float(offset), float(scale), float(shift), float(noise),
+                                  ptr(mp), ci.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                  ptr(var)))
+    return {"map": mp, "ci": ci, "var": var}

@@ -315,3 +315,51 @@ def robust_treatment(obj, newX=None, n_steps=5):
             tab[keep] = avg[4 * j:4 * j + 4].T[keep]
             out[key] = tab
     return out
+
+
+def _surface_points(obj, newX, newZ=None):
+    """newX (nx raw rows) and newZ (nz raw treatment values) normalised with
+    the fit's moments as predict_ace normalises them, each on its own."""
+    X = obj["train_data"]["X"]
+    px = X.shape[1]
+    pz = obj["train_data"]["Z"].shape[1]
+    mom = obj["moments"]
+    if newX is None:
+        Xn = X
+    else:
+        Xn = np.array(newX, dtype=np.float64, order="F", copy=True)
+        if Xn.ndim != 2 or Xn.shape[1] != px:
+            raise AceError("Dimension mismatch of X with newX")
+        native.normalize_test(Xn, np.zeros((Xn.shape[0], pz), order="F"), mom)
+    if newZ is None:
+        return Xn, None
+    Zn = np.array(np.ravel(newZ), dtype=np.float64).reshape(-1, pz, order="F")
+    Zn = np.asfortranarray(Zn)
+    native.normalize_test(np.zeros((Zn.shape[0], px), order="F"), Zn, mom)
+    return Xn, Zn
+
+
+def coef_posterior(obj, newX=None):
+    """Posterior of the coefficient functions g_b(x) of the fit at the rows
+    of newX (raw units; None: the training points): {"mean": (nx, B), "cov":
+    (nx, B, B)} in normalised-y units, without mu and the noise term."""
+    Xn, _ = _surface_points(obj, newX)
+    return obj["Kernel"].coef_posterior(obj["train_data"]["y"], obj["train_data"]["X"],
+                                        obj["Basis"].B, Xn)
+
+
+def response_surface(obj, newX, newZ, marginal=False):
+    """predict_ace on the grid of every row of newX (nx raw rows) with every
+    treatment value of newZ (nz raw values), what plot_ace computes for its
+    curves and surfaces (R/plot_ace.R:146-154, 288, 350-351), from one
+    coefficient pass: {"map": (nx, nz), "ci": (nx, nz, 2), "var": (nx, nz)};
+    raveled in Fortran order the first two axes are expand.grid(X, Z)."""
+    X = obj["train_data"]["X"]
+    px = X.shape[1]
+    pz = obj["train_data"]["Z"].shape[1]
+    mom = obj["moments"]
+    Xn, Zn = _surface_points(obj, newX, newZ)
+    tb = obj["Basis"].testbasis(Zn)
+    return obj["Kernel"].predict_surface(obj["train_data"]["y"], X, obj["Basis"].B, Xn,
+                                         tb["dB"] if marginal else tb["B"], marginal, mom[0, 0],
+                                         mom[0, 1], mom[1 + px:1 + px + pz, 1])

@@ -336,6 +336,50 @@ int ace_model_robust_treatment(ace_model *m, const double *theta, int64_t nx, co
                                const double *dZ2, const double *Z_x, double std_y, double std_Z,
                                int n_steps, double *map, double *ci, double *var,
                                double *thresholds, int32_t *level, double *avg, int64_t *counts);
+/* Posterior of the coefficient functions g_b(x) of y = mu + sum_b g_b(x)
+ * beta_b(z) + eps at nx covariate points X2 (nx x p): what plot_ace draws
+ * (R/plot_ace.R:146-154, 288, 350-351) by running predict on the expanded
+ * nx nz grid.  The cross kernel factorises on the test side,
+ * K_b((x,z), X_q) = beta_b(z) Kc_b(x, X_q) with Kc_b = k_b(x, X_q)
+ * beta_b(Z_q), so the resident inverse sees nx B right-hand sides whatever
+ * the number of treatment values.
+ * mean (nx x B) and cov (nx x B x B), column-major, point index fastest:
+ * mean[c + nx*b], cov[c + nx*(b + B*b')].  Normalised-y units, without mu
+ * and without the noise term: mean_c = Kc_c A^-1 (y - mu), cov_c =
+ * diag(exp(theta[2+b])) - Kc_c A^-1 Kc_c^T.  Kernels at theta, the resident
+ * inverse of the last para_update (Q6).  cov is exactly symmetric in (b, b')
+ * and both outputs are bitwise reproducible.  Works on sharded models
+ * (collective).  ACE_ERR_ARG before the first para_update or for nx < 1. */
+int ace_model_coef_posterior(ace_model *m, const double *theta, int64_t nx,
+                             const double *X2, double *mean, double *cov);
+/* The per-slice cross kernels the coefficient posterior is formed from:
+ * Kc (nx x n x B, column-major), Kc[c + nx*(q + n*b)] = k_b(x_c, X_q)
+ * beta_b(Z_q) -- the "elements" cube of kernmat_*_cpp (src/kernel_SE_cpp.cpp:
+ * 9-64, src/kernel_Matern_cpp.cpp:52-93) for X2 against the training points
+ * with a test basis of ones, from the pass's own assembly kernel.  For
+ * inspection and tests; needs set_data only. */
+int ace_model_coef_cross(ace_model *m, const double *theta, int64_t nx,
+                         const double *X2, double *Kc);
+/* Host only, no context: contracts a coefficient posterior with nz weight
+ * rows W (nz x B, column-major).  out index c + nx*j (X fastest, as
+ * expand.grid); ci is (nx*nz) x 2.
+ *   map = offset + scale * (W_j . mean_c + shift)
+ *   var = scale^2 * |W_j^T cov_c W_j + noise|      (src/pred_cpp.cpp:26, :75) */
+int ace_coef_contract(int64_t nx, int B, int64_t nz, const double *mean,
+                      const double *cov, const double *W, double offset,
+                      double scale, double shift, double noise,
+                      double *map, double *ci, double *var);
+/* pred_cpp / pred_marginal_cpp (src/pred_cpp.cpp:8-34, 37-83) on the nx x nz
+ * grid of (row of X2) x (row of Zb): Zb is nz x (B-1), the test basis
+ * (marginal = 0) or its derivative (marginal != 0).  One coefficient pass
+ * plus the contraction: W_j = (1, Zb_j), offset mean_y, scale std_y, shift
+ * mu = theta[1], noise exp(theta[0]); marginal: W_j = (0, Zb_j) ((1) for
+ * B == 1), scale std_y / std_Z, no offset, shift or noise.  Outputs as
+ * ace_coef_contract's. */
+int ace_model_predict_surface(ace_model *m, const double *theta, int64_t nx,
+                              const double *X2, int64_t nz, const double *Zb,
+                              int marginal, double mean_y, double std_y,
+                              double std_Z, double *map, double *ci, double *var);
 /* Per-kernel device timing for the roofline report: when enabled, HIP
  * events bracket every launch of the dense update kernel (`which` = 0),
  * the assembly kernel (1) and the gradient kernel (2) on the model's
