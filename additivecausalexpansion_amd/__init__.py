@@ -7,7 +7,8 @@ from .native import (  # noqa: F401
     DMat, Adam_cpp, Nadam_cpp, Nesterov_cpp, coef_contract, grad_Matern_cpp, grad_SE_cpp,
     invkernel_cpp, kernmat_Matern32_cpp, kernmat_Matern32_symmetric_cpp, kernmat_SE_cpp,
     kernmat_SE_symmetric_cpp, mu_solution_cpp, ncs_basis, ncs_basis_deriv, norm_clip_cpp,
-    normalize_test, normalize_train, pred_cpp, pred_marginal_cpp, robust_levels, stats_cpp)
+    normalize_test, normalize_train, pred_cpp, pred_marginal_cpp, robust_levels, stats_cpp,
+    zero_pattern_order)
 from .model import (  # noqa: F401
     DeviceModel, KernelClass_Matern32_R6, KernelClass_SE_R6, comm_unique_id, optAdam, optNadam,
     optNesterov, set_optimizer)

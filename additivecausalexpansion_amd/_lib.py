@@ -80,6 +80,8 @@ SIGNATURES = {
     "ace_ncs_basis_deriv": (ctypes.c_int, [_I64, _D, _I64, _D, _D, ctypes.POINTER(_I64)]),
     "ace_normalize_train": (ctypes.c_int, [_I64, ctypes.c_int, ctypes.c_int, _D, _D, _D, _D]),
     "ace_normalize_test": (ctypes.c_int, [_I64, ctypes.c_int, ctypes.c_int, _D, _D, _D, _I64]),
+    "ace_zero_pattern_order": (ctypes.c_int, [_I64, ctypes.c_int, _D, ctypes.POINTER(_I64),
+                                              ctypes.POINTER(ctypes.c_uint32), _I32]),
     "ace_model_create": (ctypes.c_int, [_vp, ctypes.c_int, _I64, ctypes.c_int, ctypes.c_int,
                                         ctypes.POINTER(_vp)]),
     "ace_model_destroy": (None, [_vp]),

@@ -570,7 +570,8 @@ void assemble_and_sweep(ace_ctx *ctx, SweepWork &w, const Shape &s, const PairSi
 // The gradient's tile list for n: diagonal 64-tiles first, then the strictly
 // lower ones dealt to the XCDs in S x S super-blocks (a launch's block b runs
 // on XCD b % 8).  *ndiag = -1 (and no list) for the row-major grid.
-void build_grad_tiles(ace_ctx *ctx, int64_t n, DBuf &tiles, int64_t *ntiles, int64_t *ndiag) {
+void build_grad_tiles(ace_ctx *ctx, int64_t n, DBuf &tiles, int64_t *ntiles, int64_t *ndiag,
+                      const uint32_t *mask) {
   *ntiles = grad_ntiles(n);
   *ndiag = -1;
   const int S = grad_order_block();
@@ -580,7 +581,12 @@ void build_grad_tiles(ace_ctx *ctx, int64_t n, DBuf &tiles, int64_t *ntiles, int
   for (int64_t I = 0; I < ntr; ++I) lst.push_back(Tile{(int)I, (int)I});
   for (int64_t I = 1; I < ntr; ++I)
     for (int64_t J = 0; J < I; ++J) low.push_back(Tile{(int)I, (int)J});
-  const std::vector<Tile> o = xcd_update_order(low, S);
+  // with slice masks a tile's cost is its active slices (grouped points: up
+  // to B times apart); the cheap tiles then end each XCD's share of the launch
+  std::function<double(const Tile &)> cost;
+  if (mask)
+    cost = [mask](const Tile &t) { return 1.0 + __builtin_popcount(mask[t.I] & mask[t.J]); };
+  const std::vector<Tile> o = xcd_update_order(low, S, cost);
   lst.insert(lst.end(), o.begin(), o.end());
   alloc(ctx, tiles, lst.size() * sizeof(Tile), "alloc grad tiles");
   upload_bytes(ctx, tiles.p, lst.data(), lst.size() * sizeof(Tile), "upload grad tiles");
@@ -620,7 +626,7 @@ void model_pipeline(ace_model *m, SweepWork &w, const double *theta, int use_mu,
        "upload tables");
     sig = std::exp(theta[0]);
   }
-  const PairSide ps = m->side.view(m->n);
+  const PairSide ps = m->train_side();
   if (m->norms.p) {  // the slice norms once per point, for the assembly and the gradient
     const int NS = s.kind == ACE_KERNEL_MATERN32 ? s.B + 1 : s.B;
     ck(ctx, launch_slice_norms(ps.X, s.PM, m->npad, s.B, NS, tv.wk,
@@ -880,9 +886,63 @@ int ace_model_set_data(ace_model *m, const double *y, const double *X, const dou
     m->has_data = true;
     return ACE_OK;
   }
+  // ACE_ZSKIP: Z never changes during a fit, so the zero-pattern
+  // order and the blocks' slice masks are computed here, once.  2: the device
+  // holds the points grouped by pattern (a symmetric relabelling of A: every
+  // sum over training points is unchanged up to rounding); 1: the given
+  // order with its masks; 0, B = 1, or the all-VALU pair kernels: neither.
+  const Shape &s = m->s;
+  const int64_t n = m->n;
+  const int zs = s.B - 1, mode = zskip_mode(n);
+  m->perm.clear();
+  m->has_zmask = false;
+  std::vector<double> Xp, Zp, yp((size_t)m->npad, 0.0);
+  std::copy(y, y + n, yp.begin());
+  if (mode > 0 && zs >= 1 && zs <= 32 && pairs_use_mm(s.PM, false) &&
+      mm_lds_ok(s.PM, s.B, s.kind, false) && mm_lds_ok(s.PM, s.B, s.kind, true)) {
+    const uint32_t all = zs >= 32 ? 0xffffffffu : ((uint32_t)1 << zs) - 1;
+    std::vector<uint32_t> bm((size_t)(m->npad / AT), all);  // blocks of padding: every slice
+    std::vector<int64_t> perm((size_t)n);
+    int32_t has = 0;
+    arg(ctx, ace_zero_pattern_order(n, zs, Z, perm.data(), bm.data(), &has) == ACE_OK,
+        "zero-pattern order");
+    bool ident = true;
+    for (int64_t k = 0; k < n && ident; ++k) ident = perm[(size_t)k] == k;
+    if (mode == 2 && !ident) {
+      Xp.resize((size_t)(n * s.p));
+      Zp.resize((size_t)(n * zs));
+      for (int i = 0; i < s.p; ++i)
+        for (int64_t k = 0; k < n; ++k) Xp[(size_t)(k + i * n)] = X[perm[(size_t)k] + i * n];
+      for (int b = 0; b < zs; ++b)
+        for (int64_t k = 0; k < n; ++k) Zp[(size_t)(k + b * n)] = Z[perm[(size_t)k] + b * n];
+      for (int64_t k = 0; k < n; ++k) yp[(size_t)k] = y[perm[(size_t)k]];
+      X = Xp.data();
+      Z = Zp.data();
+      m->perm = perm;
+    } else if (!ident) {  // the given order's masks
+      for (int64_t k = 0; k < n / AT; ++k) {
+        uint32_t w = 0;
+        for (int b = 0; b < zs; ++b)
+          for (int64_t j = AT * k; j < AT * (k + 1); ++j)
+            if (Z[j + b * n] != 0.0) w |= (uint32_t)1 << b;
+        bm[(size_t)k] = w;
+      }
+    }
+    bool any = false;
+    for (uint32_t w : bm) any = any || w != all;
+    if (any) {
+      alloc(ctx, m->zmask, bm.size() * sizeof(uint32_t), "alloc slice masks");
+      upload_bytes(ctx, m->zmask.p, bm.data(), bm.size() * sizeof(uint32_t), "upload slice masks");
+      m->has_zmask = true;
+    }
+    // the gradient's tile list: by cost with the grouped order (the tile sums'
+    // order then differs from the given order's, like the points' own)
+    int64_t nt = 0;
+    build_grad_tiles(ctx, n, m->gtiles, &nt, &m->ngdiag,
+                     (any && !m->perm.empty()) ? bm.data() : nullptr);
+    arg(ctx, nt == m->ntiles, "gradient tile list changed size");
+  }
   upload_side(ctx, m->side, m->s, X, Z, m->n, m->npad);
-  std::vector<double> yp((size_t)m->npad, 0.0);
-  std::copy(y, y + m->n, yp.begin());
   upload_bytes(ctx, m->y.p, yp.data(), yp.size() * sizeof(double), "upload y");
   m->std_y = std_y;
   sync(ctx);
@@ -1024,8 +1084,20 @@ int ace_model_get_inverse(ace_model *m, double *inv) {
   alloc(ctx, out, (size_t)(m->n * m->n) * sizeof(double), "alloc inverse");
   ck(ctx, launch_sym_from_lower(m->sw.A.d(), m->naug, m->n, -1.0, out.d(), m->n, ctx->stream),
      "symmetrize");
-  download(ctx, inv, out.d(), (size_t)(m->n * m->n), "download inverse");
+  if (m->perm.empty()) {
+    download(ctx, inv, out.d(), (size_t)(m->n * m->n), "download inverse");
+    sync(ctx);
+    return ACE_OK;
+  }
+  // the device's point k is the caller's perm[k]
+  const int64_t n = m->n;
+  std::vector<double> h((size_t)(n * n));
+  download(ctx, h.data(), out.d(), h.size(), "download inverse");
   sync(ctx);
+  for (int64_t j = 0; j < n; ++j) {
+    double *col = inv + m->perm[(size_t)j] * n;
+    for (int64_t i = 0; i < n; ++i) col[m->perm[(size_t)i]] = h[(size_t)(i + j * n)];
+  }
   return ACE_OK;
   ACE_CATCH
 }

@@ -265,6 +265,46 @@ int ace_robust_levels(int64_t nx, const double *var, int n_steps, double *thresh
   return ACE_OK;
 }
 
+// The zero-pattern order of the basis and its per-block slice masks (the pair
+// kernels' slice skip): a point's pattern is the set of columns of
+// Z where it is nonzero (both signs of zero are zero); the points are sorted
+// by the pattern's size, then by the pattern, and equal patterns keep their
+// input order, so a Z without exact zeros gives the identity.
+int ace_zero_pattern_order(int64_t n, int ZS, const double *Z, int64_t *perm, uint32_t *blockmask,
+                           int32_t *has_mask) {
+  if (n < 1 || ZS < 0 || (ZS > 0 && !Z) || !perm) return ACE_ERR_ARG;
+  const int W = (ZS + 63) / 64 > 0 ? (ZS + 63) / 64 : 1;  // pattern words
+  std::vector<uint64_t> pat((size_t)n * W, 0);
+  std::vector<int> cnt((size_t)n, 0);
+  for (int b = 0; b < ZS; ++b)
+    for (int64_t r = 0; r < n; ++r)
+      if (Z[r + (int64_t)b * n] != 0.0) {
+        pat[(size_t)r * W + b / 64] |= (uint64_t)1 << (b % 64);
+        ++cnt[(size_t)r];
+      }
+  for (int64_t r = 0; r < n; ++r) perm[r] = r;
+  std::stable_sort(perm, perm + n, [&](int64_t a, int64_t c) {
+    if (cnt[(size_t)a] != cnt[(size_t)c]) return cnt[(size_t)a] < cnt[(size_t)c];
+    for (int w = W - 1; w >= 0; --w)
+      if (pat[(size_t)a * W + w] != pat[(size_t)c * W + w])
+        return pat[(size_t)a * W + w] < pat[(size_t)c * W + w];
+    return false;
+  });
+  const bool mask = ZS <= 32 && blockmask != nullptr;
+  if (has_mask) *has_mask = mask ? 1 : 0;
+  if (!mask) return ACE_OK;
+  const uint32_t all = ZS >= 32 ? 0xffffffffu : ((uint32_t)1 << ZS) - 1;
+  const int64_t nblk = (n + 63) / 64;
+  for (int64_t k = 0; k < nblk; ++k) {
+    uint32_t m = 0;
+    if (64 * (k + 1) > n) m = all;  // padding points in the block: every slice
+    else
+      for (int64_t j = 64 * k; j < 64 * (k + 1); ++j) m |= (uint32_t)pat[(size_t)perm[j] * W];
+    blockmask[k] = m;
+  }
+  return ACE_OK;
+}
+
 // A coefficient posterior contracted with nz weight rows: the tails of
 // pred_cpp / pred_marginal_cpp (src/pred_cpp.cpp:20-29, 70-78) at every
 // (point c, row j), output index c + nx j

@@ -73,7 +73,21 @@ struct PairSide {
   const double *Z;   // nrows x ZS   (basis columns 1..B-1)
   const double *LZ;  // nrows x ZS   log|z| (SE only; may be null for Matern)
   int64_t n;         // valid rows
+  // slice masks of the 64-point blocks (ace_zero_pattern_order; the fused
+  // model's training side only): bit b - 1 of mask[k] is clear when z_b is
+  // exactly zero on every point of block k, so a pair tile whose row or
+  // column block has it clear skips slice b.  Null: every slice
+  // of every tile runs.  Read by the MFMA assembly and gradient tiles alone.
+  const uint32_t *mask = nullptr;
 };
+
+// ACE_ZSKIP for a model of n points: 2 the fused model groups its points by
+// zero pattern and the pair tiles skip all-zero slices, 1 skip only (given
+// order), 0 neither.  Unset: 2 above n = 8192, else 1 -- the reorder changes
+// rounding, and up to that size the model's inverse stays bit-identical to
+// the handle path's (which keeps the given order), as
+// tests/test_r6_handles_gpu.py holds it.
+int zskip_mode(int64_t n);
 
 // ---- assembly --------------------------------------------------------------
 // mode 0: fused eval -- lower 64-tiles of the n_pad x n_pad block of A (ld),

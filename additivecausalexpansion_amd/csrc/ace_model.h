@@ -174,6 +174,17 @@ struct ace_model {
   bool has_data = false;
   bool has_inverse = false;  // a para_update has left a resident inverse
   SideBufs side;
+  // ACE_ZSKIP: the device holds point perm[k] of the caller's
+  // data at position k (empty: the given order) and the slice masks of its
+  // 64-point blocks (npad / 64 words; none: every slice of every tile runs)
+  std::vector<int64_t> perm;
+  DBuf zmask;
+  bool has_zmask = false;
+  PairSide train_side() const {  // the pair kernels' operand, mask included
+    PairSide ps = side.view(n);
+    if (has_zmask) ps.mask = static_cast<const uint32_t *>(zmask.p);
+    return ps;
+  }
   DBuf y, tab, alpha, gpart, gwork;
   // the evaluation's results in one block, read back by one copy:
   // [gsum: grad_part_cols | sums: 8 (sums[4] = the sweep's flag) | scal: 16]
@@ -208,8 +219,10 @@ struct ace_model {
 void assemble_and_sweep(ace_ctx *ctx, SweepWork &w, const Shape &s, const PairSide &ps,
                         const TabView &tv, double sig, const double *y, int64_t n,
                         const SweepTiming *tmg, hipEvent_t *ev_asm);
-// the gradient's XCD-dealt tile list for n (ace_api.cpp)
-void build_grad_tiles(ace_ctx *ctx, int64_t n, DBuf &tiles, int64_t *ntiles, int64_t *ndiag);
+// the gradient's XCD-dealt tile list for n (ace_api.cpp); mask (host, the
+// blocks' slice masks): each XCD's tiles with the most active slices first
+void build_grad_tiles(ace_ctx *ctx, int64_t n, DBuf &tiles, int64_t *ntiles, int64_t *ndiag,
+                      const uint32_t *mask = nullptr);
 
 // Operands of the device prediction pipeline (pred_pipeline, ace_predict.cpp).
 struct PredOps {

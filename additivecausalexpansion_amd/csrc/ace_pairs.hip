@@ -671,6 +671,11 @@ bool pairs_use_mm(int PM, bool grad) {
   return v != 0;
 }
 
+int zskip_mode(int64_t n) {
+  static const int v = env_set("ACE_ZSKIP") ? std::max(0, std::min(2, env_int("ACE_ZSKIP", 2))) : -1;
+  return v >= 0 ? v : (n > 8192 ? 2 : 1);
+}
+
 hipError_t launch_assembly(int mode, int kind, int PM, PairSide R, PairSide C, int64_t npad,
                            int B, int ZS, TabView tab, double sig, double *out, int64_t ld,
                            double *cube, hipStream_t st, const Tile *tiles, int64_t ntiles,

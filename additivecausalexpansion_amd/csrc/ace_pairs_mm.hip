@@ -64,6 +64,10 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 #ifndef ACE_GRAD_TAIL4
 #define ACE_GRAD_TAIL4 1
 #endif
+// timing diagnostics of k_grad_mm's slice loop (results wrong; see there)
+#ifndef ACE_DIAG_GRAD
+#define ACE_DIAG_GRAD 0
+#endif
 #define MM_PAIR_FENCE(cb, v) \
   if (ACE_MM_PG > 0 && ((4 * (cb) + (v) + 1) % (ACE_MM_PG > 0 ? ACE_MM_PG : 1)) == 0) \
     __builtin_amdgcn_sched_barrier(0)
@@ -377,6 +381,19 @@ __device__ __forceinline__ void tile_of(const Tile *tiles, int64_t t, int64_t &I
   }
 }
 
+// Slices of tile (I, J) that can be nonzero (PairSide::mask): bit b - 1 for
+// slice b >= 1, set when the row block and the column block both hold a
+// nonzero z_b; slice 0 (z = 1) always runs.  Wave-uniform in a scalar
+// register, so the slice loops branch on it without a VGPR.
+__device__ __forceinline__ unsigned tile_slices(const uint32_t *__restrict__ mask, int64_t I,
+                                                int64_t J) {
+  if (!mask) return ~0u;
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)(mask[I] & mask[J]));
+}
+__device__ __forceinline__ bool slice_on(unsigned act, int b) {
+  return b == 0 || ((act >> (b - 1)) & 1u) != 0;
+}
+
 // ---------------------------------------------------------------------------
 // Per-tile staging shared by both kernels (dynamic LDS, doubles):
 //   XJ  [64][XP]      column-side covariates (gradient, PM % 16 != 0: [x | x^2])
@@ -661,11 +678,15 @@ __device__ __forceinline__ void asm_mm_tile(double *lds, PairSide S, int B, int 
   for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
     for (int v = 0; v < 4; ++v) kf[cb][v] = 0.0;
+  const unsigned act = tile_slices(S.mask, I, J);
   // diagonal tiles (I == J) need the r == c and r < c tests; below the
   // diagonal r > c for every pair
   auto slices = [&](auto diag) {
     constexpr bool DG = decltype(diag)::value;
     for (int b = 0; b < B; ++b) {
+      // z_b = 0 on the whole row or column block: every K_b of the tile is a
+      // zero of either sign and kf + it is kf (slice 0 came first)
+      if (!slice_on(act, b)) continue;
       // issued ahead of GEMM1, which hides the latency; slice 0 as z = 1,
       // log|z| = 0 (L.Z / L.LZ row -1), so the pairs need no slice test
       double zr = 1.0, lzr = 0.0;
@@ -1040,6 +1061,7 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
     ++I;                                 // (I, J) with J <= I  ->  (I + 1, J), J < I + 1
   }
   if (G > 1) A += (lcol(J * AT, G) - J * AT) * ld;
+  const unsigned act0 = tile_slices(S.mask, I, J);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int lr = lane & 15, lk = lane >> 4;
   const int wr = w & 3;                      // row block of the wave
@@ -1097,19 +1119,51 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
   }
   double fc[CB][4];  // Matern: 1 + sqrt3 t of slice b+1
   d4 acc[CB];
-  if (KIND == 1) {  // Matern, last slice: r~2 with its own weights
-    gemm1_mm<XP, CB>(L.XJ, xr, L.W + B * PM, lr, lk, acc, cbase);
-    const double sr = L.Nr[B * 64 + rl];
-    const double *nc = L.Nc + B * 64 + cbase;
+  // Matern: the first slice the loop runs, `top`, divides by the factor of
+  // the slice above it.  top = B - 1 (nothing skipped above): r~2 with the
+  // last slice's own weights (slot B of the staged weights and norms).
+  // Otherwise slice top + 1 was skipped and only its factor is formed here:
+  // its GEMM1 and square root, the slice loop's expressions, so fc gets the
+  // bits that slice would have left.  Further down, a skipped slice directly
+  // above a running one is run after all (act below): it leaves its factor
+  // in fc like any slice and contributes its exact zeros; its own divisor may
+  // be any slice's factor (finite, >= 1: zero / f is the same zero).  With
+  // the spline bases' nested patterns there is no such slice.
+  unsigned act = act0;
+  if (KIND == 1) {
+    int top = B - 1;
+    if (S.mask) {
+      const unsigned m = act0 & (B - 1 >= 32 ? ~0u : (1u << (B - 1)) - 1u);
+      top = m ? 32 - __builtin_clz(m) : 0;
+      const unsigned below = top >= 32 ? ~0u : (1u << top) - 1u;  // slices 1 .. top
+      act = m | (((m << 1) | 1u) & below);
+    }
+    const int s = top == B - 1 ? B : top + 1;
+    gemm1_mm<XP, CB>(L.XJ, xr, L.W + s * PM, lr, lk, acc, cbase);
+    const double sr = L.Nr[s * 64 + rl];
+    const double *nc = L.Nc + s * 64 + cbase;
+    if (top == B - 1) {
 #pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
+      for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int cl = 16 * cb + lk + 4 * v;
-        double rt2 = fmax(fma(-2.0, acc[cb][v], sr + nc[cl]), 0.0);
-        if (DG && C0 + cbase + cl == r) rt2 = 0.0;
-        fc[cb][v] = 1.0 + sqrt_pk(3.0 * rt2);
-      }
+        for (int v = 0; v < 4; ++v) {
+          const int cl = 16 * cb + lk + 4 * v;
+          double rt2 = fmax(fma(-2.0, acc[cb][v], sr + nc[cl]), 0.0);
+          if (DG && C0 + cbase + cl == r) rt2 = 0.0;
+          fc[cb][v] = 1.0 + sqrt_pk(3.0 * rt2);
+        }
+    } else {
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int cl = 16 * cb + lk + 4 * v;
+          double r2 = fmax(fma(-2.0, acc[cb][v], sr + nc[cl]), 1e-300);
+          if (DG && C0 + cbase + cl == r) r2 = 1e-300;
+          const double tt = (ACE_DIAG_GRAD & 4) ? r2 : sqrt_gs(r2);
+          fc[cb][v] = fma(SQRT3, tt, 1.0);  // one rounding, as in the slice loop
+        }
+    }
   }
   // gpart[b][i] of this tile from slice b's partials: the waves' x parts,
   // sum_c x_ci^2 C_c, and (i == PM) the waves' sums of T K
@@ -1150,13 +1204,21 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
   // 2 only the last slice; bits 4 / 8 / 16 / 32 drop the sqrt / exp /
   // reciprocal / GEMM2 of the Matern slice loop; bit 64 the per-slice
   // partials' combination after the loop (column-sum combine + feature dots)
-#ifndef ACE_DIAG_GRAD
-#define ACE_DIAG_GRAD 0
-#endif
   const int bstop = (ACE_DIAG_GRAD & 3) == 1 ? B : (ACE_DIAG_GRAD & 3) == 2 ? B - 1 : 0;
+  // Skipped slices (tile_slices): every U of the slice is a zero of either
+  // sign, so its partial sums are written as 0.0 here and its Red buffer
+  // stays unwritten (the combines below pass over it).  nrun: slices run so
+  // far -- the two-buffer form alternates on it, not on b, so that a barrier
+  // still lies between two uses of a buffer.
+  int nrun = 0;
 #pragma unroll 1
   for (int b = B - 1; b >= bstop; --b) {
-    double *red = L.Red + (per_slice ? b : (b & 1)) * PER;
+    if (!slice_on(act, b)) {
+      if (tid < NV) gpart[t * ldg + (int64_t)b * NV + tid] = 0.0;
+      continue;
+    }
+    double *red = L.Red + (per_slice ? b : (nrun & 1)) * PER;
+    ++nrun;
     double zr = 1.0, lzr = 0.0;  // issued ahead of GEMM1, which hides the latency
     if (b > 0) {
       zr = S.Z[r * ZS + b - 1];
@@ -1196,7 +1258,9 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
           kb = sel_f64(zlo == 0.0 || zhi == 0.0, 0.0, kz);
         } else {
           const double tt = (ACE_DIAG_GRAD & 4) ? r2 : sqrt_gs(r2);
-          f = 1.0 + SQRT3 * tt;
+          // (an explicit fma -- what the compiler contracted 1 + sqrt3 t to
+          // anyway -- so that the factor pass above forms the same bits)
+          f = fma(SQRT3, tt, 1.0);
           const double e = (ACE_DIAG_GRAD & 8) ? f * (lam - SQRT3 * tt) : f * exp_grad(lam - SQRT3 * tt, L.E);
           // z = 0 gives a zero product (of either sign: it only enters sums)
           kb = (e * zlo) * zhi;
@@ -1344,6 +1408,7 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
     // each slice's four row-block column sums added once (same expression,
     // so bit-identical), not once per feature
     for (int e = tid; e < B * 64; e += NT) {
+      if (!slice_on(act, e >> 6)) continue;  // skipped: nobody wrote its buffer
       double *cc = L.Red + (e >> 6) * PER + NWV * RS;
       const int c = e & 63;
       cc[c] = (cc[c] + cc[64 + c]) + (cc[128 + c] + cc[192 + c]);
@@ -1351,6 +1416,7 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
     __syncthreads();
     for (int e = tid; e < B * NV; e += NT) {
       const int bb = e / NV, i = e - bb * NV;
+      if (!slice_on(act, bb)) continue;  // (its gpart entries are the loop's zeros)
       finish(bb, L.Red + bb * PER, i, true);
     }
   }

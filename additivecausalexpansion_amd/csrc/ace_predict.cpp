@@ -450,10 +450,14 @@ void coef_cross(ace_model *m, const double *theta, int64_t nx, const double *X2,
     slice_assembly(ctx, s, tc, train, tv, dK.d());
     download(ctx, h.data(), dK.d(), (size_t)(ldk * n), "download Kc");
     sync(ctx);
+    // (q: the device's training point, the caller's perm[q] when the model
+    // holds its points in the zero-pattern order)
     for (int b = 0; b < B; ++b)
-      for (int64_t q = 0; q < n; ++q)
+      for (int64_t q = 0; q < n; ++q) {
+        const int64_t qo = m->perm.empty() ? q : m->perm[(size_t)q];
         for (int64_t c = 0; c < nc; ++c)
-          out[c0 + c + nx * (q + n * b)] = h[(size_t)(c + nc * b + q * ldk)];
+          out[c0 + c + nx * (qo + n * b)] = h[(size_t)(c + nc * b + q * ldk)];
+      }
   }
 }
 
@@ -593,12 +597,24 @@ int ace_model_apply_inverse(ace_model *m, int64_t k, const double *V, double *ou
   require_inverse(m);
   const int64_t n = m->n;
   DBuf dV, dout, dtmp;
-  upload(ctx, dV, V, (size_t)(n * k), "upload V");
+  // a model that holds its points in the zero-pattern order (ace_model::perm):
+  // V's rows go in, and the result's rows come back, through that order
+  const std::vector<int64_t> &perm = m->perm;
+  std::vector<double> hp;
+  if (!perm.empty()) {
+    hp.resize((size_t)(n * k));
+    for (int64_t c = 0; c < k; ++c)
+      for (int64_t q = 0; q < n; ++q) hp[(size_t)(q + c * n)] = V[perm[(size_t)q] + c * n];
+  }
+  upload(ctx, dV, perm.empty() ? V : hp.data(), (size_t)(n * k), "upload V");
   alloc(ctx, dout, (size_t)(n * k) * sizeof(double), "alloc out");
   symm_resident(m, dV.d(), n, false, k, dout.d(), dtmp);
   if (m->shard) shard_allreduce_sum(m->shard, dout.d(), n * k);
-  download(ctx, out, dout.d(), (size_t)(n * k), "download out");
+  download(ctx, perm.empty() ? out : hp.data(), dout.d(), (size_t)(n * k), "download out");
   sync(ctx);
+  if (!perm.empty())
+    for (int64_t c = 0; c < k; ++c)
+      for (int64_t q = 0; q < n; ++q) out[perm[(size_t)q] + c * n] = hp[(size_t)(q + c * n)];
   return ACE_OK;
   ACE_CATCH
 }

@@ -419,6 +419,26 @@ def robust_levels(var, n_steps):
     return thr, level
 
 
+def zero_pattern_order(Z):
+    """ace_zero_pattern_order: the stable order of the rows of Z (n x ZS) by
+    their pattern of exact zeros, fewest nonzero columns first, and the slice
+    masks of the 64-point blocks of that order (bit j: some point of the block
+    has a nonzero z in column j; a last block that is not full has every bit
+    set).  Returns (perm (int64), blockmask (uint32) or None for ZS > 32)."""
+    Zf = fmat(Z)
+    if Zf.ndim != 2 or Zf.shape[0] < 1:
+        raise AceError("Z must be n x ZS with n >= 1")
+    n, ZS = Zf.shape
+    perm = np.empty(n, dtype=np.int64)
+    mask = np.zeros((n + 63) // 64, dtype=np.uint32)
+    has = np.zeros(1, dtype=np.int32)
+    check(lib().ace_zero_pattern_order(n, ZS, ptr(Zf) if ZS else None,
+                                       perm.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                       mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                       has.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return perm, (mask if has[0] else None)
+
+
 def coef_contract(mean, cov, W, offset=0.0, scale=1.0, shift=0.0, noise=0.0):
     """ace_coef_contract: a coefficient posterior (mean nx x B, cov nx x B x B)
     contracted with the nz weight rows W (nz x B), the tails of pred_cpp /

@@ -235,6 +235,20 @@ int ace_normalize_train(int64_t n, int px, int pz, double *y, double *X,
 int ace_normalize_test(int64_t n, int px, int pz, double *X, double *Z,
                        const double *moments, int64_t moment_rows);
 
+/* The zero-pattern order of a basis Z (n x ZS, column-major) and the slice
+ * masks of its 64-point blocks (host only, no context): what
+ * ace_model_set_data computes for the pair kernels' slice skip (DESIGN.md
+ * §14).  A point's pattern is the set of columns where its z is nonzero
+ * (+0.0 and -0.0 are both zero).  perm (n): the points sorted by pattern,
+ * fewest nonzero columns first; points with equal patterns keep their input
+ * order (a Z without exact zeros gives the identity).  blockmask
+ * (ceil(n / 64) words, may be NULL): bit j of word k is set when any of the
+ * points perm[64 k .. 64 k + 63] has a nonzero z in column j; a last block
+ * that is not full is marked fully active.  For ZS > 32 no mask is built
+ * (*has_mask = 0, blockmask untouched): every slice counts as active. */
+int ace_zero_pattern_order(int64_t n, int ZS, const double *Z, int64_t *perm,
+                           uint32_t *blockmask, int32_t *has_mask);
+
 /* ------------------------------- device-resident hot path (one model fit)
  *
  * The R6 kernel classes ship Kmat, the n x n x B cube and invKmatn through
