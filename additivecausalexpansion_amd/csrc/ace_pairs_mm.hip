@@ -160,109 +160,11 @@ __device__ __forceinline__ double exp_tb5(double x, const double *tab) {
   return __builtin_amdgcn_ldexp(q * tab[ki & 31], ki >> 5);
 }
 
-// 2^(j/128), j = 0..127, correctly rounded (Python Decimal at 60 digits)
-__device__ const double kExp2Tab128[128] = {
-    1.0, 1.0054299011128027, 1.0108892860517005, 1.016378314910953,
-    1.0218971486541166, 1.0274459491187637, 1.0330248790212284, 1.0386341019613787,
-    1.0442737824274138, 1.0499440858006872, 1.0556451783605572, 1.061377227289262,
-    1.0671404006768237, 1.0729348675259756, 1.0787607977571199, 1.0846183622133092,
-    1.0905077326652577, 1.0964290818163769, 1.102382583307841, 1.1083684117236787,
-    1.1143867425958924, 1.1204377524096067, 1.1265216186082418, 1.1326385195987192,
-    1.1387886347566916, 1.1449721444318042, 1.1511892299529827, 1.1574400736337511,
-    1.1637248587775775, 1.1700437696832502, 1.1763969916502812, 1.182784710984341,
-    1.189207115002721, 1.1956643920398273, 1.202156731452703, 1.2086843236265816,
-    1.215247359980469, 1.2218460329727576, 1.22848053610687, 1.2351510639369334,
-    1.241857812073484, 1.2486009771892048, 1.255380757024691, 1.2621973503942507,
-    1.2690509571917332, 1.275941778396392, 1.2828700160787783, 1.2898358734066657,
-    1.2968395546510096, 1.3038812651919358, 1.3109612115247644, 1.318079601266064,
-    1.3252366431597413, 1.3324325470831615, 1.339667524053303, 1.3469417862329458,
-    1.3542555469368927, 1.3616090206382248, 1.3690024229745905, 1.3764359707545302,
-    1.383909881963832, 1.3914243757719262, 1.3989796725383112, 1.4065759938190154,
-    1.4142135623730951, 1.4218926021691656, 1.42961333839197, 1.4373759974489824,
-    1.4451808069770467, 1.4530279958490526, 1.460917794180647, 1.4688504333369818,
-    1.4768261459394993, 1.4848451658727524, 1.4929077282912648, 1.5010140696264256,
-    1.5091644275934228, 1.5173590411982147, 1.5255981507445384, 1.533881997840956,
-    1.5422108254079407, 1.550584877685, 1.559004400237837, 1.567469639965553,
-    1.5759808451078865, 1.5845382652524937, 1.593142151342267, 1.6017927556826934,
-    1.6104903319492543, 1.6192351351948637, 1.6280274218573478, 1.6368674497669644,
-    1.645755478153965, 1.6546917676561943, 1.6636765803267364, 1.6727101796415966,
-    1.681792830507429, 1.6909247992693053, 1.7001063537185235, 1.709337763100463,
-    1.718619298122478, 1.7279512309618377, 1.7373338352737062, 1.746767386199169,
-    1.7562521603732995, 1.7657884359332727, 1.7753764925265212, 1.785016611318935,
-    1.7947090750031072, 1.804454167806624, 1.8142521755003989, 1.8241033854070534,
-    1.8340080864093424, 1.843966568958626, 1.8539791250833855, 1.864046048397789,
-    1.8741676341103, 1.8843441790323345, 1.8945759815869656, 1.9048633418176741,
-    1.9152065613971474, 1.925605943636125, 1.9360617934922943, 1.9465744175792332,
-    1.9571441241754002, 1.9677712232331759, 1.978456026387951, 1.9891988469672663,
-};
-// exp for the gradient's trace factors (ACE_GRAD_EXP=2): the 128-entry
-// table, |r| <= ln2/256, degree-4 Taylor (truncation < 1.3e-15 relative, the
-// degree-5 / 32-entry form's class) -- one FMA fewer per pair than exp_tb5.
-// The split of ln2/128 is exp_tb's ln2/32 split divided by 4 (exact).
-__device__ __forceinline__ double exp_tb128(double x, const double *tab) {
-  const double kf = __builtin_rint(x * 184.66496523378732);  // 128 / ln2
-  double r = fma(-kf, 0.02166084938653512 * 0.25, x);          // (ln2 / 128) hi
-  r = fma(-kf, 5.9631716539705866e-12 * 0.25, r);              // (ln2 / 128) lo
-  const int ki = (int)kf;
-  double q = 1.0 / 24.0;
-  q = fma(q, r, 1.0 / 6.0);
-  q = fma(q, r, 0.5);
-  q = fma(q, r, 1.0);
-  q = fma(q, r, 1.0);
-  return __builtin_amdgcn_ldexp(q * tab[ki & 127], ki >> 7);
-}
-
-// Table-free form for the gradient's trace factors (ACE_GRAD_EXP=1):
-// x = m ln2 + r, |r| <= ln2/2, exp(r) by a degree-10 polynomial with the
-// first three Taylor coefficients pinned and the rest fitted on Chebyshev
-// nodes against an extended-precision exp (3.9e-16 relative over the
-// interval), so the per-pair chain has no LDS lookup.
-#ifndef ACE_GRAD_EXP
-#define ACE_GRAD_EXP 0
-#endif
-__device__ __forceinline__ double exp_pl(double x) {
-  const double kf = __builtin_rint(x * 1.4426950408889634);  // 1 / ln2
-  double r = fma(-kf, 0.6931471805599453, x);                 // ln2 hi
-  r = fma(-kf, 2.3190468138462996e-17, r);                    // ln2 lo
-  double q = 2.7545674171354605e-07;
-  q = fma(q, r, 2.763525742080496e-06);
-  q = fma(q, r, 2.4801715258403783e-05);
-  q = fma(q, r, 0.0001984118454548405);
-  q = fma(q, r, 0.001388888875659234);
-  q = fma(q, r, 0.008333333371438512);
-  q = fma(q, r, 0.04166666666704061);
-  q = fma(q, r, 0.1666666666661009);
-  q = fma(q, r, 0.5);
-  q = fma(q, r, 1.0);
-  q = fma(q, r, 1.0);
-  return __builtin_amdgcn_ldexp(q, (int)kf);
-}
-__device__ __forceinline__ double exp_grad(double x, const double *tab) {
-  return ACE_GRAD_EXP == 2 ? exp_tb128(x, tab) : ACE_GRAD_EXP ? exp_pl(x) : exp_tb5(x, tab);
-}
-// degree-11 form of exp_pl (7e-18 relative over the interval) for the
-// assembly (ACE_ASM_EXP=1): K enters the inverse
+// exp of the assembly and the cross tiles (K enters the inverse): 2 (default)
+// exp_tb64 below, 0 exp_tb
 #ifndef ACE_ASM_EXP
 #define ACE_ASM_EXP 2
 #endif
-__device__ __forceinline__ double exp_pl11(double x) {
-  const double kf = __builtin_rint(x * 1.4426950408889634);
-  double r = fma(-kf, 0.6931471805599453, x);
-  r = fma(-kf, 2.3190468138462996e-17, r);
-  double q = 2.491759739472051e-08;
-  q = fma(q, r, 2.762544312686786e-07);
-  q = fma(q, r, 2.75578396598084e-06);
-  q = fma(q, r, 2.480150797092874e-05);
-  q = fma(q, r, 0.00019841269233459403);
-  q = fma(q, r, 0.0013888888927429829);
-  q = fma(q, r, 0.008333333333614103);
-  q = fma(q, r, 0.04166666666660212);
-  q = fma(q, r, 0.16666666666666238);
-  q = fma(q, r, 0.5);
-  q = fma(q, r, 1.0);
-  q = fma(q, r, 1.0);
-  return __builtin_amdgcn_ldexp(q, (int)kf);
-}
 // 2^(j/64), j = 0..63, correctly rounded (Python Decimal at 60 digits)
 __device__ const double kExp2Tab64[64] = {
     1.0, 1.0108892860517005, 1.0218971486541166, 1.0330248790212284,
@@ -299,7 +201,7 @@ __device__ __forceinline__ double exp_tb64(double x, const double *tab) {
   return __builtin_amdgcn_ldexp(q * tab[ki & 63], ki >> 6);
 }
 __device__ __forceinline__ double exp_asm(double x, const double *tab) {
-  return ACE_ASM_EXP == 2 ? exp_tb64(x, tab) : ACE_ASM_EXP ? exp_pl11(x) : exp_tb(x, tab);
+  return ACE_ASM_EXP == 2 ? exp_tb64(x, tab) : exp_tb(x, tab);
 }
 
 
@@ -428,7 +330,7 @@ __host__ __device__ inline MmLayout mm_layout(int PM, int B, int KIND, bool grad
   const int NS = (grad && KIND == 1) ? B + 1 : B;
   int off = 0;
   o.etab = off;
-  off += (grad && ACE_GRAD_EXP == 2) ? 128 : (!grad && ACE_ASM_EXP == 2) ? 64 : 32;
+  off += (!grad && ACE_ASM_EXP == 2) ? 64 : 32;
   o.xj = off;
   off += 64 * xj_pitch(PM);
   o.xi = off;
@@ -496,9 +398,7 @@ __device__ __forceinline__ MmLds mm_stage(double *lds, PairSide S, int B, int ZS
     L.Z[tid - 64] = 1.0;
     if (KIND == 0) L.LZ[tid - 64] = 0.0;
   }
-  if (GRAD && ACE_GRAD_EXP == 2) {
-    for (int e = tid; e < 128; e += NT) L.E[e] = kExp2Tab128[e];
-  } else if (!GRAD && ACE_ASM_EXP == 2) {
+  if (!GRAD && ACE_ASM_EXP == 2) {
     if (tid < 64) L.E[tid] = kExp2Tab64[tid];
   } else if (tid < 32) {
     L.E[tid] = kExp2Tab[tid];
@@ -639,13 +539,9 @@ static int asm_first_cols(int nt) {
   return jb < nt ? jb : nt;
 }
 
-// Column blocks per wave of the assembly: ACE_ASM_CB = 4 (256 threads, 16
-// pairs per lane) or 2 (512 threads, wave w: rows 16 (w & 3).., columns
-// 32 (w >> 2)..; 8 pairs per lane), the gradient kernel's layout.
-#ifndef ACE_ASM_CB
-#define ACE_ASM_CB 4
-#endif
-constexpr int ASM_NT = 64 * 4 * (4 / ACE_ASM_CB);
+// The assembly: 256 threads, wave w holds rows 16 w.., all 64 columns (16
+// pairs per lane in 4 column blocks)
+constexpr int ASM_NT = 256;
 // One lower 64-tile (I, J) of the assembly (k_asm_mm, k_asm_mm_q)
 template <int PM, int KIND, bool LOWER = false>
 __device__ __forceinline__ void asm_mm_tile(double *lds, PairSide S, int B, int ZS, const TabView &tab,
@@ -657,13 +553,17 @@ __device__ __forceinline__ void asm_mm_tile(double *lds, PairSide S, int B, int 
     out += coff * ld;
     if (kcopy) kcopy += coff * ld;
   }
-  constexpr int CB = ACE_ASM_CB;
+  constexpr int CB = 4;
   int tid = threadIdx.x;
   // LOWER (the persistent loop): the lane's indices opaque per tile, so the
   // compiler does not hoist every lane-derived address out of the tile loop
   if (LOWER) __asm__ volatile("" : "+v"(tid));
   const int lane = tid & 63, w = tid >> 6;
   const int lr = lane & 15, lk = lane >> 4;
+  // The wave's row block and first column, w and 0 at 256 threads, stay
+  // derived from the lane: with a constant 0 the compiler hoists the lane's
+  // column addresses out of k_asm_mm_q's tile loop after all (112 - 134 ->
+  // 126 - 148 VGPRs, 4 -> 3 waves per SIMD at PM >= 48)
   const int wr = w & 3, cbase = 16 * CB * (w >> 2);
   const int64_t R0 = I * AT, C0 = J * AT, n = S.n;
   const int rl = 16 * wr + lr;
@@ -735,11 +635,9 @@ __device__ __forceinline__ void asm_mm_tile(double *lds, PairSide S, int B, int 
 }
 
 template <int PM, int KIND>
-__global__ __launch_bounds__(ASM_NT, (ACE_ASM_CB == 2 ? 4 : PM <= 32 ? 3 : 2)) void k_asm_mm(PairSide S, int B, int ZS, TabView tab,
-                                                double sig, double *__restrict__ out, int64_t ld,
-                                                double *__restrict__ kcopy,
-                                                const Tile *__restrict__ tiles, int G, int part,
-                                                int nt, int JB) {
+__global__ __launch_bounds__(ASM_NT, PM <= 32 ? 3 : 2) void k_asm_mm(
+    PairSide S, int B, int ZS, TabView tab, double sig, double *__restrict__ out, int64_t ld,
+    double *__restrict__ kcopy, const Tile *__restrict__ tiles, int G, int part, int nt, int JB) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const double sg = tab.sig ? *tab.sig : sig;  // exp(theta[0]) on the diagonal
   int64_t I, J;
@@ -781,46 +679,73 @@ __global__ __launch_bounds__(ASM_NT, (ACE_ASM_CB == 2 ? 4 : PM <= 32 ? 3 : 2)) v
 // k_assembly<PM, KIND, 2> (lane = row, p FMAs per pair and slice on the
 // VALU: 10.8 TF/s at n = 16384, nx = 4096).
 // ---------------------------------------------------------------------------
-template <int PM, int KIND>
-__global__ __launch_bounds__(256, PM <= 32 ? 4 : 2) void k_cross_mm(PairSide R, PairSide C, int B,
-                                                                   int ZS, TabView tab, int b0,
-                                                                   int b1,
-                                                                   double *__restrict__ out,
-                                                                   int64_t ld) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
+// The two-sided tile (k_cross_mm, k_cross_slices_mm, k_group_mm).  Its LDS
+// is the assembly's layout with the row side's 64 points XI behind it at the
+// column side's pitch (cross_mm_lds); slice b's basis row is at
+// Zc + (b - 1) * 64, b = 0 (the unit row) included.  The pieces below take a
+// side each, because k_group_mm stages its rows once per strip and its
+// columns once per tile.
+// The pointers are plain locals and every piece names the ones it uses: held
+// in a struct (as MmLds is), they cost k_group_mm 3 - 5 VGPRs at most PM with
+// the other pieces unchanged -- at PM = 64, SE, 168 -> 172 and with that the
+// third wave per SIMD.
+#define CROSS_LDS_POINTERS(lds, PM, B, KIND)                                                   \
+  const MmLayout o = mm_layout(PM, B, KIND, false);                                            \
+  double *const E = lds + o.etab, *const XJ = lds + o.xj, *const Zc = lds + o.z + 64,          \
+               *const LZc = lds + o.lz + 64, *const Nc = lds + o.nc, *const Nr = lds + o.nr,   \
+               *const W = lds + o.w, *const XI = lds + o.total
+
+// The 64 points from C0 of the column side (COLS) and from R0 of the row side
+// (ROWS), coalesced, zeros past either side's n.  Both sides' points are
+// staged, so the row side's slice norms are LDS loops too, not PM dependent
+// global loads per thread.
+template <int PM, bool COLS, bool ROWS>
+__device__ __forceinline__ void cross_stage_x(double *XJ, double *XI, const PairSide &C,
+                                              int64_t C0, const PairSide &R, int64_t R0,
+                                              int tid) {
   constexpr int XP = xj_pitch(PM);
-  const int64_t J = blockIdx.x, I = blockIdx.y;
-  const int64_t R0 = I * AT, C0 = J * AT;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, w = tid >> 6;
-  const int lr = lane & 15, lk = lane >> 4;
-  const MmLayout o = mm_layout(PM, B, KIND, false);
-  double *const E = lds + o.etab, *const XJ = lds + o.xj, *const Zc = lds + o.z + 64,
-               *const LZc = lds + o.lz + 64, *const Nc = lds + o.nc, *const Nr = lds + o.nr,
-               *const W = lds + o.w, *const XI = lds + o.total;
-  // both sides' points staged (coalesced): the row side's slice norms are
-  // then LDS loops too, not PM dependent global loads per thread
   for (int e = tid; e < 64 * PM; e += 256) {
     const int c = e / PM, i = e - c * PM;
-    XJ[c * XP + i] = (C0 + c < C.n) ? C.X[(C0 + c) * PM + i] : 0.0;
-    XI[c * XP + i] = (R0 + c < R.n) ? R.X[(R0 + c) * PM + i] : 0.0;
+    if (COLS) XJ[c * XP + i] = (C0 + c < C.n) ? C.X[(C0 + c) * PM + i] : 0.0;
+    if (ROWS) XI[c * XP + i] = (R0 + c < R.n) ? R.X[(R0 + c) * PM + i] : 0.0;
   }
+}
+
+// The column side's basis rows of slices 1 .. B - 1 (none at B = 1)
+template <int KIND>
+__device__ __forceinline__ void cross_stage_z(double *Zc, double *LZc, const PairSide &C,
+                                              int64_t C0, int B, int ZS, int tid) {
   for (int e = tid; e < (B - 1) * 64; e += 256) {
     const int bb = e >> 6, c = e & 63;
     const bool ok = C0 + c < C.n;
     Zc[e] = ok ? C.Z[(C0 + c) * ZS + bb] : 0.0;
     if (KIND == 0) LZc[e] = ok ? C.LZ[(C0 + c) * ZS + bb] : 0.0;
   }
-  if (tid < 64) {  // slice 0: z = 1, log|z| = 0
+}
+
+// Slice 0's unit row (z = 1, log|z| = 0: no per-pair slice test, kval_nb),
+// the exp table and the slice weights
+template <int PM, int KIND>
+__device__ __forceinline__ void cross_stage_tab(double *E, double *Zc, double *LZc, double *W,
+                                                const TabView &tab, int B, int tid) {
+  if (tid < 64) {
     Zc[tid - 64] = 1.0;
     if (KIND == 0) LZc[tid - 64] = 0.0;
     if (ACE_ASM_EXP == 2) E[tid] = kExp2Tab64[tid];
     else if (tid < 32) E[tid] = kExp2Tab[tid];
   }
   for (int e = tid; e < B * PM; e += 256) W[e] = tab.wk[e];
-  __syncthreads();
-  for (int e = tid; e < 2 * B * 64; e += 256) {
-    const int side = e / (B * 64), rem = e - side * B * 64;
+}
+
+// Slice norms of the staged points (i ascending, fma(x^2, w, s), as
+// k_slice_norms): Nc from XJ (COLS), Nr from XI (ROWS), or both in one loop
+template <int PM, bool COLS, bool ROWS>
+__device__ __forceinline__ void cross_norms(const double *XJ, const double *XI, const double *W,
+                                            double *Nc, double *Nr, int B, int tid) {
+  constexpr int XP = xj_pitch(PM);
+  for (int e = tid; e < (COLS && ROWS ? 2 : 1) * B * 64; e += 256) {
+    const int side = (COLS && ROWS) ? e / (B * 64) : (COLS ? 0 : 1);
+    const int rem = e - side * (COLS && ROWS ? B * 64 : 0);
     const int sl = rem >> 6, pt = rem & 63;
     const double *wv = W + sl * PM;
     double s = 0.0;
@@ -840,43 +765,75 @@ __global__ __launch_bounds__(256, PM <= 32 ? 4 : 2) void k_cross_mm(PairSide R, 
       Nr[rem] = s;
     }
   }
+}
+
+// One slice of the tile, added to kf: GEMM1, then per pair r2 and K_b with
+// the row factors zr / lzr (slice 0 and k_cross_slices_mm: 1 and 0).  Every
+// pair of the slice stays in one basic block (see kval_nb).
+template <int PM, int KIND>
+__device__ __forceinline__ void cross_slice_pairs(double (&kf)[4][4], const double *XJ,
+                                                  const double *W, const double *Nr,
+                                                  const double *Nc, const double *Zc,
+                                                  const double *LZc, const double *E,
+                                                  const RowX<PM> &xr, const TabView &tab, int b,
+                                                  double zr, double lzr, int rl, int lr, int lk) {
+  d4 acc[4];
+  gemm1_mm<xj_pitch(PM), 4>(XJ, xr, W + b * PM, lr, lk, acc, 0);
+  const double sr = Nr[b * 64 + rl];
+  const double *nc = Nc + b * 64;
+  const double *zcol = Zc + (b - 1) * 64, *lzcol = LZc + (b - 1) * 64;
+  const double lam = tab.lam[b];
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int cl = 16 * cb + lk + 4 * v;
+      // Matern: r2 >= 1e-300 (sqrt_pk_pos's domain; the same K as 0)
+      constexpr double R2MIN = KIND == 1 ? 1e-300 : 0.0;
+      const double r2 = fmax(fma(-2.0, acc[cb][v], sr + nc[cl]), R2MIN);
+      const double zc = zcol[cl];
+      const double lzc = KIND == 0 ? lzcol[cl] : 0.0;
+      kf[cb][v] += kval_nb<KIND>(r2, lam, zr, zc, lzr, lzc, E);
+      MM_PAIR_FENCE(cb, v);
+    }
+}
+
+template <int PM, int KIND>
+__global__ __launch_bounds__(256, PM <= 32 ? 4 : 2) void k_cross_mm(PairSide R, PairSide C, int B,
+                                                                   int ZS, TabView tab, int b0,
+                                                                   int b1,
+                                                                   double *__restrict__ out,
+                                                                   int64_t ld) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int64_t J = blockIdx.x, I = blockIdx.y;
+  const int64_t R0 = I * AT, C0 = J * AT;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+  CROSS_LDS_POINTERS(lds, PM, B, KIND);
+  cross_stage_x<PM, true, true>(XJ, XI, C, C0, R, R0, tid);
+  cross_stage_z<KIND>(Zc, LZc, C, C0, B, ZS, tid);
+  cross_stage_tab<PM, KIND>(E, Zc, LZc, W, tab, B, tid);
+  __syncthreads();
+  cross_norms<PM, true, true>(XJ, XI, W, Nc, Nr, B, tid);
   __syncthreads();
   const int rl = 16 * w + lr;
   const int64_t r = R0 + rl;
   const bool rok = r < R.n;
   RowX<PM> xr;
-  xr.load(XI + rl * XP, lk);
+  xr.load(XI + rl * xj_pitch(PM), lk);
   double kf[4][4];
 #pragma unroll
   for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
     for (int v = 0; v < 4; ++v) kf[cb][v] = 0.0;
   for (int b = b0; b < b1; ++b) {
-    // slice 0 as z = 1, log|z| = 0 (Zc / LZc row -1 holds them): no per-pair
-    // slice test (kval_nb)
-    double zr = 1.0, lzr = 0.0;
+    double zr = 1.0, lzr = 0.0;  // issued ahead of GEMM1
     if (b > 0) {
       zr = rok ? R.Z[r * ZS + b - 1] : 0.0;
       if (KIND == 0) lzr = rok ? R.LZ[r * ZS + b - 1] : 0.0;
     }
-    d4 acc[4];
-    gemm1_mm<XP, 4>(XJ, xr, W + b * PM, lr, lk, acc, 0);
-    const double sr = Nr[b * 64 + rl];
-    const double *nc = Nc + b * 64;
-    const double *zcol = Zc + (b - 1) * 64, *lzcol = LZc + (b - 1) * 64;
-    const double lam = tab.lam[b];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int cl = 16 * cb + lk + 4 * v;
-        constexpr double R2MIN = KIND == 1 ? 1e-300 : 0.0;
-        const double r2 = fmax(fma(-2.0, acc[cb][v], sr + nc[cl]), R2MIN);
-        const double zc = zcol[cl];
-        const double lzc = KIND == 0 ? lzcol[cl] : 0.0;
-        kf[cb][v] += kval_nb<KIND>(r2, lam, zr, zc, lzr, lzc, E);
-        MM_PAIR_FENCE(cb, v);
-      }
+    cross_slice_pairs<PM, KIND>(kf, XJ, W, Nr, Nc, Zc, LZc, E, xr, tab, b, zr, lzr, rl, lr, lk);
   }
   if (!rok) return;
 #pragma unroll
@@ -900,7 +857,7 @@ __global__ __launch_bounds__(256, PM <= 32 ? 4 : 2) void k_cross_mm(PairSide R, 
 // the exit (the counter runs past nblk); the tiles are those of part 2, each
 // assembled exactly as by k_asm_mm (bit-identical).
 template <int PM, int KIND>
-__global__ __launch_bounds__(ASM_NT, (ACE_ASM_CB == 2 ? 4 : PM <= 24 ? 4 : PM <= 32 ? 3 : 2)) void k_asm_mm_q(
+__global__ __launch_bounds__(ASM_NT, PM <= 24 ? 4 : PM <= 32 ? 3 : 2) void k_asm_mm_q(
     PairSide S, int B, int ZS, TabView tab, double sig, double *__restrict__ out, int64_t ld,
     int *__restrict__ queue, int64_t nblk, int JB, int reserve) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -1254,14 +1211,14 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
           // log|0| = -inf makes the exponential NaN: a select (not a branch)
           // puts the reference's 0 there
           const double kz = (sgn_mm(zlo) * sgn_mm(zhi)) *
-                            exp_grad(((lam - r2) + (rlo ? lzr : lzc)) + (rlo ? lzc : lzr), L.E);
+                            exp_tb5(((lam - r2) + (rlo ? lzr : lzc)) + (rlo ? lzc : lzr), L.E);
           kb = sel_f64(zlo == 0.0 || zhi == 0.0, 0.0, kz);
         } else {
           const double tt = (ACE_DIAG_GRAD & 4) ? r2 : sqrt_gs(r2);
           // (an explicit fma -- what the compiler contracted 1 + sqrt3 t to
           // anyway -- so that the factor pass above forms the same bits)
           f = fma(SQRT3, tt, 1.0);
-          const double e = (ACE_DIAG_GRAD & 8) ? f * (lam - SQRT3 * tt) : f * exp_grad(lam - SQRT3 * tt, L.E);
+          const double e = (ACE_DIAG_GRAD & 8) ? f * (lam - SQRT3 * tt) : f * exp_tb5(lam - SQRT3 * tt, L.E);
           // z = 0 gives a zero product (of either sign: it only enters sums)
           kb = (e * zlo) * zhi;
         }
@@ -1439,6 +1396,39 @@ __host__ __device__ constexpr int grad_cb(int PM, int kind) {
   return (ACE_MM_GRAD_CB == 2 && (kind == 0 || PM <= 32)) ? 2 : 4;
 }
 
+// f(std::integral_constant<int, PM>) for the instantiated covariate buckets,
+// f(std::integral_constant<int, KIND>) for the kernel family (0 SE, else
+// Matern32)
+template <class F>
+static hipError_t with_pm(int PM, F &&f) {
+  switch (PM) {
+#define ACE_CASE(P) \
+  case P: return f(std::integral_constant<int, P>{});
+    ACE_CASE(4) ACE_CASE(8) ACE_CASE(12) ACE_CASE(16) ACE_CASE(20) ACE_CASE(24)
+    ACE_CASE(32) ACE_CASE(48) ACE_CASE(64)
+#undef ACE_CASE
+    default: return hipErrorInvalidValue;
+  }
+}
+template <class F>
+static hipError_t with_kind(int kind, F &&f) {
+  return kind == 0 ? f(std::integral_constant<int, 0>{}) : f(std::integral_constant<int, 1>{});
+}
+
+// One launch with `lds` bytes of dynamic LDS (above 64 KB a kernel has to be
+// allowed it first)
+template <class... P, class... A>
+static hipError_t launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds,
+                             hipStream_t st, A... args) {
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute((const void *)kernel,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+  return hipGetLastError();
+}
+
 template <int PM, int KIND, bool PS, bool DG>
 static hipError_t grad_mm_launch_ps(PairSide S, int B, int ZS, TabView tab, const double *A,
                                     int64_t ld, double sA, const double *alpha, double *gpart,
@@ -1447,15 +1437,8 @@ static hipError_t grad_mm_launch_ps(PairSide S, int B, int ZS, TabView tab, cons
   constexpr int CB = grad_cb(PM, KIND);
   constexpr int NT = 64 * 4 * (4 / CB);
   if (nblk == 0) return hipSuccess;
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute((const void *)k_grad_mm<PM, KIND, CB, PS, DG>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((k_grad_mm<PM, KIND, CB, PS, DG>), dim3((unsigned)nblk), dim3(NT), lds, st,
-                     S, B, ZS, tab, A, ld, sA, alpha, gpart, (int64_t)grad_part_cols(PM, B), tiles,
-                     G, t0);
-  return hipGetLastError();
+  return launch_lds(k_grad_mm<PM, KIND, CB, PS, DG>, dim3((unsigned)nblk), dim3(NT), lds, st, S, B,
+                    ZS, tab, A, ld, sA, alpha, gpart, grad_part_cols(PM, B), tiles, G, t0);
 }
 
 // Two launches: the diagonal tiles (with the r == c / r < c tests) and the
@@ -1497,20 +1480,6 @@ static hipError_t grad_mm_launch(PairSide S, int B, int ZS, TabView tab, const d
                                                   tiles, nslot, ndiag, G, lds);
 }
 
-template <int PM>
-static hipError_t grad_mm_pm(int kind, PairSide S, int B, int ZS, TabView tab, const double *A,
-                             int64_t ld, double sA, const double *alpha, double *gpart,
-                             hipStream_t st, const Tile *tiles, int64_t ntiles, int64_t ndiag,
-                             int G) {
-  const int64_t nt = (S.n + AT - 1) / AT;
-  const int64_t nslot = tiles ? ntiles : nt * (nt + 1) / 2;
-  if (nslot == 0) return hipSuccess;
-  return kind == 0 ? grad_mm_launch<PM, 0>(S, B, ZS, tab, A, ld, sA, alpha, gpart, st, tiles,
-                                           nslot, ndiag, G)
-                   : grad_mm_launch<PM, 1>(S, B, ZS, tab, A, ld, sA, alpha, gpart, st, tiles,
-                                           nslot, ndiag, G);
-}
-
 // Whether the per-tile staging of the MFMA kernels fits the 160 KB of LDS
 // a gfx950 workgroup can use (up to 80 KB two workgroups share a CU; above
 // it one, at large B and p).  Every supported shape (B <= 32, p <= 64)
@@ -1526,21 +1495,21 @@ hipError_t launch_grad_mm(int kind, int PM, PairSide S, int B, int ZS, TabView t
                           const double *A, int64_t ld, double sA, const double *alpha,
                           double *gpart, hipStream_t st, const Tile *tiles, int64_t ntiles, int G,
                           int64_t ndiag) {
-  switch (PM) {
-#define ACE_CASE(P) \
-  case P:           \
-    return grad_mm_pm<P>(kind, S, B, ZS, tab, A, ld, sA, alpha, gpart, st, tiles, ntiles, ndiag, G);
-    ACE_CASE(4) ACE_CASE(8) ACE_CASE(12) ACE_CASE(16) ACE_CASE(20) ACE_CASE(24)
-    ACE_CASE(32) ACE_CASE(48) ACE_CASE(64)
-#undef ACE_CASE
-    default: return hipErrorInvalidValue;
-  }
+  return with_pm(PM, [&](auto pm) {
+    const int64_t nt = (S.n + AT - 1) / AT;
+    const int64_t nslot = tiles ? ntiles : nt * (nt + 1) / 2;
+    if (nslot == 0) return hipSuccess;
+    return with_kind(kind, [&](auto kd) {
+      return grad_mm_launch<decltype(pm)::value, decltype(kd)::value>(
+          S, B, ZS, tab, A, ld, sA, alpha, gpart, st, tiles, nslot, ndiag, G);
+    });
+  });
 }
 
-template <int PM>
-static hipError_t asm_mm_pm(int kind, PairSide S, int64_t npad, int B, int ZS, TabView tab,
-                            double sig, double *out, int64_t ld, double *kcopy, hipStream_t st,
-                            const Tile *tiles, int64_t ntiles, int G, int part) {
+template <int PM, int KIND>
+static hipError_t asm_mm_launch(PairSide S, int64_t npad, int B, int ZS, TabView tab, double sig,
+                                double *out, int64_t ld, double *kcopy, hipStream_t st,
+                                const Tile *tiles, int64_t ntiles, int G, int part) {
   const int64_t nt = npad / AT, JB = asm_first_cols((int)nt);
   if (tiles) part = 0;
   const int64_t nblk = tiles ? ntiles
@@ -1549,48 +1518,29 @@ static hipError_t asm_mm_pm(int kind, PairSide S, int64_t npad, int B, int ZS, T
                        : part == 3 ? nt - JB
                                    : nt * (nt + 1) / 2;
   if (nblk == 0) return hipSuccess;
-  const size_t lds = (size_t)mm_layout(PM, B, kind == 0 ? 0 : 1, false).total * sizeof(double);
-  if (lds > 65536) {
-    const void *f = kind == 0 ? (const void *)k_asm_mm<PM, 0> : (const void *)k_asm_mm<PM, 1>;
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  if (kind == 0)
-    hipLaunchKernelGGL((k_asm_mm<PM, 0>), dim3((unsigned)nblk), dim3(ASM_NT), lds, st, S, B, ZS,
-                       tab, sig, out, ld, kcopy, tiles, G, part, (int)nt, (int)JB);
-  else
-    hipLaunchKernelGGL((k_asm_mm<PM, 1>), dim3((unsigned)nblk), dim3(ASM_NT), lds, st, S, B, ZS,
-                       tab, sig, out, ld, kcopy, tiles, G, part, (int)nt, (int)JB);
-  return hipGetLastError();
+  const size_t lds = (size_t)mm_layout(PM, B, KIND, false).total * sizeof(double);
+  return launch_lds(k_asm_mm<PM, KIND>, dim3((unsigned)nblk), dim3(ASM_NT), lds, st, S, B, ZS, tab,
+                    sig, out, ld, kcopy, tiles, G, part, nt, JB);
 }
 
-template <int PM>
-static hipError_t asm_mm_persist_pm(int kind, PairSide S, int64_t npad, int B, int ZS, TabView tab,
-                                    double sig, double *out, int64_t ld, hipStream_t st, int *queue,
-                                    int reserve, int slots, bool fill) {
+template <int PM, int KIND>
+static hipError_t asm_mm_persist_launch(PairSide S, int64_t npad, int B, int ZS, TabView tab,
+                                        double sig, double *out, int64_t ld, hipStream_t st,
+                                        int *queue, int reserve, int slots, bool fill) {
   const int64_t nt = npad / AT, JB = asm_first_cols((int)nt);
   const int64_t nblk = (nt - JB) * (nt - JB - 1) / 2;  // strictly lower tiles of part 2
   if (nt - JB <= 0) return hipSuccess;
-  const size_t lds = (size_t)mm_layout(PM, B, kind == 0 ? 0 : 1, false).total * sizeof(double);
-  if (lds > 65536) {
-    const void *f = kind == 0 ? (const void *)k_asm_mm_q<PM, 0> : (const void *)k_asm_mm_q<PM, 1>;
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  const size_t lds = (size_t)mm_layout(PM, B, KIND, false).total * sizeof(double);
   // part 2's diagonal tiles (the r == c / r < c path) as a plain grid first;
   // a filler launch (fill: `slots` more workgroups on another stream, none
   // reserved) only joins the queue of the running one
-  hipError_t e = fill ? hipSuccess
-                      : asm_mm_pm<PM>(kind, S, npad, B, ZS, tab, sig, out, ld, nullptr, st, nullptr, 0, 1, 3);
+  const hipError_t e = fill ? hipSuccess
+                            : asm_mm_launch<PM, KIND>(S, npad, B, ZS, tab, sig, out, ld, nullptr,
+                                                      st, nullptr, 0, 1, 3);
   if (e != hipSuccess || nblk == 0) return e;
   if (fill) reserve = 0;
-  if (kind == 0)
-    hipLaunchKernelGGL((k_asm_mm_q<PM, 0>), dim3((unsigned)slots), dim3(ASM_NT), lds, st, S, B, ZS,
-                       tab, sig, out, ld, queue, nblk, (int)JB, reserve);
-  else
-    hipLaunchKernelGGL((k_asm_mm_q<PM, 1>), dim3((unsigned)slots), dim3(ASM_NT), lds, st, S, B, ZS,
-                       tab, sig, out, ld, queue, nblk, (int)JB, reserve);
-  return hipGetLastError();
+  return launch_lds(k_asm_mm_q<PM, KIND>, dim3((unsigned)slots), dim3(ASM_NT), lds, st, S, B, ZS,
+                    tab, sig, out, ld, queue, nblk, JB, reserve);
 }
 
 // Workgroup slots of k_asm_mm_q (occupancy x CUs), 0 if unknown; cached per
@@ -1631,14 +1581,12 @@ int assembly_persist_per_cu(int kind, int PM, int B) {
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
     return 0;
-  switch (PM) {
-#define ACE_CASE(P) \
-  case P: return asm_mm_slots<P>(kind, B) / ncu;
-    ACE_CASE(4) ACE_CASE(8) ACE_CASE(12) ACE_CASE(16) ACE_CASE(20) ACE_CASE(24)
-    ACE_CASE(32) ACE_CASE(48) ACE_CASE(64)
-#undef ACE_CASE
-    default: return 0;
-  }
+  int per = 0;  // stays 0 for a PM without kernels
+  (void)with_pm(PM, [&](auto pm) {
+    per = asm_mm_slots<decltype(pm)::value>(kind, B) / ncu;
+    return hipSuccess;
+  });
+  return per;
 }
 
 #ifdef ACE_DIAG_WGTIME
@@ -1652,19 +1600,15 @@ namespace ace {
 hipError_t launch_assembly_persist(int kind, int PM, PairSide S, int64_t npad, int B, int ZS,
                                    TabView tab, double sig, double *out, int64_t ld,
                                    hipStream_t st, int *queue, int reserve, int fill) {
-  switch (PM) {
-#define ACE_CASE(P)                                                                          \
-  case P: {                                                                                  \
-    const int slots = fill > 0 ? fill : asm_mm_slots<P>(kind, B);                            \
-    if (slots <= 0) return hipErrorInvalidValue;                                             \
-    return asm_mm_persist_pm<P>(kind, S, npad, B, ZS, tab, sig, out, ld, st, queue, reserve, \
-                                slots, fill > 0);                                            \
-  }
-    ACE_CASE(4) ACE_CASE(8) ACE_CASE(12) ACE_CASE(16) ACE_CASE(20) ACE_CASE(24)
-    ACE_CASE(32) ACE_CASE(48) ACE_CASE(64)
-#undef ACE_CASE
-    default: return hipErrorInvalidValue;
-  }
+  return with_pm(PM, [&](auto pm) {
+    constexpr int P = decltype(pm)::value;
+    const int slots = fill > 0 ? fill : asm_mm_slots<P>(kind, B);
+    if (slots <= 0) return hipErrorInvalidValue;
+    return with_kind(kind, [&](auto kd) {
+      return asm_mm_persist_launch<P, decltype(kd)::value>(S, npad, B, ZS, tab, sig, out, ld, st,
+                                                           queue, reserve, slots, fill > 0);
+    });
+  });
 }
 
 // k_cross_mm's LDS: the assembly's layout plus the row side's points
@@ -1674,35 +1618,19 @@ static size_t cross_mm_lds(int PM, int B, int kind) {
 }
 bool cross_mm_lds_ok(int PM, int B, int kind) { return cross_mm_lds(PM, B, kind) <= 160 * 1024; }
 
-template <int PM>
-static hipError_t cross_mm_pm(int kind, PairSide R, PairSide C, int B, int ZS, TabView tab, int b0,
-                              int b1, double *out, int64_t ld, hipStream_t st) {
-  if (R.n <= 0 || C.n <= 0 || b1 <= b0) return hipSuccess;
-  const size_t lds = cross_mm_lds(PM, B, kind);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  const void *f = kind == 0 ? (const void *)k_cross_mm<PM, 0> : (const void *)k_cross_mm<PM, 1>;
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const dim3 grid((unsigned)((C.n + AT - 1) / AT), (unsigned)((R.n + AT - 1) / AT));
-  if (kind == 0)
-    hipLaunchKernelGGL((k_cross_mm<PM, 0>), grid, dim3(256), lds, st, R, C, B, ZS, tab, b0, b1, out, ld);
-  else
-    hipLaunchKernelGGL((k_cross_mm<PM, 1>), grid, dim3(256), lds, st, R, C, B, ZS, tab, b0, b1, out, ld);
-  return hipGetLastError();
-}
-
 hipError_t launch_cross_mm(int kind, int PM, PairSide R, PairSide C, int B, int ZS, TabView tab,
                            int b0, int b1, double *out, int64_t ld, hipStream_t st) {
-  switch (PM) {
-#define ACE_CASE(P) \
-  case P: return cross_mm_pm<P>(kind, R, C, B, ZS, tab, b0, b1, out, ld, st);
-    ACE_CASE(4) ACE_CASE(8) ACE_CASE(12) ACE_CASE(16) ACE_CASE(20) ACE_CASE(24)
-    ACE_CASE(32) ACE_CASE(48) ACE_CASE(64)
-#undef ACE_CASE
-    default: return hipErrorInvalidValue;
-  }
+  return with_pm(PM, [&](auto pm) {
+    constexpr int P = decltype(pm)::value;
+    if (R.n <= 0 || C.n <= 0 || b1 <= b0) return hipSuccess;
+    const size_t lds = cross_mm_lds(P, B, kind);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((C.n + AT - 1) / AT), (unsigned)((R.n + AT - 1) / AT));
+    return with_kind(kind, [&](auto kd) {
+      return launch_lds(k_cross_mm<P, decltype(kd)::value>, grid, dim3(256), lds, st, R, C, B, ZS,
+                        tab, b0, b1, out, ld);
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1720,73 +1648,32 @@ template <int PM, int KIND>
 __global__ __launch_bounds__(256, PM <= 32 ? 4 : 2) void k_cross_slices_mm(
     PairSide R, PairSide C, int B, int ZS, TabView tab, double *__restrict__ out, int64_t ld) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  constexpr int XP = xj_pitch(PM);
   const int64_t J = blockIdx.x, I = blockIdx.y;
   const int64_t R0 = I * AT, C0 = J * AT;
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
   const int lr = lane & 15, lk = lane >> 4;
-  const MmLayout o = mm_layout(PM, B, KIND, false);
-  double *const E = lds + o.etab, *const XJ = lds + o.xj, *const Zc = lds + o.z + 64,
-               *const LZc = lds + o.lz + 64, *const Nc = lds + o.nc, *const Nr = lds + o.nr,
-               *const W = lds + o.w, *const XI = lds + o.total;
-  for (int e = tid; e < 64 * PM; e += 256) {
-    const int c = e / PM, i = e - c * PM;
-    XJ[c * XP + i] = (C0 + c < C.n) ? C.X[(C0 + c) * PM + i] : 0.0;
-    XI[c * XP + i] = (R0 + c < R.n) ? R.X[(R0 + c) * PM + i] : 0.0;
-  }
-  for (int e = tid; e < (B - 1) * 64; e += 256) {
-    const int bb = e >> 6, c = e & 63;
-    const bool ok = C0 + c < C.n;
-    Zc[e] = ok ? C.Z[(C0 + c) * ZS + bb] : 0.0;
-    if (KIND == 0) LZc[e] = ok ? C.LZ[(C0 + c) * ZS + bb] : 0.0;
-  }
-  if (tid < 64) {  // slice 0: z = 1, log|z| = 0
-    Zc[tid - 64] = 1.0;
-    if (KIND == 0) LZc[tid - 64] = 0.0;
-    if (ACE_ASM_EXP == 2) E[tid] = kExp2Tab64[tid];
-    else if (tid < 32) E[tid] = kExp2Tab[tid];
-  }
-  for (int e = tid; e < B * PM; e += 256) W[e] = tab.wk[e];
+  CROSS_LDS_POINTERS(lds, PM, B, KIND);
+  cross_stage_x<PM, true, true>(XJ, XI, C, C0, R, R0, tid);
+  cross_stage_z<KIND>(Zc, LZc, C, C0, B, ZS, tid);
+  cross_stage_tab<PM, KIND>(E, Zc, LZc, W, tab, B, tid);
   __syncthreads();
-  for (int e = tid; e < 2 * B * 64; e += 256) {
-    const int side = e / (B * 64), rem = e - side * B * 64;
-    const int sl = rem >> 6, pt = rem & 63;
-    const double *wv = W + sl * PM;
-    const double *x = (side == 0 ? XJ : XI) + pt * XP;
-    double s = 0.0;
-#pragma unroll 4
-    for (int i = 0; i < PM; ++i) s = fma(x[i] * x[i], wv[i], s);
-    (side == 0 ? Nc : Nr)[rem] = s;
-  }
+  cross_norms<PM, true, true>(XJ, XI, W, Nc, Nr, B, tid);
   __syncthreads();
   const int rl = 16 * w + lr;
   const int64_t r = R0 + rl;
   const bool rok = r < R.n;
   RowX<PM> xr;
-  xr.load(XI + rl * XP, lk);
+  xr.load(XI + rl * xj_pitch(PM), lk);
   for (int b = 0; b < B; ++b) {
-    d4 acc[4];
-    gemm1_mm<XP, 4>(XJ, xr, W + b * PM, lr, lk, acc, 0);
-    const double sr = Nr[b * 64 + rl];
-    const double *nc = Nc + b * 64;
-    const double *zcol = Zc + (b - 1) * 64, *lzcol = LZc + (b - 1) * 64;
-    const double lam = tab.lam[b];
-    // every pair of the slice in one basic block (see kval_nb); the stores
-    // follow the loop
+    // 0 + k per slice: the last product fused into the addition exactly as
+    // by k_cross_mm's sum; the stores follow the slice's pairs
     double kf[4][4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int cl = 16 * cb + lk + 4 * v;
-        constexpr double R2MIN = KIND == 1 ? 1e-300 : 0.0;
-        const double r2 = fmax(fma(-2.0, acc[cb][v], sr + nc[cl]), R2MIN);
-        const double zc = zcol[cl];
-        const double lzc = KIND == 0 ? lzcol[cl] : 0.0;
-        kf[cb][v] = 0.0 + kval_nb<KIND>(r2, lam, 1.0, zc, 0.0, lzc, E);
-        MM_PAIR_FENCE(cb, v);
-      }
+      for (int v = 0; v < 4; ++v) kf[cb][v] = 0.0;
+    cross_slice_pairs<PM, KIND>(kf, XJ, W, Nr, Nc, Zc, LZc, E, xr, tab, b, 1.0, 0.0, rl, lr, lk);
     // the values are pinned here: used only under the stores' conditions,
     // each pair's math would otherwise sink into its store's block (a block
     // per pair again: 128 VGPRs with 73 - 126 spills at PM <= 32)
@@ -1807,36 +1694,20 @@ __global__ __launch_bounds__(256, PM <= 32 ? 4 : 2) void k_cross_slices_mm(
   }
 }
 
-template <int PM>
-static hipError_t cross_slices_mm_pm(int kind, PairSide R, PairSide C, int B, int ZS, TabView tab,
-                                     double *out, int64_t ld, hipStream_t st) {
-  if (R.n <= 0 || C.n <= 0) return hipSuccess;
-  const size_t lds = cross_mm_lds(PM, B, kind);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  const void *f = kind == 0 ? (const void *)k_cross_slices_mm<PM, 0>
-                            : (const void *)k_cross_slices_mm<PM, 1>;
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const dim3 grid((unsigned)((C.n + AT - 1) / AT), (unsigned)((R.n + AT - 1) / AT));
-  if (kind == 0)
-    hipLaunchKernelGGL((k_cross_slices_mm<PM, 0>), grid, dim3(256), lds, st, R, C, B, ZS, tab, out, ld);
-  else
-    hipLaunchKernelGGL((k_cross_slices_mm<PM, 1>), grid, dim3(256), lds, st, R, C, B, ZS, tab, out, ld);
-  return hipGetLastError();
-}
 
 hipError_t launch_cross_slices_mm(int kind, int PM, PairSide R, PairSide C, int B, int ZS,
                                   TabView tab, double *out, int64_t ld, hipStream_t st) {
-  switch (PM) {
-#define ACE_CASE(P) \
-  case P: return cross_slices_mm_pm<P>(kind, R, C, B, ZS, tab, out, ld, st);
-    ACE_CASE(4) ACE_CASE(8) ACE_CASE(12) ACE_CASE(16) ACE_CASE(20) ACE_CASE(24)
-    ACE_CASE(32) ACE_CASE(48) ACE_CASE(64)
-#undef ACE_CASE
-    default: return hipErrorInvalidValue;
-  }
+  return with_pm(PM, [&](auto pm) {
+    constexpr int P = decltype(pm)::value;
+    if (R.n <= 0 || C.n <= 0) return hipSuccess;
+    const size_t lds = cross_mm_lds(P, B, kind);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((C.n + AT - 1) / AT), (unsigned)((R.n + AT - 1) / AT));
+    return with_kind(kind, [&](auto kd) {
+      return launch_lds(k_cross_slices_mm<P, decltype(kd)::value>, grid, dim3(256), lds, st, R, C,
+                        B, ZS, tab, out, ld);
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1861,7 +1732,6 @@ __global__ __launch_bounds__(256, 2) void k_group_mm(PairSide S, int B, int ZS, 
                                                     int tpw, double *__restrict__ part,
                                                     int64_t ldp) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  constexpr int XP = xj_pitch(PM);
   const int64_t I = blockIdx.y, js = blockIdx.x;
   const int64_t nt = (S.n + AT - 1) / AT;
   const int64_t J0 = js * tpw, J1 = (J0 + tpw < nt) ? J0 + tpw : nt;
@@ -1870,69 +1740,29 @@ __global__ __launch_bounds__(256, 2) void k_group_mm(PairSide S, int B, int ZS, 
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
   const int lr = lane & 15, lk = lane >> 4;
-  const MmLayout o = mm_layout(PM, B, KIND, false);
-  double *const E = lds + o.etab, *const XJ = lds + o.xj, *const Zc = lds + o.z + 64,
-               *const LZc = lds + o.lz + 64, *const Nc = lds + o.nc, *const Nr = lds + o.nr,
-               *const W = lds + o.w, *const XI = lds + o.total;
-  int *const Lab = (int *)(XI + 64 * XP);
+  CROSS_LDS_POINTERS(lds, PM, B, KIND);
+  int *const Lab = (int *)(XI + 64 * xj_pitch(PM));
   // the strip's row side, the weights and the tables: staged once
-  for (int e = tid; e < 64 * PM; e += 256) {
-    const int c = e / PM, i = e - c * PM;
-    XI[c * XP + i] = (R0 + c < S.n) ? S.X[(R0 + c) * PM + i] : 0.0;
-  }
-  if (tid < 64) {  // slice 0: z = 1, log|z| = 0
-    Zc[tid - 64] = 1.0;
-    if (KIND == 0) LZc[tid - 64] = 0.0;
-    if (ACE_ASM_EXP == 2) E[tid] = kExp2Tab64[tid];
-    else if (tid < 32) E[tid] = kExp2Tab[tid];
-  }
-  for (int e = tid; e < B * PM; e += 256) W[e] = tab.wk[e];
+  cross_stage_x<PM, false, true>(XJ, XI, S, 0, S, R0, tid);
+  cross_stage_tab<PM, KIND>(E, Zc, LZc, W, tab, B, tid);
   __syncthreads();
-  for (int e = tid; e < B * 64; e += 256) {
-    const int sl = e >> 6, pt = e & 63;
-    const double *wv = W + sl * PM;
-    double s = 0.0;
-#pragma unroll 4
-    for (int i = 0; i < PM; ++i) {
-      const double x = XI[pt * XP + i];
-      s = fma(x * x, wv[i], s);
-    }
-    Nr[e] = s;
-  }
+  cross_norms<PM, false, true>(XJ, XI, W, Nc, Nr, B, tid);
   const int rl = 16 * w + lr;
   const int64_t r = R0 + rl;
   const bool rok = r < S.n;
   RowX<PM> xr;
-  xr.load(XI + rl * XP, lk);
+  xr.load(XI + rl * xj_pitch(PM), lk);
   d4 racc[4];
 #pragma unroll
   for (int hb = 0; hb < 4; ++hb) racc[hb] = d4{0.0, 0.0, 0.0, 0.0};
   for (int64_t J = J0; J < J1; ++J) {
     const int64_t C0 = J * AT;
     if (J > J0) __syncthreads();  // the previous tile's readers are done
-    for (int e = tid; e < 64 * PM; e += 256) {
-      const int c = e / PM, i = e - c * PM;
-      XJ[c * XP + i] = (C0 + c < S.n) ? S.X[(C0 + c) * PM + i] : 0.0;
-    }
-    for (int e = tid; e < (B - 1) * 64; e += 256) {
-      const int bb = e >> 6, c = e & 63;
-      const bool ok = C0 + c < S.n;
-      Zc[e] = ok ? S.Z[(C0 + c) * ZS + bb] : 0.0;
-      if (KIND == 0) LZc[e] = ok ? S.LZ[(C0 + c) * ZS + bb] : 0.0;
-    }
+    cross_stage_x<PM, true, false>(XJ, XI, S, C0, S, 0, tid);
+    cross_stage_z<KIND>(Zc, LZc, S, C0, B, ZS, tid);
     if (tid < 64) Lab[tid] = (C0 + tid < S.n) ? label[C0 + tid] : -1;
     __syncthreads();
-    for (int e = tid; e < B * 64; e += 256) {
-      const int sl = e >> 6, pt = e & 63;
-      const double *wv = W + sl * PM;
-      double s = 0.0;
-#pragma unroll 4
-      for (int i = 0; i < PM; ++i) {
-        const double x = XJ[pt * XP + i];
-        s = fma(x * x, wv[i], s);
-      }
-      Nc[e] = s;
-    }
+    cross_norms<PM, true, false>(XJ, XI, W, Nc, Nr, B, tid);
     __syncthreads();
     double kf[4][4];
 #pragma unroll
@@ -1940,29 +1770,12 @@ __global__ __launch_bounds__(256, 2) void k_group_mm(PairSide S, int B, int ZS, 
 #pragma unroll
       for (int v = 0; v < 4; ++v) kf[cb][v] = 0.0;
     for (int b = b0; b < b1; ++b) {
-      double zr = 1.0, lzr = 0.0;
+      double zr = 1.0, lzr = 0.0;  // issued ahead of GEMM1
       if (b > 0) {
         zr = rok ? S.Z[r * ZS + b - 1] : 0.0;
         if (KIND == 0) lzr = rok ? S.LZ[r * ZS + b - 1] : 0.0;
       }
-      d4 acc[4];
-      gemm1_mm<XP, 4>(XJ, xr, W + b * PM, lr, lk, acc, 0);
-      const double sr = Nr[b * 64 + rl];
-      const double *nc = Nc + b * 64;
-      const double *zcol = Zc + (b - 1) * 64, *lzcol = LZc + (b - 1) * 64;
-      const double lam = tab.lam[b];
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int cl = 16 * cb + lk + 4 * v;
-          constexpr double R2MIN = KIND == 1 ? 1e-300 : 0.0;
-          const double r2 = fmax(fma(-2.0, acc[cb][v], sr + nc[cl]), R2MIN);
-          const double zc = zcol[cl];
-          const double lzc = KIND == 0 ? lzcol[cl] : 0.0;
-          kf[cb][v] += kval_nb<KIND>(r2, lam, zr, zc, lzr, lzc, E);
-          MM_PAIR_FENCE(cb, v);
-        }
+      cross_slice_pairs<PM, KIND>(kf, XJ, W, Nr, Nc, Zc, LZc, E, xr, tab, b, zr, lzr, rl, lr, lk);
     }
     // GEMM2: racc[hb] += K[rows][16 cb + 4 v + lk] E[16 cb + 4 v + lk][16 hb + lr]
     int lb[4][4];
@@ -1995,6 +1808,7 @@ __global__ __launch_bounds__(256, 2) void k_group_mm(PairSide S, int B, int ZS, 
     }
   }
 }
+
 
 // The same reduction on the VALU alone (the staging of k_group_mm does not
 // fit in LDS, or ACE_PAIRS=valu): one thread per row of the strip, r2 as the
@@ -2075,25 +1889,6 @@ int group_sums_parts(int64_t n) {
   return (int)((nt + tpw - 1) / tpw);
 }
 
-template <int PM>
-static hipError_t group_mm_pm(int kind, PairSide S, int B, int ZS, TabView tab, int b0, int b1,
-                              const int *label, int G, int tpw, dim3 grid, double *part,
-                              hipStream_t st) {
-  const size_t lds = group_mm_lds(PM, B, kind);
-  const void *f = kind == 0 ? (const void *)k_group_mm<PM, 0> : (const void *)k_group_mm<PM, 1>;
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  if (kind == 0)
-    hipLaunchKernelGGL((k_group_mm<PM, 0>), grid, dim3(256), lds, st, S, B, ZS, tab, b0, b1, label,
-                       G, tpw, part, S.n);
-  else
-    hipLaunchKernelGGL((k_group_mm<PM, 1>), grid, dim3(256), lds, st, S, B, ZS, tab, b0, b1, label,
-                       G, tpw, part, S.n);
-  return hipGetLastError();
-}
-
 hipError_t launch_group_sums(int kind, int PM, PairSide S, int B, int ZS, TabView tab, int b0,
                              int b1, const int *label, int G, double *part, double *R,
                              hipStream_t st) {
@@ -2102,26 +1897,17 @@ hipError_t launch_group_sums(int kind, int PM, PairSide S, int B, int ZS, TabVie
   const int tpw = group_tpw(S.n);
   const int nparts = group_sums_parts(S.n);
   const dim3 grid((unsigned)nparts, (unsigned)nt);
-  hipError_t e = hipSuccess;
-  if (pairs_use_mm(PM, false) && group_mm_lds(PM, B, kind) <= 160 * 1024) {
-    switch (PM) {
-#define ACE_CASE(P) \
-  case P: e = group_mm_pm<P>(kind, S, B, ZS, tab, b0, b1, label, G, tpw, grid, part, st); break;
-      ACE_CASE(4) ACE_CASE(8) ACE_CASE(12) ACE_CASE(16) ACE_CASE(20) ACE_CASE(24)
-      ACE_CASE(32) ACE_CASE(48) ACE_CASE(64)
-#undef ACE_CASE
-      default: return hipErrorInvalidValue;
-    }
-  } else {
-    const size_t lds = (size_t)(64 + 64 * G) * sizeof(double);
-    if (kind == 0)
-      hipLaunchKernelGGL((k_group_valu<0>), grid, dim3(64), lds, st, S, PM, B, ZS, tab, b0, b1,
-                         label, G, tpw, part, S.n);
-    else
-      hipLaunchKernelGGL((k_group_valu<1>), grid, dim3(64), lds, st, S, PM, B, ZS, tab, b0, b1,
-                         label, G, tpw, part, S.n);
-    e = hipGetLastError();
-  }
+  const hipError_t e = with_kind(kind, [&](auto kd) {
+    constexpr int KIND = decltype(kd)::value;
+    if (pairs_use_mm(PM, false) && group_mm_lds(PM, B, kind) <= 160 * 1024)
+      return with_pm(PM, [&](auto pm) {
+        return launch_lds(k_group_mm<decltype(pm)::value, KIND>, grid, dim3(256),
+                          group_mm_lds(PM, B, kind), st, S, B, ZS, tab, b0, b1, label, G, tpw,
+                          part, S.n);
+      });
+    return launch_lds(k_group_valu<KIND>, grid, dim3(64), (size_t)(64 + 64 * G) * sizeof(double),
+                      st, S, PM, B, ZS, tab, b0, b1, label, G, tpw, part, S.n);
+  });
   if (e != hipSuccess) return e;
   const int64_t count = S.n * G;
   hipLaunchKernelGGL(k_sum_parts, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, part,
@@ -2132,15 +1918,12 @@ hipError_t launch_group_sums(int kind, int PM, PairSide S, int B, int ZS, TabVie
 hipError_t launch_assembly_mm(int kind, int PM, PairSide S, int64_t npad, int B, int ZS,
                               TabView tab, double sig, double *out, int64_t ld, double *kcopy,
                               hipStream_t st, const Tile *tiles, int64_t ntiles, int G, int part) {
-  switch (PM) {
-#define ACE_CASE(P) \
-  case P:           \
-    return asm_mm_pm<P>(kind, S, npad, B, ZS, tab, sig, out, ld, kcopy, st, tiles, ntiles, G, part);
-    ACE_CASE(4) ACE_CASE(8) ACE_CASE(12) ACE_CASE(16) ACE_CASE(20) ACE_CASE(24)
-    ACE_CASE(32) ACE_CASE(48) ACE_CASE(64)
-#undef ACE_CASE
-    default: return hipErrorInvalidValue;
-  }
+  return with_pm(PM, [&](auto pm) {
+    return with_kind(kind, [&](auto kd) {
+      return asm_mm_launch<decltype(pm)::value, decltype(kd)::value>(
+          S, npad, B, ZS, tab, sig, out, ld, kcopy, st, tiles, ntiles, G, part);
+    });
+  });
 }
 
 }  // namespace ace
