@@ -10,9 +10,9 @@ from .native import (  # noqa: F401
     normalize_test, normalize_train, pred_cpp, pred_marginal_cpp, robust_levels, stats_cpp,
     zero_pattern_order)
 from .model import (  # noqa: F401
-    DeviceModel, KernelClass_Matern32_R6, KernelClass_SE_R6, comm_unique_id, optAdam, optNadam,
-    optNesterov, set_optimizer)
+    BatchModel, DeviceModel, KernelClass_Matern32_R6, KernelClass_SE_R6, comm_unique_id, optAdam,
+    optNadam, optNesterov, set_optimizer)
 from .r6 import R6KernelMatern32, R6KernelSE  # noqa: F401
 from .train import (  # noqa: F401
-    AceFit, ace_train, coef_posterior, linear_spline, ns_spline, predict_ace, response_surface,
-    robust_treatment, set_basis, set_initial_parameters, square_spline)
+    AceFit, ace_train, ace_train_batch, coef_posterior, linear_spline, ns_spline, predict_ace,
+    response_surface, robust_treatment, set_basis, set_initial_parameters, square_spline)

@@ -129,6 +129,16 @@ SIGNATURES = {
     "ace_model_create_sharded_host": (ctypes.c_int, [_vp, ctypes.c_int, _I64, ctypes.c_int,
                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                      ctypes.c_void_p, ctypes.POINTER(_vp)]),
+    "ace_batch_create": (ctypes.c_int, [_vp, ctypes.c_int, _I64, _I64, ctypes.c_int, ctypes.c_int,
+                                        ctypes.POINTER(_vp)]),
+    "ace_batch_destroy": (None, [_vp]),
+    "ace_batch_set_data": (ctypes.c_int, [_vp, _I64, _I64, _D, _D, _D, ctypes.c_double]),
+    "ace_batch_para_update": (ctypes.c_int, [_vp, ctypes.c_int, _D, _D, _D, _D]),
+    "ace_batch_train": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                       ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                       ctypes.c_double, ctypes.c_int, ctypes.c_double, _D, _D,
+                                       _I32, _I32, _I32]),
+    "ace_batch_get_inverse": (ctypes.c_int, [_vp, _I64, _D]),
 }
 
 # ace_comm_ops (include/ace_hip.h): host-callback collectives

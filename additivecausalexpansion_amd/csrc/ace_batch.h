@@ -1,0 +1,58 @@
+// ace_batch.h -- shared between the batched kernels (ace_batch.hip) and their
+// host side (ace_batch.cpp): many small models, one workgroup per model.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ace {
+
+constexpr int BATCH_NMAX = 512;  // rows of the largest model one workgroup takes
+constexpr int BT = 16;           // pivot block = MFMA fragment width
+
+// Feature-count buckets of k_batch_eval (its own, coarser than pm_bucket's).
+int batch_pm_bucket(int p);
+// rows (= leading dimension) of a model's scratch matrix: n padded to BT,
+// plus one BT block whose first two rows carry the right-hand sides y and 1
+__host__ __device__ constexpr int batch_rows(int n) { return (n + BT - 1) / BT * BT + BT; }
+// LDS pitch of a pivot panel (16 mod 32 doubles: the two 16-lane groups of a
+// half wave read different banks)
+__host__ __device__ constexpr int batch_pitch(int nmax) {
+  return batch_rows(nmax) % 32 == 16 ? batch_rows(nmax) : batch_rows(nmax) + 16;
+}
+// dynamic LDS of k_batch_eval in bytes
+size_t batch_lds_bytes(int nmax, int B, int PM);
+
+// Per model j: n[j] rows; y, X (row-major n x PM), Z / LZ (row-major n x ZS)
+// at stride nmax rows; scratch matrix A + j ld ld (column-major, lower
+// triangle used).  theta of model j at theta + j ldt.  out + j ldo: grad (P),
+// stats (2), mu_solution, flag.  ctl (null: every model runs) holds {last
+// iteration done, stop} per model; skip = 1 leaves out models with stop != 0,
+// skip = 2 those with stop == 2.
+struct BatchView {
+  int M, nmax, p, B, PM, ZS, P;
+  int64_t ld;
+  const int *n;
+  const double *y, *X, *Z, *LZ, *std_y;
+  double *A;
+  const double *theta;
+  int64_t ldt;
+  double *out;
+  int64_t ldo;
+  const int *ctl;
+  int skip, use_mu;
+};
+hipError_t launch_batch_eval(int kind, const BatchView &v, hipStream_t st);
+
+struct BatchStepCfg {
+  int optimizer;
+  double lr, momentum, beta1, beta2;
+  int clip;
+  double clip_at, tol;
+  int P, M;
+};
+// k_train_step's logic per model: st + j 3 P = [theta | m1 | m2], hist + j ldh
+// the model's stats matrix, ctl as above, out as k_batch_eval left it.
+hipError_t launch_batch_step(const BatchStepCfg &c, int it, const double *out, int64_t ldo,
+                             double *st, double *hist, int64_t ldh, int *ctl, hipStream_t stream);
+
+}  // namespace ace

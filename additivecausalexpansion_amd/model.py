@@ -276,6 +276,82 @@ class DeviceModel:
             pass
 
 
+class BatchModel:
+    """ace_batch handle: M independent models of at most nmax <= 512 rows, one
+    kernel kind, p and B; one workgroup per model (single GPU)."""
+
+    def __init__(self, kind, M, nmax, p, B, ctx=None):
+        self.ctx = ctx or default_context()
+        self.kind, self.M, self.nmax, self.p, self.B = kind, int(M), int(nmax), p, B
+        self.P = 2 + B * (p + 1)
+        self.n = [0] * self.M
+        h = ctypes.c_void_p()
+        check(lib().ace_batch_create(self.ctx.handle, KIND[kind], self.M, self.nmax, p, B,
+                                     ctypes.byref(h)), self.ctx.handle)
+        self.handle = h
+
+    def set_data(self, j, y, X, Z, std_y):
+        yv = np.ascontiguousarray(np.ravel(y), dtype=np.float64)
+        n = yv.size
+        Xf = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(n, -1))
+        Zf = np.asfortranarray(np.asarray(Z, dtype=np.float64).reshape(n, -1))
+        check(lib().ace_batch_set_data(self.handle, int(j), n, ptr(yv), ptr(Xf), ptr(Zf),
+                                       float(std_y)), self.ctx.handle)
+        self.n[int(j)] = n
+
+    def para_update(self, it, theta):
+        """theta (float64, P x M column-major) is mutated at it == 1 (mu
+        overwrite); returns grad (P x M), stats (2 x M), mu_post (M)."""
+        assert theta.shape == (self.P, self.M) and theta.flags.f_contiguous
+        g = np.empty((self.P, self.M), order="F")
+        st = np.empty((2, self.M), order="F")
+        mu = np.empty(self.M)
+        check(lib().ace_batch_para_update(self.handle, int(it), ptr(theta), ptr(g), ptr(st),
+                                          ptr(mu)), self.ctx.handle)
+        return g, st, mu
+
+    def train(self, theta, optimizer="Nadam", learning_rate=0.01, momentum=0.0, beta1=0.9,
+              beta2=0.999, norm_clip=True, clip_at=1.0, maxiter=1000, tol=1e-4):
+        """ace_batch_train: every model's ace.train loop, in lock step.  theta
+        (float64, P x M column-major) is updated in place; returns (stats
+        2 x (maxiter + 2) x M, iterations M, converged M, status M -- 0 or
+        ACE_ERR_NONFINITE = 5 per model)."""
+        from ._lib import OPTIMIZER
+        assert theta.shape == (self.P, self.M) and theta.flags.f_contiguous
+        if optimizer == "GD":
+            momentum = 0.0
+        stats = np.zeros((2, maxiter + 2, self.M), order="F")
+        it = np.zeros(self.M, dtype=np.int32)
+        conv = np.zeros(self.M, dtype=np.int32)
+        status = np.zeros(self.M, dtype=np.int32)
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        check(lib().ace_batch_train(self.handle, OPTIMIZER[optimizer], float(learning_rate),
+                                    float(momentum), float(beta1), float(beta2),
+                                    1 if norm_clip else 0, float(clip_at), int(maxiter),
+                                    float(tol), ptr(theta),
+                                    stats.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                    it.ctypes.data_as(i32), conv.ctypes.data_as(i32),
+                                    status.ctypes.data_as(i32)), self.ctx.handle)
+        return stats, it, conv.astype(bool), status
+
+    def inverse(self, j):
+        n = self.n[int(j)]
+        out = np.empty((n, n), order="F")
+        check(lib().ace_batch_get_inverse(self.handle, int(j), ptr(out)), self.ctx.handle)
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().ace_batch_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def comm_unique_id():
     """ace_comm_unique_id: the RCCL bootstrap id (rank 0 calls it and sends
     the bytes to every rank out of band)."""

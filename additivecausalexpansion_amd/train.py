@@ -128,15 +128,9 @@ class AceFit(dict):
     """The S3 "ace" list (R/main_ace.R:242-253)."""
 
 
-def ace_train(y, X, Z, pi=None, kernel="SE", basis="linear", n_knots=1, optimizer="Nadam",
-              maxiter=1000, tol=1e-4, learning_rate=0.01, beta1=0.9, beta2=0.999, momentum=0.0,
-              norm_clip=None, clip_at=1.0, init_sigma=None, init_length_scale=20.0,
-              plot_stats=False, verbose=True, ctx=None, native_loop=False):
-    """R/main_ace.R:132-254 (ace.train).  native_loop=True runs the optimisation
-    loop inside the library (ace_model_train: no per-iteration round trip
-    through Python; same arithmetic, so the same trajectory)."""
-    if norm_clip is None:
-        norm_clip = optimizer in ("Adam", "Nadam")  # R/main_ace.R:143 (Q5)
+def _prepare(y, X, Z, pi, basis, n_knots, init_sigma, init_length_scale, verbose):
+    """ace.train's host preprocessing (R/main_ace.R:146-211): normalisation,
+    the basis and the initial parameters of one dataset."""
     yv = np.array(np.ravel(y), dtype=np.float64)
     n = yv.shape[0]
     Xi = np.array(X, dtype=np.float64, order="F", copy=True)
@@ -170,6 +164,20 @@ def ace_train(y, X, Z, pi=None, kernel="SE", basis="linear", n_knots=1, optimize
     myBasis.trainbasis(Zi, n_knots, verbose)
     theta0 = set_initial_parameters(px, myBasis.dim(), n, yv, Xi, Zi, init_sigma,
                                     init_length_scale, verbose)
+    return yv, Xi, Zi, px, moments, isbinary, myBasis, theta0
+
+
+def ace_train(y, X, Z, pi=None, kernel="SE", basis="linear", n_knots=1, optimizer="Nadam",
+              maxiter=1000, tol=1e-4, learning_rate=0.01, beta1=0.9, beta2=0.999, momentum=0.0,
+              norm_clip=None, clip_at=1.0, init_sigma=None, init_length_scale=20.0,
+              plot_stats=False, verbose=True, ctx=None, native_loop=False):
+    """R/main_ace.R:132-254 (ace.train).  native_loop=True runs the optimisation
+    loop inside the library (ace_model_train: no per-iteration round trip
+    through Python; same arithmetic, so the same trajectory)."""
+    if norm_clip is None:
+        norm_clip = optimizer in ("Adam", "Nadam")  # R/main_ace.R:143 (Q5)
+    yv, Xi, Zi, px, moments, isbinary, myBasis, theta0 = _prepare(
+        y, X, Z, pi, basis, n_knots, init_sigma, init_length_scale, verbose)
     Kc = KernelClass_Matern32_R6 if kernel == "Matern32" else KernelClass_SE_R6
     myKernel = Kc(px, myBasis.dim(), theta0, moments[0, 1], verbose, ctx=ctx)
     myOptimizer = set_optimizer(optimizer, myKernel, learning_rate, momentum, beta1, beta2,
@@ -220,6 +228,99 @@ def ace_train(y, X, Z, pi=None, kernel="SE", basis="linear", n_knots=1, optimize
                                "init.length_scale": init_length_scale,
                                "convergence": convergence, "final_evidence": stats[1, -1],
                                "stats": stats})
+
+
+BATCH_NMAX = 512  # rows of the largest model the batched engine takes
+
+
+def ace_train_batch(ys, Xs, Zs, pis=None, kernel="SE", basis="linear", n_knots=1,
+                    optimizer="Nadam", maxiter=1000, tol=1e-4, learning_rate=0.01, beta1=0.9,
+                    beta2=0.999, momentum=0.0, norm_clip=None, clip_at=1.0, init_sigma=None,
+                    init_length_scale=20.0, verbose=False, ctx=None, nonfinite="raise"):
+    """ace_train of M small datasets (n <= 512 each) in one ace_batch_train
+    call: one workgroup per model on one GPU.  ys, Xs, Zs (and pis) are
+    sequences of length M; init_length_scale and init_sigma may be sequences
+    of length M (multi-start: pass the same dataset M times).  The datasets
+    must agree in p and in the basis dimension B.  Returns a list of AceFit;
+    each carries its model's inverse of the last para_update on the host
+    (Q6), so predict_ace runs through the host-buffer path.  A model whose
+    gradient becomes non-finite stops alone: nonfinite="raise" then raises
+    AceError naming the models (ace_train's behaviour), nonfinite="none" puts
+    None in their places and returns the other fits."""
+    from .model import BatchModel
+    M = len(ys)
+    if M < 1 or len(Xs) != M or len(Zs) != M or (pis is not None and len(pis) != M):
+        raise AceError("ys, Xs, Zs (and pis) must be sequences of one length M >= 1")
+    if isinstance(kernel, (list, tuple)):  # one kernel per dataset: they must agree
+        if len(kernel) != M or len(set(kernel)) != 1:
+            raise AceError("the datasets of a batch must use one kernel")
+        kernel = kernel[0]
+    if kernel not in ("SE", "Matern32"):
+        raise AceError(f"unknown kernel {kernel!r}")
+    if norm_clip is None:
+        norm_clip = optimizer in ("Adam", "Nadam")
+    if nonfinite not in ("raise", "none"):
+        raise AceError('nonfinite must be "raise" or "none"')
+
+    def per_model(v, j):
+        return v[j] if isinstance(v, (list, tuple, np.ndarray)) else v
+
+    for j in range(M):
+        if np.size(ys[j]) > BATCH_NMAX:
+            raise AceError(f"dataset {j}: n = {np.size(ys[j])} > {BATCH_NMAX}, the batched "
+                           "engine's limit (use ace_train)")
+    for v in (init_length_scale, init_sigma):
+        if isinstance(v, (list, tuple, np.ndarray)) and len(v) != M:
+            raise AceError("init_length_scale / init_sigma sequences must have length M")
+    prep = [_prepare(ys[j], Xs[j], Zs[j], None if pis is None else pis[j], basis, n_knots,
+                     per_model(init_sigma, j), per_model(init_length_scale, j), verbose)
+            for j in range(M)]
+    px, B = prep[0][3], prep[0][6].dim()
+    for j, q in enumerate(prep):
+        if q[3] != px:
+            raise AceError(f"dataset {j} has p = {q[3]}, dataset 0 has p = {px}")
+        if q[6].dim() != B:
+            raise AceError(f"dataset {j} has basis dimension B = {q[6].dim()}, dataset 0 has "
+                           f"B = {B}")
+    nmax = max(q[0].size for q in prep)
+    bm = BatchModel(kernel, M, nmax, px, B, ctx=ctx)
+    try:
+        theta = np.empty((2 + B * (px + 1), M), order="F")
+        for j, q in enumerate(prep):
+            bm.set_data(j, q[0], q[1], q[6].B, q[4][0, 1])
+            theta[:, j] = q[7]
+        stats, its, conv, status = bm.train(theta, optimizer, learning_rate, momentum, beta1,
+                                            beta2, norm_clip, clip_at, maxiter, tol)
+        bad = [j for j in range(M) if status[j] != 0]
+        if bad and nonfinite != "none":
+            raise AceError(f"ACE_ERR_NONFINITE: models {bad}: Some gradients are not finite, "
+                           "NaN, or NA. Often this is due to too large learning rates.")
+        invs = [None if j in bad else bm.inverse(j) for j in range(M)]
+    finally:
+        bm.close()
+    Kc = KernelClass_Matern32_R6 if kernel == "Matern32" else KernelClass_SE_R6
+    fits = []
+    for j, (yv, Xi, Zi, _, moments, isbinary, myBasis, _t0) in enumerate(prep):
+        if invs[j] is None:
+            fits.append(None)
+            continue
+        myKernel = Kc(px, B, theta[:, j].copy(), moments[0, 1], False, ctx=ctx)
+        myKernel._mark_kernel(Xi, myBasis.B)
+        myKernel._inv = invs[j]
+        myKernel._inv_from_model = False
+        it = int(its[j])
+        st = stats[:, 2:it + 2, j]
+        fits.append(AceFit(
+            Kernel=myKernel, Basis=myBasis,
+            OptimSettings={"optim": optimizer, "lr": learning_rate, "momentum": momentum,
+                           "beta1": beta1, "beta2": beta2},
+            moments=moments,
+            train_data={"y": yv, "X": Xi, "Z": Zi, "Zbinary": isbinary},
+            train_stats={"RIC_bias_corrected": pis is not None and pis[j] is not None,
+                         "init.length_scale": per_model(init_length_scale, j),
+                         "convergence": bool(conv[j]), "final_evidence": st[1, -1],
+                         "stats": st}))
+    return fits
 
 
 def predict_ace(obj, newX=None, newZ=None, marginal=False, return_average_treatments=False,

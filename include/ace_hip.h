@@ -503,6 +503,49 @@ int ace_model_create_sharded_host(ace_ctx *ctx, int kind, int64_t n, int p, int 
                                   int world, int rank, const ace_comm_ops *ops,
                                   ace_model **out);
 
+/* ------------------------------- batched engine: many small models at once
+ *
+ * M independent models of at most nmax <= 512 rows each (Monte-Carlo
+ * replications, bootstrap refits, cross-validation folds, multi-start), all
+ * of one kernel kind, p and B.  One workgroup runs one model's whole
+ * para_update, and the workgroups never communicate, so M >= 256 models
+ * occupy the whole chip.  Per model the meaning of theta,
+ * grad, stats and mu_post is exactly ace_model_para_update's, and the stats
+ * columns of ace_batch_train are exactly ace_model_train's.  A model's
+ * outputs are bitwise reproducible and depend neither on M nor on its
+ * position in the batch.
+ * Errors: nmax > 512, p > 64 or B > 32 ACE_ERR_UNSUPPORTED; M < 1, j or n_j
+ * out of range, or a call that needs data before every model has some
+ * ACE_ERR_ARG; an allocation that does not fit ACE_ERR_OOM.
+ * Out of scope: sharded batches (single GPU only) and the ace_dmat handle
+ * path. */
+typedef struct ace_batch ace_batch;
+int ace_batch_create(ace_ctx *ctx, int kind, int64_t M, int64_t nmax, int p, int B,
+                     ace_batch **out);
+void ace_batch_destroy(ace_batch *b);
+/* model j's data, 1 <= n_j <= nmax: y (n_j), X (n_j x p), Z (n_j x (B - 1)) */
+int ace_batch_set_data(ace_batch *b, int64_t j, int64_t n_j, const double *y, const double *X,
+                       const double *Z, double std_y);
+/* One para_update of every model: theta P x M (in/out: row 1 <- mu_solution
+ * at iter 1), grad P x M, stats 2 x M, mu_post M (may be NULL).  A model whose
+ * matrix is not positive definite gets NaN grad / stats / mu_post; the
+ * others are untouched by it. */
+int ace_batch_para_update(ace_batch *b, int iter, double *theta, double *grad, double *stats,
+                          double *mu_post);
+/* ace_model_train of every model, in lock step; a model that stopped
+ * (converged, non-finite gradient, maxiter) is skipped from then on, so its
+ * theta, stats and resident inverse are those of its own last para_update
+ * (Q6).  theta P x M in/out; stats 2 x (maxiter + 2) x M, model j's matrix at
+ * stats + 2 (maxiter + 2) j; iters, converged, status M each.  Returns ACE_OK
+ * when the call ran: a model's non-finite stop is status[j] =
+ * ACE_ERR_NONFINITE (else ACE_OK) and does not stop the others.  The
+ * interrupt poll is honoured between iterations (ACE_ERR_INTERRUPTED). */
+int ace_batch_train(ace_batch *b, int optimizer, double learn_rate, double momentum, double beta1,
+                    double beta2, int norm_clip, double clip_at, int maxiter, double tol,
+                    double *theta, double *stats, int *iters, int *converged, int *status);
+/* model j's resident inverse (n_j x n_j) of its last para_update */
+int ace_batch_get_inverse(ace_batch *b, int64_t j, double *inv);
+
 #ifdef __cplusplus
 }
 #endif
