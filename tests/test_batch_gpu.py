@@ -6,6 +6,8 @@ outputs are bitwise independent of M, of its position and of its neighbours
 (a non-finite neighbour included), and every model stops on its own."""
 import numpy as np
 import pytest
+
+import batch_cases as C
 from conftest import golden
 from test_gpu import close
 
@@ -30,8 +32,7 @@ def O():
 
 
 def _problems(ns, p, B, seed0=0):
-    from additivecausalexpansion_amd.synthetic import make_problem
-    return [make_problem(n, p, B, seed=seed0 + 11 * j + n) for j, n in enumerate(ns)]
+    return C.problems(ns, p, B, seed0)
 
 
 def _batch(A, kernel, probs, p, B, nmax=None, order=None):
@@ -97,8 +98,17 @@ def _ragged(A, kernel):
 
 # ------------------------------------------------------------------ 1. evaluation
 @pytest.mark.parametrize("kernel", KERNELS)
-@pytest.mark.parametrize("ns,p,B", [(RAGGED_N, 3, 5), ((33, 33), 1, 1), ((97, 97), 20, 10),
-                                    ((300, 300), 2, 5), ((512, 512), 2, 2)])
+@pytest.mark.parametrize("ns,p,B", [
+    (RAGGED_N, 3, 5), ((33, 33), 1, 1), ((97, 97), 20, 10), ((300, 300), 2, 5), ((512, 512), 2, 2),
+    ((130,), 8, 3), ((97,), 16, 2),  # p equals its feature bucket: no zero padding
+    ((70, 45), 64, 2),               # PM = 64 unpadded: both passes of the length-scale sums
+    ((50,), 2, 32),                  # B at its maximum, ZS = 31
+    # 256 threads: the second trip of the assembly and gradient row loops at
+    # n = 257 (one live lane in the fifth wave), the assembly's third at n = 512
+    # (528 rows with the right-hand sides)
+    ((257, 300, 512), 20, 3),
+    ((272, 511), 33, 2),             # PM = 64 at 256 threads; n a multiple of 16, and 511
+])
 def test_batch_para_update_matches_oracle_and_device_model(A, O, kernel, ns, p, B):
     """Every model of the batch against the oracle's kernmat_sym -> invkernel ->
     grad chain and against DeviceModel.para_update, at iter 1 (mu first) and 2."""
@@ -333,3 +343,145 @@ def test_batch_argument_errors(A):
     g, st, mu = bm.para_update(1, th2)
     assert np.all(np.isfinite(g)) and bm.inverse(1).shape == (20, 20)
     bm.close()
+
+
+# ------------------------------------------------------------------ 9. slot reuse
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_batch_slot_reused_for_a_smaller_model(A, kernel):
+    """A slot given new, smaller data after a larger model runs over that
+    model's leftovers in the scratch matrix: they must not reach its results."""
+    big, small, other = _problems((130, 40, 97), 3, 5)
+    th_of = lambda *ps: np.asfortranarray(np.column_stack([q[3] for q in ps]))  # noqa: E731
+    bm = A.BatchModel(kernel, 2, 130, 3, 5)
+    bm.set_data(0, big[0], big[1], big[2], big[4])
+    bm.set_data(1, other[0], other[1], other[2], other[4])
+    g1, st1, mu1 = bm.para_update(1, th_of(big, other))
+    inv1 = bm.inverse(1)
+    assert np.all(np.isfinite(g1)) and bm.inverse(0).shape == (130, 130)
+    bm.set_data(0, small[0], small[1], small[2], small[4])
+    g2, st2, mu2 = bm.para_update(1, th_of(small, other))
+    fresh = A.BatchModel(kernel, 1, 130, 3, 5)
+    fresh.set_data(0, small[0], small[1], small[2], small[4])
+    gf, stf, muf = fresh.para_update(1, th_of(small))
+    assert np.all(np.isfinite(gf)) and np.all(np.isfinite(stf))
+    assert np.array_equal(g2[:, 0], gf[:, 0]) and np.array_equal(st2[:, 0], stf[:, 0])
+    assert mu2[0] == muf[0]
+    assert np.array_equal(bm.inverse(0), fresh.inverse(0)) and bm.inverse(0).shape == (40, 40)
+    assert np.array_equal(g2[:, 1], g1[:, 1]) and np.array_equal(st2[:, 1], st1[:, 1])
+    assert mu2[1] == mu1[1] and np.array_equal(bm.inverse(1), inv1)
+    fresh.close()
+    bm.close()
+
+
+# ------------------------------------------------------------------ 10. not positive definite
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_batch_not_positive_definite_model_gets_nan_and_does_not_leak(A, kernel):
+    """Three models with an exactly zero pivot (batch_cases.singular_cases;
+    tests/test_batch_regimes_cpu.py shows the row of A is exactly zero) -- in
+    the first 16-block, in a later one and in the ragged last one -- between
+    two healthy models.  The kernel's own pivot test has to fire: nothing in
+    theta or the data is non-finite."""
+    ragged, res = _ragged(A, kernel)
+    healthy = [RAGGED_N.index(n) for n in C.HEALTHY_N]
+    sing = [c[1] for c in C.singular_cases()]
+    probs = [sing[0], ragged[healthy[0]], sing[1], ragged[healthy[1]], sing[2]]
+    bad, good = (0, 2, 4), (1, 3)
+    th_all = lambda: np.asfortranarray(np.column_stack([q[3] for q in probs]))  # noqa: E731
+    bm = _batch(A, kernel, probs, 3, 5)
+    th = th_all()
+    assert np.all(np.isfinite(th))
+    g, st, mu = bm.para_update(1, th)
+    for j in bad:
+        assert not np.any(np.isfinite(g[:, j])) and not np.any(np.isfinite(st[:, j]))
+        assert not np.isfinite(mu[j])
+    # the healthy ones as in the ragged batch, which holds no singular model
+    _, g0, st0, mu0, inv0 = res[0]
+    for j, j0 in zip(good, healthy):
+        assert np.all(np.isfinite(g[:, j]))
+        assert np.array_equal(g[:, j], g0[:, j0]) and np.array_equal(st[:, j], st0[:, j0])
+        assert mu[j] == mu0[j0] and th[1, j] == mu0[j0]
+        assert np.array_equal(bm.inverse(j), inv0[j0])
+    # train: status ACE_ERR_NONFINITE at iteration 1, theta kept (but theta[1],
+    # the iteration-1 mean_solution assigned before the optimizer)
+    th = th_all()
+    before = th.copy()
+    stats, its, conv, status = bm.train(th, "Nadam", maxiter=5, tol=-1.0)
+    keep = np.delete(np.arange(th.shape[0]), 1)
+    for j in bad:
+        assert status[j] == NONFINITE and its[j] == 1 and not conv[j]
+        assert np.array_equal(th[keep, j], before[keep, j])
+    clean = _batch(A, kernel, [probs[j] for j in good], 3, 5)
+    th_c = np.asfortranarray(before[:, list(good)])
+    stats_c, its_c, _, status_c = clean.train(th_c, "Nadam", maxiter=5, tol=-1.0)
+    assert np.all(status_c == 0) and np.all(its_c == 5)
+    for k, j in enumerate(good):
+        assert status[j] == 0 and its[j] == 5
+        assert np.array_equal(th[:, j], th_c[:, k])
+        assert np.array_equal(stats[:, :, j], stats_c[:, :, k])
+    clean.close()
+    bm.close()
+    # the single-model path promises the same
+    y, X, Z, ths, sy = sing[2]
+    m = A.DeviceModel(kernel, y.size, 3, 5)
+    m.set_data(y, X, Z, sy)
+    g1, st1, mu1 = m.para_update(1, ths.copy())
+    m.close()
+    assert not np.any(np.isfinite(g1)) and not np.any(np.isfinite(st1)) and not np.isfinite(mu1)
+
+
+# ------------------------------------------------------------------ 11. the other optimizers, the clip
+_opt_oracle = {}
+
+
+def _oracle_trajectory(O, kernel, name):
+    """The oracle's trajectories of one configuration, computed once."""
+    if (kernel, name) not in _opt_oracle:
+        _, oname, lr, mom, clip, clip_at = C.OPT_CONFIGS[name]
+        out = []
+        for y, X, Z, th, sy in C.opt_problems(name):
+            opt = O.OracleOptimizer(oname, th.size, lr, momentum=mom, norm_clip=clip, clip_at=clip_at)
+            out.append(O.train_trajectory(kernel, y, X, Z, th, sy, C.OPT_ITERS, opt)[:3])
+        _opt_oracle[(kernel, name)] = out
+    return _opt_oracle[(kernel, name)]
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("name", list(C.OPT_CONFIGS))
+def test_batch_step_optimizers_and_clip(A, O, kernel, name):
+    """k_batch_step's Nesterov and Adam branches, the clip switched off, and
+    Q5 (||g|| > clip_at rescales to unit norm) at clip_at = 0.3, against the
+    oracle's trajectory and DeviceModel.train with the bounds of
+    test_batch_train_matches_golden_trajectory."""
+    pname, _, lr, mom, clip, clip_at = C.OPT_CONFIGS[name]
+    probs = C.opt_problems(name)
+    T = C.OPT_ITERS
+    ref = _oracle_trajectory(O, kernel, name)
+    if clip_at != 1.0:
+        # Q5 differs from a rescale to clip_at only where clip_at < ||g|| <= 1
+        norms = np.array([np.linalg.norm(r[2], axis=1) for r in ref])
+        print(f"{name} {kernel}: the oracle's ||g|| per model and iteration\n{norms}")
+        assert np.all(np.any((norms > clip_at) & (norms <= 1.0), axis=1)), norms
+    args = (pname, lr, mom, 0.9, 0.999, clip, clip_at)
+    bm = _batch(A, kernel, probs, C.OPT_P, C.OPT_B)
+    th = _theta(probs)
+    stats, its, conv, status = bm.train(th, *args, maxiter=T, tol=-1.0)
+    bm.close()
+    assert np.all(its == T) and not np.any(conv) and np.all(status == 0)
+    for j, (y, X, Z, th0, sy) in enumerate(probs):
+        thetas, st_ref, _ = ref[j]
+        close(stats[:, 1:T + 1, j].T, st_ref, 1e-6, 1e-9, check=f"batch {name} stats vs oracle")
+        close(th[:, j], thetas[T - 1], 1e-5, 1e-9, check=f"batch {name} theta vs oracle")
+        m = A.DeviceModel(kernel, y.size, C.OPT_P, C.OPT_B)
+        m.set_data(y, X, Z, sy)
+        th2 = th0.copy()
+        stats2, it2, _ = m.train(th2, *args, maxiter=T, tol=-1.0)
+        m.close()
+        assert it2 == T
+        close(stats[:, 1:T + 1, j], stats2[:, 1:T + 1], 1e-6, 1e-9, check=f"batch {name} stats vs DeviceModel")
+        close(th[:, j], th2, 1e-5, 1e-9, check=f"batch {name} theta vs DeviceModel")
+        one = _batch(A, kernel, probs, C.OPT_P, C.OPT_B, order=[j])
+        th1 = _theta(probs, [j])
+        stats1, its1, _, status1 = one.train(th1, *args, maxiter=T, tol=-1.0)
+        one.close()
+        assert its1[0] == its[j] and status1[0] == 0
+        assert np.array_equal(th1[:, 0], th[:, j]) and np.array_equal(stats1[:, :, 0], stats[:, :, j])

@@ -133,7 +133,7 @@ _REF = {}
 
 def referee(kernel, name, n, p, B, seed=9):
     """One regime's problem and its para_update_ld (iteration 1) with the
-    pieces grad_from_inverse needs (the slices Kb, log det A), computed once
+    pieces grad_from_inverse needs (the slices Kb, A^-1, log det A), computed once
     and shared; never modified."""
     key = (kernel, name, n, p, B, seed)
     if key not in _REF:
@@ -142,7 +142,7 @@ def referee(kernel, name, n, p, B, seed=9):
         A = Kb.sum(axis=0) + np.exp(LD(th[0])) * np.eye(n, dtype=LD)
         inv, logdet = _chol_inverse(A)
         g, st, mu = grad_from_inverse(kernel, y, X, Z, th, sy, inv, logdet, 1, Kb)
-        _REF[key] = dict(y=y, X=X, Z=Z, th=th, sy=sy, Kb=Kb, logdet=logdet, g=g, st=st, mu=mu)
+        _REF[key] = dict(y=y, X=X, Z=Z, th=th, sy=sy, Kb=Kb, inv=inv, logdet=logdet, g=g, st=st, mu=mu)
     return _REF[key]
 
 
