@@ -184,78 +184,70 @@ struct SweepBufs {
   double *A;      // Naug x Naug, col-major, ld = Naug, lower triangle used
   int64_t ld;     // Naug
   int64_t npad;   // multiple of NB
-  double *P[8];   // Naug x NB : -panel (negated copy), slot k & 1 (k % 2Z with Z steps per group)
+  double *P[8];   // Naug x NB : -panel (negated copy), slot k % 2Z (one-step schedule: k & 1)
   double *W[8];   // Naug x NB : panel being swept, same slots; [2] .. null unless used
-  int Z = 2;      // steps per bulk launch (sweep_group()); the lists below follow it
+  int Z = 2;      // steps per bulk launch (sweep_group_n()); gorder / htiles follow it
   double *SW;     // SW_DOUBLES: 2 SUB x SUB sub-pivot inverses + split-panel chunks
   double *S[2];   // SUB x NB col-major: pivot rows before their sub-sweep (ping-pong)
   double *piv;    // npad pivots
   int *flag;      // set to 1 on a non-positive / non-finite pivot
   const Tile *order = nullptr;  // k_update tile order (xcd_update_order), or row-major
   int64_t norder = 0;
-  // lookahead cross update on k_update's 128-tiles (cross_update_tiles):
-  // device list of every step's cross tiles, host offsets (steps + 1); null:
-  // k_update_x on 64-tiles
+  // the one-step schedule's lookahead cross (cross_update_tiles): device list
+  // of every step's cross tiles, host offsets (steps + 1)
   const Tile *xtiles = nullptr;
   const int64_t *xoff = nullptr;
-  // two sweep steps per bulk launch (pair_steps()): every group's lookahead
-  // cross tiles (pair_cross_tiles), host offsets per group
-  const Tile *ptiles = nullptr;
-  const int64_t *poff = nullptr;
-  const Tile *gorder = nullptr;  // per-group bulk orders (tail_sort), glen each
+  const Tile *gorder = nullptr;  // per-group bulk orders (pair_bulk_orders), glen each
   const Tile *htiles = nullptr;  // group_head_tiles lists (run_sweep_heads), offsets hoff
   const int64_t *hoff = nullptr;
   int64_t glen = 0;
-  // small n: per group a bulk work queue of BQ_INTS ints (k_update_multi_r,
-  // zeroed per sweep) and the CUs per shader engine it leaves to the chains
+  // small n: the bulk work queues and launch counters (bq_layout) and the CUs
+  // per shader engine the bulk launches leave to the chains
   int *bq = nullptr;
   int breserve = 0;
 };
+// SweepBufs::bq for a sweep of `steps` steps in groups of Z: per group a bulk
+// work queue of BQ_INTS ints (k_update_multi_r, zeroed per sweep), from fctr
+// on two counters per step (k_panel_split4's grid barrier and exits), from
+// qctr on one per step (k_update_q4's D_0 pieces).  The counters are zero
+// between launches: each launch's last workgroup resets them.
 constexpr int BQ_INTS = 2 + 64;
+struct BqLayout {
+  int64_t fctr, qctr, ints;
+};
+inline BqLayout bq_layout(int steps, int Z) {
+  const int64_t q = (int64_t)((steps + Z - 1) / Z) * BQ_INTS;
+  return BqLayout{q, q + 2 * steps, q + 3 * steps};
+}
+// CUs per shader engine a small-n bulk launch leaves to the panel chains:
+// ACE_BULK_RESERVE (0 .. 2) overrides; default 1 up to n = ACE_BULK_RESERVE_N,
+// none above (there the bulk launches are the critical path)
 int bulk_reserve(int64_t naug);
+// small n: a group's first head launch before the rest of its lookahead
+// (ACE_QFIRST overrides)
 bool q_first(int64_t naug);
-// Two sweep steps per bulk update launch (k_update_pair, K = 2 NB per tile;
-// default): ACE_PAIR=0 selects one step per launch (A/B switch).
+// Several sweep steps per bulk update launch (run_sweep_heads, default);
+// ACE_PAIR=0 selects the one-step reference schedule.
 bool pair_steps();
-// Lookahead cross tiles of group g = steps 2g, 2g + 1, for g = 1 ..
-// ngroups-1 (each list dealt to the XCDs): [off[2g], off[2g+1]) the lower
-// 128-tiles with I or J in block 2g, [off[2g+1], off[2g+2]) those with I or
-// J in block 2g + 1 and not in block 2g (empty for a one-step group).
-// Z steps per group (sweep_group()): off[2g] .. off[2g+1] the tiles with I
-// or J in the group's first block, off[2g+1] .. off[2g+2] those in its other
-// blocks and not in the first.
-std::vector<Tile> pair_cross_tiles(int64_t naug, int steps, std::vector<int64_t> &off,
-                                   int Z = 2);
 // Head / tail lists of the group schedule's lookahead (run_sweep_heads):
-// 2Z lists per group at off[G 2Z + m] (see ace_sweep.hip).  heads_on():
-// ACE_HEADS switch.
+// 2Z lists per group at off[G 2Z + m] (see ace_sweep.hip).
 std::vector<Tile> group_head_tiles(int64_t naug, int steps, int Z, std::vector<int64_t> &off);
-bool heads_on();
-// Steps per bulk launch: 2 (k_update_pair, default), ACE_GROUP=3 or 4 selects
-// k_update_multi groups (run_sweep_groups).
+// Steps per bulk launch: ACE_GROUP = 2 .. 4 (default 4); sweep_group_n: for a
+// model of naug rows (3 at small n unless ACE_GROUP is set)
 int sweep_group();
-int sweep_group_n(int64_t naug);  // sweep_group() for a model of naug rows
+int sweep_group_n(int64_t naug);
 double update_gemm_tiles_group(int64_t naug, int64_t ka0, int npan, int kx0, int kx1);
 // The lower 128-tiles with I or J in block k+1, for k = 0 .. steps-2,
 // concatenated (each step's list dealt to the XCDs like the bulk order);
-// off[k] .. off[k+1] is step k's range.  ACE_XUPD=0 selects k_update_x.
-bool cross_update_on_tiles();
+// off[k] .. off[k+1] is step k's range.
 std::vector<Tile> cross_update_tiles(int64_t naug, int steps, std::vector<int64_t> &off);
 // k_update tile order: the tiles of `tl` grouped into S x S super-blocks of
 // 128-tiles that are dealt whole to the 8 XCDs; list index b runs on XCD
 // b % 8 (dispatch is round-robin).  Entries with I < 0 are padding.
 std::vector<Tile> xcd_update_order(const std::vector<Tile> &tl, int S,
                                    const std::function<double(const Tile &)> &cost = nullptr);
-// The tiles along a Hilbert curve cut into 8 equal-work pieces, one per XCD
-// (ACE_BULK_CURVE=1: the bulk orders of pair_bulk_orders)
-bool bulk_curve();
-std::vector<Tile> curve_update_order(const std::vector<Tile> &tl,
-                                     const std::function<double(const Tile &)> &cost = nullptr);
-// per group of two steps, the bulk order with each XCD's cheap tiles last
-// (ACE_TAIL_SORT=1): ngroups lists of *len entries
-bool tail_sort();
-// (sharded: rank r's own tiles of G)
-// (Z: steps per group, sweep_group())
+// per group of Z steps, the bulk order with each XCD's cheap tiles last:
+// ngroups lists of *len entries (sharded: rank r's own tiles of G)
 std::vector<Tile> pair_bulk_orders(int64_t naug, int steps, int64_t *len, int G = 1, int r = 0,
                                    int Z = 2);
 // own lower tiles of size T over [0, ntile*T) in row-major order (ace_shard.cpp)
@@ -263,11 +255,12 @@ std::vector<Tile> own_tiles(int64_t ntile, int T, int G, int r);
 // super-block size S of that order (0: row-major grid); ACE_UPD_ORDER=S
 // overrides (diagnostic A/B switch)
 int update_order_block();
-// Lookahead: the panel sweep of step k+1 runs on `side` while the main
-// stream updates the rest of step k.  `ev` needs 2*steps + 1 events.
+// Lookahead streams and events of one sweep.  side: the panel chains (one-step
+// schedule) / the head path; side2: the tail path; either may alias the main
+// stream (ACE_STREAMS).  ev: 6 steps + 10 events (SweepWork::ensure).
 struct SweepSync {
   hipStream_t side;
-  hipStream_t side2 = nullptr;  // pair steps: the second block's cross (needs 4 steps + 4 events)
+  hipStream_t side2 = nullptr;
   hipEvent_t *ev;
   int nev;
   bool ready_recorded = false;  // caller already recorded ev[2 * steps] ("inputs ready")

@@ -8,16 +8,18 @@
 
 // Buffers of one Gauss-Jordan sweep and its lookahead events.
 struct SweepWork {
-  DBuf A, Ps[8], Ws[8], SW, S0, S1, piv, flag, order, xtiles, ptiles, gorder, htiles;
-  int Z = 2;  // steps per bulk launch (sweep_group()), panel slots k % 2Z
+  DBuf A, Ps[8], Ws[8], SW, S0, S1, piv, flag, order, xtiles, gorder, htiles;
+  int Z = 2;  // steps per bulk launch (sweep_group_n()), panel slots k % 2Z
   DBuf gtiles;                          // handle path: the gradient's tile list (build_grad_tiles)
   DBuf aq;                              // persistent assembly: tile counter, exits, CU claims
   DBuf bq;                              // small n: the bulk launches' work queues
   int breserve = 0;
+  int64_t bq_npad = -1;                 // the (npad, Z) bq's counters were last zeroed for
+  int bq_Z = 0;
   DBuf gpart, gwork, gsum;              // handle path: gradient partial-sum scratch
   DBuf norms;                           // handle path: slice norms (TabView::norms)
   int64_t ngtiles = 0, ngdiag = -2;     // -2: not built yet
-  std::vector<int64_t> xoff, poff, hoff;
+  std::vector<int64_t> xoff, hoff;
   int64_t glen = 0;
   std::vector<hipEvent_t> ev;
   int64_t n = 0, npad = 0, naug = 0, norder = 0;
@@ -48,50 +50,46 @@ struct SweepWork {
       upload_bytes(ctx, order.p, t.data(), t.size() * sizeof(Tile), "upload tile order");
       norder = (int64_t)t.size();
     }
-    poff.clear();
-    if (pair_steps() && cross_update_on_tiles() && npad / NB >= 2) {
+    const int steps = (int)(npad / NB);
+    // the group schedule's lists (run_sweep_heads); the one-step schedule
+    // (ACE_PAIR=0, or a single step) needs none of them
+    glen = 0;
+    hoff.clear();
+    if (pair_steps() && steps >= 2) {
       Z = sweep_group_n(naug);
       for (int j = 2; j < 2 * Z; ++j) {
         alloc(ctx, Ps[j], (size_t)(naug * NB) * sizeof(double), "alloc panel");
         alloc(ctx, Ws[j], (size_t)(naug * NB) * sizeof(double), "alloc panel");
       }
-      const std::vector<Tile> t = pair_cross_tiles(naug, (int)(npad / NB), poff, Z);
-      alloc(ctx, ptiles, std::max<size_t>(t.size(), 1) * sizeof(Tile), "alloc pair cross tiles");
-      if (!t.empty())
-        upload_bytes(ctx, ptiles.p, t.data(), t.size() * sizeof(Tile), "upload pair cross tiles");
-      glen = 0;
-      if (tail_sort()) {
-        const std::vector<Tile> o = pair_bulk_orders(naug, (int)(npad / NB), &glen, 1, 0, Z);
-        alloc(ctx, gorder, o.size() * sizeof(Tile), "alloc bulk orders");
-        upload_bytes(ctx, gorder.p, o.data(), o.size() * sizeof(Tile), "upload bulk orders");
-      }
-      hoff.clear();
-      if (heads_on()) {
-        const std::vector<Tile> h = group_head_tiles(naug, (int)(npad / NB), Z, hoff);
-        alloc(ctx, htiles, std::max<size_t>(h.size(), 1) * sizeof(Tile), "alloc head tiles");
-        if (!h.empty())
-          upload_bytes(ctx, htiles.p, h.data(), h.size() * sizeof(Tile), "upload head tiles");
-      }
+      const std::vector<Tile> o = pair_bulk_orders(naug, steps, &glen, 1, 0, Z);
+      alloc(ctx, gorder, o.size() * sizeof(Tile), "alloc bulk orders");
+      upload_bytes(ctx, gorder.p, o.data(), o.size() * sizeof(Tile), "upload bulk orders");
+      const std::vector<Tile> h = group_head_tiles(naug, steps, Z, hoff);
+      alloc(ctx, htiles, std::max<size_t>(h.size(), 1) * sizeof(Tile), "alloc head tiles");
+      if (!h.empty())
+        upload_bytes(ctx, htiles.p, h.data(), h.size() * sizeof(Tile), "upload head tiles");
     }
-    breserve = (Z > 2 && heads_on()) ? bulk_reserve(naug) : 0;
+    breserve = Z > 2 ? bulk_reserve(naug) : 0;
     if (breserve > 0) {
-      // + per sweep step the barrier and exit counters of k_panel_split4 and
-      // the D_0 counter of k_update_q4 (ACE_QSPLIT): zero
-      // when allocated, reset by each launch's last workgroup (the per-sweep
-      // memset covers the queues only: the first chain can start before it)
-      void *const old = bq.p;
-      alloc(ctx, bq, (size_t)((npad / NB + Z - 1) / Z * BQ_INTS + 3 * (npad / NB)) * sizeof(int),
-            "alloc bulk queues");
-      if (bq.p != old) ck(ctx, hipMemsetAsync(bq.p, 0, bq.bytes, ctx->stream), "memset queues");
+      // bq_layout: the bulk queues, then per sweep step the counters of
+      // k_panel_split4 and k_update_q4.  The counters must be zero before the
+      // first launch and are reset by each launch's last workgroup (the
+      // per-sweep memset covers the queues only: the first chain can start
+      // before it).  Their offsets depend on (npad, Z): when either changes
+      // they would land on stale queue words, so the whole buffer is zeroed.
+      const size_t qbytes = (size_t)bq_layout(steps, Z).ints * sizeof(int);
+      const bool fresh = !bq.p || bq.bytes < qbytes;
+      alloc(ctx, bq, qbytes, "alloc bulk queues");
+      if (fresh || bq_npad != npad || bq_Z != Z)
+        ck(ctx, hipMemsetAsync(bq.p, 0, bq.bytes, ctx->stream), "memset queues");
+      bq_npad = npad;
+      bq_Z = Z;
     }
-    xoff.clear();
-    if (cross_update_on_tiles()) {
-      const std::vector<Tile> t = cross_update_tiles(naug, (int)(npad / NB), xoff);
-      alloc(ctx, xtiles, std::max<size_t>(t.size(), 1) * sizeof(Tile), "alloc cross tiles");
-      if (!t.empty())
-        upload_bytes(ctx, xtiles.p, t.data(), t.size() * sizeof(Tile), "upload cross tiles");
-    }
-    const size_t need = (size_t)(6 * (npad / NB) + 10);
+    const std::vector<Tile> t = cross_update_tiles(naug, steps, xoff);
+    alloc(ctx, xtiles, std::max<size_t>(t.size(), 1) * sizeof(Tile), "alloc cross tiles");
+    if (!t.empty())
+      upload_bytes(ctx, xtiles.p, t.data(), t.size() * sizeof(Tile), "upload cross tiles");
+    const size_t need = (size_t)(6 * steps + 10);
     while (ev.size() < need) {
       hipEvent_t e;
       ck(ctx, hipEventCreateWithFlags(&e, ACE_SYNC_EVENT_FLAGS), "event");
@@ -108,10 +106,6 @@ struct SweepWork {
       b.W[j] = Ws[j].p ? Ws[j].d() : nullptr;
     }
     b.Z = Z;
-    if (!poff.empty()) {
-      b.ptiles = reinterpret_cast<const Tile *>(ptiles.p);
-      b.poff = poff.data();
-    }
     if (glen > 0) {
       b.gorder = reinterpret_cast<const Tile *>(gorder.p);
       b.glen = glen;

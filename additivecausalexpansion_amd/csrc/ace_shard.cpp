@@ -637,9 +637,8 @@ void run_sweep_sharded_steps(ShardModel &m, int which, bool timed) {
   }
 }
 
-// Z sweep steps per bulk launch (Z = sweep_group(), 4 by default), the
-// single-GPU group schedule (ace_sweep.hip run_sweep_groups) on each rank's own
-// tiles.  Group g = steps Z g .. Z g + z - 1, panels in slots k % (2 Z):
+// Z sweep steps per bulk launch (Z = sweep_group_n()), the group schedule
+// without the head / tail split on each rank's own tiles.  Group g = steps Z g .. Z g + z - 1, panels in slots k % (2 Z):
 //   main:  wait(ready g) -> k_update_multi over the own tiles outside group
 //          g+1's cross (group g's z panels, K = z NB per tile) -> bulkdone(g)
 //   side:  wait(bulkdone g-1) -> group g's panels on block kb's cross (the
@@ -983,7 +982,7 @@ ShardModel *shard_create_any(ace_ctx *ctx, const Shape &s, int64_t n, int world,
   const int steps = (int)(npad / NB);
   // the head schedule in every mode (the host-callback group's head and tail
   // exchanges block the host one at a time, in issue order)
-  m->heads = shard_heads_on() && heads_on() && pair_steps() && steps >= 2 && m->Z >= 2 &&
+  m->heads = shard_heads_on() && pair_steps() && steps >= 2 && m->Z >= 2 &&
              (m->sim || m->proxy || m->host || rccl().CommSplit);
   if (m->heads && m->comm)
     nck(ctx, rccl().CommSplit(m->comm, 0, rank, &m->comm2, nullptr), "ncclCommSplit");

@@ -33,8 +33,8 @@ namespace ace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-// The lookahead chain kernels (k_pivot, k_panel: one to four workgroups of
-// latency-bound work) share CUs with the MFMA-heavy update tiles of the main
+// The lookahead chain kernels (k_pivot, k_panel_split: one to sixteen
+// workgroups of latency-bound work) share CUs with the MFMA-heavy update tiles of the main
 // stream.  Raising their waves' issue priority lets them win the SIMD
 // arbitration instead of getting a 1/5 share of the issue slots.
 // (Priority 3 on them and on the head-path gather k_update_q: C1 -0.06 ms
@@ -46,109 +46,49 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // Sweeps the 64x64 sub-block s of the panel's pivot rows:
 //   d = D_tt; D_ij -= D_it D_tj / d; D_it /= d; D_tj /= d; D_tt = -1/d
 // -> SW = -D_s^-1 (exactly symmetric: every product is formed as a*b with
-// a = D_it = D_ti).  Layout: lane = row i, wave w of NW keeps columns
-// CW w .. CW w + CW - 1 (CW = 64 / NW) in registers; per pivot the owning
-// wave publishes column t and lane t of every wave publishes its part of
-// row t through double-buffered LDS vectors, so there is one barrier per
-// pivot.  More waves = fewer dependent VALU operations per wave per pivot
-// (the chain's critical path); the arithmetic per element is the same for
-// every NW.  D_s is read from the pivot-row snapshot S (written by k_gather
-// / the previous panel update); every pivot d (Cholesky diagonal squared)
-// is recorded.
-template <int NW>
+// a = D_it = D_ti).  Register layout in and out: lane = row i, wave w of 4
+// keeps columns 16 w .. 16 w + 15.  D_s is read from the pivot-row snapshot
+// S (written by k_gather / the previous panel update); every pivot d
+// (Cholesky diagonal squared) is recorded in pv[].
+//
+// The sweep is blocked by 16: the sweep operator composes, so sweeping
+// pivots 0..63 one by one equals four block sweeps of the 16x16 diagonal
+// blocks, each
+//   M_ss <- S = -D^-1 (D = M_ss),  M_sc <- D^-1 M_sc = -S M_sc,
+//   M_rc <- M_rc - M_rs D^-1 M_sc = M_rc + M_rs (S M_sc)   (r, c != s).
+// The 16 scalar pivots of M_ss run in ONE wave with no barrier and no LDS
+// memory: lane (r, g) = (lane & 15, lane >> 4) holds M(r, 4g .. 4g+3); pivot
+// t's row comes by a 64-bit DPP row_newbcast:t (lane t of every 16-lane row
+// holds row t's part of that row's columns) and its column by replicating
+// row t/4 (the lanes holding column t) into all four rows (rep_row_bp).
+// Every wave sweeps M_ss redundantly, so S is in every wave's registers as
+// the MFMA A operand (the k index of a 16x16x4 step permuted to 4g + e,
+// which needs no data movement); wave w != s then forms Un = S M_sw (4
+// MFMAs), writes M_sw = -Un (and its mirror M_ws), and for c >= w, c != s
+// updates M_cw += M_cs Un (4 MFMAs each, k permuted to g + 4e so that Un's
+// accumulator layout is the B operand as it stands) and mirrors it: every
+// off-diagonal block is formed once and mirrored, every diagonal block from
+// its lower triangle, so M stays exactly symmetric.  Per 16 pivots ~35 VALU
+// + 4 permlane + 5 DPP instructions per wave, where one scalar pivot per
+// barrier (the form this replaced; DESIGN.md "retired variants") took 16
+// barriers and 64 columns of updates per row: the latency of the pivot
+// chain's 64x64 sweep (k_pivot 35 us alone, 93 us under the bulk update) is
+// what this cuts.  M: the 64x64 matrix in LDS (pitch P, even, 16-B aligned
+// rows).
+
+// LDS of the kernels that run the sub-sweep beside other work (k_pivot,
+// k_panel_split*): only pv is used.  colb / rowb (the retired scalar sweep's
+// 2 KB of row / column vectors) stay as padding: the small-n schedule sizes
+// k_panel_split4's extra LDS (ACE_CHAIN_XLDS) so that no bulk workgroup fits
+// beside a chain workgroup, and that sum counts them.
 struct PivotLds {
   __attribute__((aligned(16))) double colb[2][SUB];
   __attribute__((aligned(16))) double rowb[2][SUB];
   double pv[SUB];
 };
 
-// the sub-sweep itself: v = this lane's row, columns CW w .. CW w + CW - 1
-template <int NW>
-__device__ __forceinline__ void pivot_sweep(double (&v)[SUB / NW], PivotLds<NW> &L, int tid) {
-  constexpr int CW = SUB / NW;
-  static_assert(CW % 2 == 0, "double2 row publishing");
-  const int lane = tid & 63, w = tid >> 6;
-  // no global memory traffic inside the loop: every __syncthreads() is then
-  // a bare s_barrier (a pending global store would add a vmcnt(0) wait)
-#pragma unroll 1
-  for (int tw = 0; tw < NW; ++tw) {
-#pragma unroll
-    for (int tq = 0; tq < CW; ++tq) {
-      const int t = CW * tw + tq;
-      const int buf = tq & 1;
-      if (w == tw) L.colb[buf][lane] = v[tq];
-      if (lane == t) {
-#pragma unroll
-        for (int q = 0; q < CW; q += 2)
-          *reinterpret_cast<double2 *>(&L.rowb[buf][CW * w + q]) = double2{v[q], v[q + 1]};
-      }
-      __syncthreads();
-      const double d = L.rowb[buf][t];
-      // 1/d by v_rcp_f64 + two Newton steps (<= 1 ulp): five dependent fp64
-      // operations on the chain's critical path instead of the eleven of
-      // the IEEE division sequence
-      double rd = __builtin_amdgcn_rcp(d);
-      double re = fma(-d, rd, 1.0);
-      rd = fma(rd, re, rd);
-      re = fma(-d, rd, 1.0);
-      rd = fma(rd, re, rd);
-      const double dit = L.colb[buf][lane];
-      double rt[CW];
-#pragma unroll
-      for (int q = 0; q < CW; q += 2) {
-        const double2 x = *reinterpret_cast<const double2 *>(&L.rowb[buf][CW * w + q]);
-        rt[q] = x.x;
-        rt[q + 1] = x.y;
-      }
-#pragma unroll
-      for (int q = 0; q < CW; ++q) {
-        const int j = CW * w + q;
-        const double dtj = rt[q];
-        double x;
-        if (lane == t) x = (j == t) ? -rd : dtj * rd;
-        else if (j == t) x = dit * rd;
-        else x = fma(-(dit * dtj), rd, v[q]);
-        v[q] = x;
-      }
-      if (tid == 0) L.pv[t] = d;
-    }
-  }
-  __syncthreads();
-}
-
-// ---------------------------------------------------------------- blocked pivot
-// The same 64x64 sweep as pivot_sweep<4> (same register layout in and out,
-// pivots into pv[]), blocked by 16 (ACE_PIVOT_BLK=1, default): the sweep
-// operator composes, so sweeping pivots 0..63 one by one equals four block
-// sweeps of the 16x16 diagonal blocks, each
-//   M_ss <- S = -D^-1 (D = M_ss),  M_sc <- D^-1 M_sc = -S M_sc,
-//   M_rc <- M_rc - M_rs D^-1 M_sc = M_rc + M_rs (S M_sc)   (r, c != s).
-// The 16 scalar pivots of M_ss run in ONE wave with no barrier and no LDS:
-// lane (r, g) = (lane & 15, lane >> 4) holds M(r, 4g .. 4g+3); pivot t's
-// row comes by a 64-bit DPP row_newbcast:t (lane t of every 16-lane row
-// holds row t's part of that row's columns) and its column by a
-// permlane16/32 swap pair that replicates row t/4 (the lanes holding
-// column t) into all four rows.  Every wave sweeps M_ss redundantly, so S
-// is in every wave's registers as the MFMA A operand (the k index of a
-// 16x16x4 step permuted to 4g + e, which needs no data movement); wave w !=
-// s then forms Un = S M_sw (4 MFMAs), writes M_sw = -Un (and its mirror
-// M_ws), and for c >= w, c != s updates M_cw += M_cs Un (4 MFMAs each, k
-// permuted to g + 4e so that Un's accumulator layout is the B operand as it
-// stands) and mirrors it: every off-diagonal block is formed once and
-// mirrored, every diagonal block from its lower triangle, so M stays exactly
-// symmetric as the scalar sweep keeps it.  Per 16 pivots ~35 VALU + 4
-// permlane + 5 DPP instructions per wave instead of 16 barriers and 64
-// columns of updates per row: the latency of the pivot chain's 64x64 sweep
-// (k_pivot 35 us alone, 93 us under the bulk update) is what this cuts.
-// M: the 64x64 matrix in LDS (pitch P, even, 16-B aligned rows).
-#ifndef ACE_PIVOT_BLK
-#define ACE_PIVOT_BLK 1
-#endif
 #ifndef ACE_BULK_RESERVE_N
 #define ACE_BULK_RESERVE_N 8192
-#endif
-#ifndef ACE_PGEMM_HEADQ
-#define ACE_PGEMM_HEADQ 1
 #endif
 
 // broadcast lane T of every 16-lane row to the row (64-bit DPP)
@@ -189,7 +129,10 @@ __device__ __forceinline__ void blk_pivot(double (&x)[4], int r, int g, double &
 #pragma unroll
   for (int e = 0; e < 4; ++e) rw[e] = row_bcast<T>(x[e]);
   const double d = row_bcast<T>(c);      // M(t, t)
-  double rd = __builtin_amdgcn_rcp(d);  // + two Newton steps, as in pivot_sweep
+  // 1/d by v_rcp_f64 + two Newton steps (<= 1 ulp): five dependent fp64
+  // operations on the chain's critical path instead of the eleven of the
+  // IEEE division sequence
+  double rd = __builtin_amdgcn_rcp(d);
   double re = fma(-d, rd, 1.0);
   rd = fma(rd, re, rd);
   re = fma(-d, rd, 1.0);
@@ -308,12 +251,10 @@ __device__ __forceinline__ void pivot_sweep_blk(double (&v)[SUB / 4], double (*M
 }
 
 // pivots (and the non-PD flag) and SW = -D^-1 out
-template <int NW>
-__device__ __forceinline__ void pivot_store(const double (&v)[SUB / NW], const double *pv,
-                                            int tid, double *__restrict__ SW,
-                                            double *__restrict__ piv, int64_t p0,
-                                            int *__restrict__ flag) {
-  constexpr int CW = SUB / NW;
+__device__ __forceinline__ void pivot_store(const double (&v)[SUB / 4], const double *pv, int tid,
+                                            double *__restrict__ SW, double *__restrict__ piv,
+                                            int64_t p0, int *__restrict__ flag) {
+  constexpr int CW = SUB / 4;
   const int lane = tid & 63, w = tid >> 6;
   if (tid < SUB) {
     const double d = pv[tid];
@@ -324,38 +265,33 @@ __device__ __forceinline__ void pivot_store(const double (&v)[SUB / NW], const d
   for (int q = 0; q < CW; ++q) SW[lane + (CW * w + q) * SUB] = v[q];
 }
 
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_pivot(const double *__restrict__ S, int s,
-                                                   double *__restrict__ SW,
-                                                   double *__restrict__ piv, int64_t p0,
-                                                   int *__restrict__ flag) {
+__global__ __launch_bounds__(256) void k_pivot(const double *__restrict__ S, int s,
+                                               double *__restrict__ SW,
+                                               double *__restrict__ piv, int64_t p0,
+                                               int *__restrict__ flag) {
   ACE_WGT(1, true);
   CHAIN_PRIO();
-  constexpr int CW = SUB / NW;
-  __shared__ PivotLds<NW> L;
+  constexpr int CW = SUB / 4;
+  __shared__ PivotLds L;
+  __shared__ double M[SUB][SUB + 2];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   double v[CW];
 #pragma unroll
   for (int q = 0; q < CW; ++q) v[q] = S[lane + (s * SUB + CW * w + q) * SUB];
   ACE_WGT_MARK(0);
-  if constexpr (ACE_PIVOT_BLK && NW == 4) {
-    __shared__ double M[SUB][SUB + 2];
-    pivot_sweep_blk<SUB + 2>(v, M, L.pv, tid);
-  } else {
-    pivot_sweep<NW>(v, L, tid);
-  }
+  pivot_sweep_blk<SUB + 2>(v, M, L.pv, tid);
   ACE_WGT_MARK(1);
-  pivot_store<NW>(v, L.pv, tid, SW, piv, p0, flag);
+  pivot_store(v, L.pv, tid, SW, piv, p0, flag);
 }
 
 static void launch_pivot(const double *S, int s, double *SW, double *piv, int64_t p0, int *flag,
                          hipStream_t st) {
-  hipLaunchKernelGGL(k_pivot<4>, dim3(1), dim3(256), 0, st, S, s, SW, piv, p0, flag);
+  hipLaunchKernelGGL(k_pivot, dim3(1), dim3(256), 0, st, S, s, SW, piv, p0, flag);
 }
 
 // ---------------------------------------------------------------- gather
-// P = -A[:, k] for every row; W = A[:, k] only on the pivot rows (k_panel
-// sweeps them; k_panel_gemm forms every other row of W from P).
+// P = -A[:, k] for every row; W = A[:, k] only on the pivot rows (the
+// panel chain sweeps them; the panel GEMM forms every other row of W from P).
 __global__ __launch_bounds__(256) void k_gather(const double *__restrict__ A, int64_t ld,
                                                 int64_t k0, double *__restrict__ P,
                                                 double *__restrict__ W, int64_t ldp,
@@ -396,7 +332,7 @@ __global__ __launch_bounds__(256) void k_gather(const double *__restrict__ A, in
       if (piv) W[i + (int64_t)(j0 + b) * ldp] = v;
     }
   }
-  if (i0 == k0) {  // pivot rows of sub-block 0: snapshot for k_pivot / k_panel
+  if (i0 == k0) {  // pivot rows of sub-block 0: snapshot for k_pivot / k_panel_split
     for (int e = tid; e < 4096; e += 256) {
       const int a = e & 63, b = e >> 6;
       S0[a + (int64_t)(j0 + b) * SUB] = W[(i0 + a) + (int64_t)(j0 + b) * ldp];
@@ -405,15 +341,33 @@ __global__ __launch_bounds__(256) void k_gather(const double *__restrict__ A, in
 }
 
 // ---------------------------------------------------------------- panel
-// Applies sub-pivot s to 64 rows of the panel W (Naug x NB), on MFMA:
+// Sub-step s applies sub-pivot s to the NB pivot rows of the panel W, on
+// MFMA (every other row of W comes from the panel GEMM afterwards):
 //   other rows : V = -W[:, s] SW (= W_is D_s^-1); W[:, s] = V;
 //                W[:, j] -= V S[:, j]            (j outside s)
 //   pivot rows : V = SW;  W[:, s] = SW;  W[:, j] = -SW S[:, j] (= D_s^-1 S)
-// Wave w owns rows 16w..16w+15.  Phase 1 forms Vn^T = -V^T = SW W_is^T
-// (SW is symmetric) so that its accumulator fragments are directly the B
-// operands of phase 2's D = S_chunk^T Vn^T + W_chunk^T (no LDS round trip).
+// Workgroup (g, cc) of (NB/SUB)^2 updates rows g (64) of the pivot block in
+// column chunk cc (64 columns); wave w owns rows 16w..16w+15.  Phase 1 forms
+// Vn^T = -V^T = SW W_is^T (SW is symmetric) so that its accumulator
+// fragments are directly the B operands of phase 2's D = S_chunk^T Vn^T +
+// W_chunk^T (no LDS round trip).  Sixteen small workgroups, where NB/SUB
+// that each walked every chunk lost: under the bulk update a chain
+// workgroup runs on a CU it shares with an update workgroup, so the chain's
+// latency is its per-workgroup work (profiles/r02_chain_ab.txt).  Phase 1
+// is recomputed by each workgroup of the row group, so its input W[:, s]
+// must not change during sub-step s:
+//   * sub-step s >= 1 reads it from X[s & 1], the copy of chunk s that the
+//     chunk-s workgroups of sub-step s-1 wrote beside W;
+//   * sub-step 0 reads W[:, 0] (the gathered panel) and writes its chunk 0
+//     (V) to V0 instead of W; sub-step 1 takes chunk 0's accumulator there.
+// X[0], X[1] and V0 are NB x SUB (row within the pivot block, column within
+// the chunk) after SW[0], SW[1] in the SW buffer.  The workgroup holding the
+// next diagonal block D_{s+1} (g = cc = s + 1) then runs k_pivot's sub-sweep
+// of sub-step s+1 on it (into SWn = the other SW buffer), which saves one
+// launch -- and its wait for a free CU slot under the bulk update -- per
+// sub-step.
 // LDS pitch for sSW: 64 + 16 doubles, conflict-free fragment reads
-// (ACE_PLD=72: the split kernel's LDS fits 72 KB, the hole one finished
+// (ACE_PLD=72: the kernel's LDS fits 72 KB, the hole one finished
 // bulk-update workgroup leaves -- A/B switch)
 #ifndef ACE_PLD
 #define ACE_PLD 80
@@ -421,112 +375,12 @@ __global__ __launch_bounds__(256) void k_gather(const double *__restrict__ A, in
 constexpr int PLD = ACE_PLD;
 constexpr int SLD = 66;  // LDS pitch for the transposed S chunk (c-major)
 
-__global__ __launch_bounds__(256) void k_panel(double *__restrict__ W, int64_t ldp, int64_t k0,
-                                               int s, const double *__restrict__ SW,
-                                               const double *__restrict__ S,
-                                               double *__restrict__ Snext, int64_t row0) {
-  CHAIN_PRIO();
-  __shared__ double sSW[SUB][PLD];  // sSW[b][a] = SW(a, b)
-  __shared__ double sSt[SUB][SLD];  // sSt[c][t] = S(t, 64 cc + c)
-  const int64_t i0 = row0 + (int64_t)blockIdx.x * SUB;
-  const bool pivrows = (i0 == k0 + (int64_t)s * SUB);
-  const bool nextrows = (s + 1 < NB / SUB) && (i0 == k0 + (int64_t)(s + 1) * SUB);
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int lr = lane & 15, lk = lane >> 4;
-  for (int e = tid; e < SUB * SUB; e += 256) {
-    const int a = e & 63, b = e >> 6;
-    sSW[b][a] = SW[a + b * SUB];
-  }
-  __syncthreads();
-  const int64_t row = i0 + 16 * w + lr;
-  const int srow = 16 * w + lr;  // row within the block (for Snext)
-  d4 acc1[4];
-  if (pivrows) {
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc1[ct][j] = -sSW[16 * ct + lk + 4 * j][16 * w + lr];
-  } else {
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) acc1[ct] = d4{0.0, 0.0, 0.0, 0.0};
-    double bw[SUB / 4];  // all 16 B fragments in flight at once
-#pragma unroll
-    for (int kk = 0; kk < SUB / 4; ++kk) bw[kk] = W[row + (int64_t)(s * SUB + 4 * kk + lk) * ldp];
-#pragma unroll
-    for (int kk = 0; kk < SUB / 4; ++kk) {
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct)
-        acc1[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(sSW[4 * kk + lk][16 * ct + lr], bw[kk],
-                                                        acc1[ct], 0, 0, 0);
-    }
-  }
-  // acc1[ct][j] = Vn[i = row][t' = 16 ct + lk + 4 j];  W[:, s] = V = -Vn
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int col = s * SUB + 16 * ct + lk + 4 * j;
-      W[row + (int64_t)col * ldp] = -acc1[ct][j];
-      if (nextrows) Snext[srow + col * SUB] = -acc1[ct][j];
-    }
-  for (int cc = 0; cc < NB / SUB; ++cc) {
-    if (cc == s) continue;
-    // issue this chunk's accumulator loads before the staging barrier
-    d4 accs[4];
-#pragma unroll
-    for (int ctc = 0; ctc < 4; ++ctc)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        accs[ctc][j] = pivrows ? 0.0 : W[row + (int64_t)(cc * SUB + 16 * ctc + lk + 4 * j) * ldp];
-    __syncthreads();
-    for (int e = tid; e < SUB * SUB; e += 256) {
-      const int t = e & 63, c = e >> 6;
-      sSt[c][t] = S[t + (cc * SUB + c) * SUB];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ctc = 0; ctc < 4; ++ctc) {
-      d4 acc = accs[ctc];
-#pragma unroll
-      for (int kk = 0; kk < SUB / 4; ++kk)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sSt[16 * ctc + lr][4 * kk + lk],
-                                                   acc1[kk >> 2][kk & 3], acc, 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int col = cc * SUB + 16 * ctc + lk + 4 * j;
-        W[row + (int64_t)col * ldp] = acc[j];
-        if (nextrows) Snext[srow + col * SUB] = acc[j];
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------- split panel
-// k_panel's arithmetic with the column chunks spread over workgroups:
-// workgroup (g, cc) updates rows g (64) of the pivot block in chunk cc (64
-// columns) only -- (NB/SUB)^2 small workgroups instead of NB/SUB that each
-// walk every chunk.  Under the bulk update a chain workgroup runs on a CU it
-// shares with an update workgroup, so the chain's latency is its
-// per-workgroup work (profiles/r02_chain_ab.txt).  Phase 1 (Vn for the
-// rows) is recomputed by each workgroup of the row group, so its input
-// W[:, s] must not change during sub-step s:
-//   * sub-step s >= 1 reads it from X[s & 1], the copy of chunk s that the
-//     chunk-s workgroups of sub-step s-1 wrote beside W;
-//   * sub-step 0 reads W[:, 0] (the gathered panel) and writes its chunk 0
-//     (V) to V0 instead of W; sub-step 1 takes chunk 0's accumulator there.
-// X[0], X[1] and V0 are NB x SUB (row within the pivot block, column within
-// the chunk) after SW[0], SW[1] in the SW buffer.  The workgroup holding the
-// next diagonal block D_{s+1} (g = cc = s + 1) then runs the k_pivot
-// sub-sweep of sub-step s+1 on it (into SWn = the other SW buffer), which
-// saves one launch -- and its wait for a free CU slot under the bulk update
-// -- per sub-step.  Every element sees k_panel's / k_pivot's operations in
-// their order: bit-identical.
 template <class Mark>
 __device__ __forceinline__ void panel_split_step(
     double *__restrict__ W, int64_t ldp, int64_t k0, int s, const double *__restrict__ SW,
     const double *__restrict__ S, double *__restrict__ Snext, double *__restrict__ Xb,
     double *__restrict__ SWn, double *__restrict__ piv, int *__restrict__ flag,
-    double (&sSW)[SUB][PLD], double (&sSt)[SUB][SLD], PivotLds<4> &PL, int g, int cc,
+    double (&sSW)[SUB][PLD], double (&sSt)[SUB][SLD], PivotLds &PL, int g, int cc,
     const Mark &mark) {
   // sSW[b][a] = SW(a, b); sSt[c][t] = S(t, 64 cc + c)
   constexpr int NS = NB / SUB;
@@ -648,15 +502,10 @@ __device__ __forceinline__ void panel_split_step(
   double v[SUB / 4];
 #pragma unroll
   for (int q = 0; q < SUB / 4; ++q) v[q] = sSW[16 * w + q][lane];
-#if ACE_PIVOT_BLK
   mark(2);
   pivot_sweep_blk<SLD>(v, sSt, PL.pv, tid);  // sSt is free (the update phase is done)
-#else
-  mark(2);
-  pivot_sweep<4>(v, PL, tid);
-#endif
   mark(3);
-  pivot_store<4>(v, PL.pv, tid, SWn, piv, k0 + (int64_t)(s + 1) * SUB, flag);
+  pivot_store(v, PL.pv, tid, SWn, piv, k0 + (int64_t)(s + 1) * SUB, flag);
 }
 
 
@@ -673,14 +522,15 @@ __global__ __launch_bounds__(256) void k_panel_split(double *__restrict__ W, int
   CHAIN_PRIO();
   __shared__ double sSW[SUB][PLD];
   __shared__ double sSt[SUB][SLD];
-  __shared__ PivotLds<4> PL;
+  __shared__ PivotLds PL;
   auto mark = [&](int i) { (void)i; ACE_WGT_MARK(i); };
   panel_split_step(W, ldp, k0, s, SW, S, Snext, Xb, SWn, piv, flag, sSW, sSt, PL, (int)blockIdx.x,
                    (int)blockIdx.y, mark);
 }
 
-// The four sub-steps of the split panel sweep in ONE launch (ACE_CHAIN_FUSE,
-// small n): the same 16 workgroups run sub-step s = 0 .. 3, each the
+// The four sub-steps of the split panel sweep in ONE launch (small n, the
+// bulk-queue schedule: C1 3.60 -> 3.52 ms against four k_panel_split
+// launches, profiles/r06_chain_fuse_ab.txt): the same 16 workgroups run sub-step s = 0 .. 3, each the
 // workgroup (g, cc) of k_panel_split's grid, with a grid barrier between the
 // sub-steps instead of a launch boundary -- every workgroup keeps its CU slot
 // across the chain, and the next sub-step's workgroups do not wait for a
@@ -725,7 +575,7 @@ __global__ __launch_bounds__(256, 2) void k_panel_split4(double *__restrict__ W,
   CHAIN_PRIO();
   __shared__ double sSW[SUB][PLD];
   __shared__ double sSt[SUB][SLD];
-  __shared__ PivotLds<4> PL;
+  __shared__ PivotLds PL;
   auto mark = [&](int i) { (void)i; ACE_WGT_MARK(i); };
   static_assert(NB / SUB == 4, "four sub-steps");
   double *const Xb = SW + 2 * SUB * SUB, *const SW1 = SW + SUB * SUB;
@@ -748,78 +598,6 @@ __global__ __launch_bounds__(256, 2) void k_panel_split4(double *__restrict__ W,
     __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(ctr + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-}
-
-// ---------------------------------------------------------------- panel GEMM
-// After the four sub-sweeps restricted to the pivot rows, W[k0:k0+NB, :]
-// holds W_kk = -D^-1 (symmetric).  Every other row of the panel is then one
-// GEMM:  W_i = A_ik D^-1 = Pn_i W_kk  (Pn = -P).  Computed transposed,
-// Out^T[c][i] = sum_k W_kk[c][k] Pn[i][k], so that fragment lanes walk
-// consecutive rows of W.  64 rows x NB columns per 512-thread workgroup,
-// 8 waves = 4 row strips x 2 column halves, 8 MFMA fragments each.
-constexpr int GBKP = 8;            // k per LDS stage
-constexpr int GLB = NB + 16;       // pitch of the W_kk stage  [k][c]
-constexpr int GLA = SUB + 16;      // pitch of the Pn stage    [k][i]
-
-// Sharded model (G > 1): rank r forms W only for the rows it consumes -- the
-// rows of its own column blocks (operand of its update tiles) and, on the
-// owner of block k, every row >= k0 (written back into column block k).
-__global__ __launch_bounds__(512) void k_panel_gemm(double *__restrict__ W,
-                                                    const double *__restrict__ Pn, int64_t ldp,
-                                                    int64_t k0, int G, int r) {
-  __shared__ __attribute__((aligned(16))) double sB[2][GBKP][GLB];
-  __shared__ __attribute__((aligned(16))) double sA[2][GBKP][GLA];
-  const int64_t i0 = (int64_t)blockIdx.x * SUB;
-  if (i0 >= k0 && i0 < k0 + NB) return;  // pivot rows are already final
-  if (G > 1 && !owns_col(i0, G, r) && !(owns_col(k0, G, r) && i0 >= k0)) return;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int wi = wv & 3, wc = wv >> 2;
-  const int lr = lane & 15, lk = lane >> 4;
-  constexpr int CT = NB / 2 / 16;  // c-tiles per wave
-  d4 acc[CT];
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct) acc[ct] = d4{0.0, 0.0, 0.0, 0.0};
-  // staging maps: B: 8 k x NB c  (NB/128 double2 per thread); A: 8 k x 64 i (1 per thread)
-  const int bk = tid >> 6, bc = (tid & 63) * (NB / 64);
-  const int ak = tid >> 6, ai = tid & 63;
-  constexpr int NBQ = NB / 128;  // double2 per thread for the B stage
-  double2 rb[NBQ];
-  double ra;
-  auto load = [&](int kc) {
-#pragma unroll
-    for (int e = 0; e < NBQ; ++e)
-      rb[e] = *reinterpret_cast<const double2 *>(W + (k0 + bc + 2 * e) + (int64_t)(kc + bk) * ldp);
-    ra = Pn[(i0 + ai) + (int64_t)(kc + ak) * ldp];
-  };
-  auto store = [&](int buf) {
-#pragma unroll
-    for (int e = 0; e < NBQ; ++e) *reinterpret_cast<double2 *>(&sB[buf][bk][bc + 2 * e]) = rb[e];
-    sA[buf][ak][ai] = ra;
-  };
-  load(0);
-  store(0);
-  __syncthreads();
-  constexpr int NCHP = NB / GBKP;
-  for (int ch = 0; ch < NCHP; ++ch) {
-    const int cur = ch & 1;
-    if (ch + 1 < NCHP) load((ch + 1) * GBKP);
-#pragma unroll
-    for (int kk = 0; kk < GBKP / 4; ++kk) {
-      const double b = sA[cur][4 * kk + lk][16 * wi + lr];
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct)
-        acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(
-            sB[cur][4 * kk + lk][(NB / 2) * wc + 16 * ct + lr], b, acc[ct], 0, 0, 0);
-    }
-    if (ch + 1 < NCHP) store(cur ^ 1);
-    __syncthreads();
-  }
-  const int64_t row = i0 + 16 * wi + lr;
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      W[row + (int64_t)((NB / 2) * wc + 16 * ct + lk + 4 * j) * ldp] = acc[ct][j];
 }
 
 // ---------------------------------------------------------------- update
@@ -860,7 +638,7 @@ static_assert(BK == 16, "staging maps 512 threads x 4 doubles onto a 128 x 16 ch
 __device__ __forceinline__ void st_a(double *p, double v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ double ld_a(const double *p) { return __builtin_nontemporal_load(p); }
 
-// Gather fused into a lookahead cross launch (ACE_XGATHER): the cross tiles
+// Gather fused into a lookahead launch: the cross tiles
 // of block kg are exactly the lower tiles holding column block kg of the
 // symmetric matrix, so the launch that writes them can also write what
 // k_gather would read back from them -- P = -A[:, kg], W = A[:, kg] on the
@@ -1124,13 +902,19 @@ __global__ __launch_bounds__(UTHREADS, 2) void k_update(double *__restrict__ A, 
   }
 }
 
-// Panel GEMM on the update kernel's 128 x 128 tiles (ACE_PGEMM_TILES, the
-// default): W_I,J = Pn_I W_kk[:, J] for the two 128-column halves J of the
-// panel, K = NB.  Same operand roles, k order and zero start as
-// k_panel_gemm, so bit-identical to it, but each workgroup runs the bulk
-// update's pipelined 8-wave tile: under the bulk update k_panel_gemm's 64-row
-// strips held 258 update-sized CU slots for ~185 us per panel (skipping it
-// took 6 ms off a C2 evaluation, profiles/r02_chain_ab.txt).
+// ---------------------------------------------------------------- panel GEMM
+// After the four sub-sweeps restricted to the pivot rows, W[k0:k0+NB, :]
+// holds W_kk = -D^-1 (symmetric).  Every other row of the panel is then one
+// GEMM:  W_i = A_ik D^-1 = Pn_i W_kk  (Pn = -P), started from zero.
+// Computed transposed, Out^T[c][i] = sum_k W_kk[c][k] Pn[i][k], so that
+// fragment lanes walk consecutive rows of W.  One 128 x 128 tile (row tile,
+// 128-column half J of the panel), K = NB, per workgroup on the bulk update's
+// pipelined 8-wave tile: under the bulk update 64-row strips of 512 threads
+// held 258 update-sized CU slots for ~185 us per panel (skipping them took
+// 6 ms off a C2 evaluation, profiles/r02_chain_ab.txt).
+// Sharded model (G > 1): rank r forms W only for the rows it consumes -- the
+// rows of its own column blocks (operand of its update tiles) and, on the
+// owner of block k, every row >= k0 (written back into column block k).
 __global__ __launch_bounds__(UTHREADS, 2) void k_panel_gemm_t(double *__restrict__ W,
                                                               const double *__restrict__ Pn,
                                                               int64_t ldp, int64_t k0, int G,
@@ -1221,219 +1005,8 @@ __global__ __launch_bounds__(UTHREADS, 2) void k_panel_gemm_t(double *__restrict
     }
 }
 
-// Two sweep steps per launch: A_IJ += W_a,I Pn_a,J^T + W_b,I Pn_b,J^T with
-// panels a (block [ka0, ka0 + NB)) and b = a + 1 (the next block), K = 2 NB
-// per tile -- every accumulator runs the same MFMA chain over the same k
-// order as two k_update launches (acc stored / reloaded in fp64 between
-// them), so the results are bit-identical, while the C tile is read and
-// written once per two steps.  Tiles of block b take W_b (k_update's copy);
-// tiles of block a take W_a (what step a left there) and then only panel b's
-// product; tiles with I or J in blocks [kx0, kx1) (the lookahead cross,
-// updated on the side stream) are skipped.  Sharded (G > 1 or wcol): A's
-// columns are block-cyclic (lcol) and the operands swapped (R = Pn, C = W).
-__device__ __forceinline__ void update_pair_tile(
-    int I, int J, double (&sW)[2][BK][LDL], double (&sP)[2][BK][LDL], double *__restrict__ A,
-    int64_t ld, const double *__restrict__ Ra, const double *__restrict__ Ca,
-    const double *__restrict__ Rb, const double *__restrict__ Cb, int64_t ldp, int64_t ka0,
-    const GatherOut &go, int G, bool wcol) {
-  constexpr int KT = NB / UT;
-  const int64_t kb0 = ka0 + NB;
-  const int ta0 = (int)(ka0 / UT), tb0 = ta0 + KT;
-  const bool Ia = I >= ta0 && I < tb0, Ja = J >= ta0 && J < tb0;
-  const bool Ib = I >= tb0 && I < tb0 + KT, Jb = J >= tb0 && J < tb0 + KT;
-  const int64_t R0 = (int64_t)I * UT, C0 = (int64_t)J * UT;
-  const int64_t L0 = lcol(C0, G);  // A's local column of the tile (sharded: block-cyclic)
-  const int tid = threadIdx.x;
-  // single GPU: R = W, C = Pn; sharded (wcol): R = Pn, C = W (own columns)
-  const double *Wa = wcol ? Ca : Ra, *Wb = wcol ? Cb : Rb;
-
-  if (Ib || Jb) {  // block b holds W_b after the pair
-    if (Ib && !Jb) {
-      double *tileT = &sW[0][0][0];  // 64 x 65 scratch
-      for (int sa = 0; sa < 2; ++sa)
-        for (int sb = 0; sb < 2; ++sb) {
-          __syncthreads();
-          for (int e = tid; e < 4096; e += UTHREADS) {
-            const int c = e & 63, a = e >> 6;
-            tileT[a * 65 + c] = Wb[(C0 + 64 * sb + c) + (R0 - kb0 + 64 * sa + a) * ldp];
-          }
-          __syncthreads();
-          for (int e = tid; e < 4096; e += UTHREADS) {
-            const int a = e & 63, c = e >> 6;
-            const double v = tileT[a * 65 + c];
-            A[(R0 + 64 * sa + a) + (L0 + 64 * sb + c) * ld] = v;
-            if (go.k0 >= 0) gput(go, R0 + 64 * sa + a, C0 + 64 * sb + c, v);
-          }
-        }
-    } else {
-      for (int e = tid; e < UT * UT; e += UTHREADS) {
-        const int a = e & (UT - 1), c = e >> 7;
-        const double v = Wb[(R0 + a) + (C0 - kb0 + c) * ldp];
-        A[(R0 + a) + (L0 + c) * ld] = v;
-        if (go.k0 >= 0) gput(go, R0 + a, C0 + c, v);
-      }
-    }
-    return;
-  }
-  // block a (not b): the tile starts from W_a and gets panel b only
-  const bool from_w = Ia || Ja;
-  // W_a at (row r, column c) of such a tile: column block a (and the
-  // diagonal block) W_a[r, c - ka0]; row block a W_a[c, r - ka0] (transposed)
-  const int64_t wrs = Ja ? 1 : ldp, wcs = Ja ? ldp : 1;  // strides of r, c
-  const double *wab = Ja ? Wa - ka0 * ldp : Wa - ka0 * ldp;  // (r, c) -> wab[r wrs + c wcs]
-
-  const int lane = tid & 63, wv = tid >> 6;
-  const int lr = lane & 15, lk = lane >> 4;
-  if (R0 >= ld - AUG) {  // AUG row block: 16 live rows (as k_update)
-    d4 acc;
-    const int64_t r = R0 + lr;
-    const int64_t c = C0 + 16 * wv + lk, lc = L0 + 16 * wv + lk;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      acc[j] = from_w ? wab[r * wrs + (c + 4 * j) * wcs] : ld_a(&A[r + (lc + 4 * j) * ld]);
-    for (int pnl = from_w ? 1 : 0; pnl < 2; ++pnl) {
-      const double *gr = (pnl ? Rb : Ra) + R0 + lr + (int64_t)lk * ldp;
-      const double *gc = (pnl ? Cb : Ca) + C0 + 16 * wv + lr + (int64_t)lk * ldp;
-      double an = gc[0], bn = gr[0];
-      for (int kk = 0; kk < NB / 4; ++kk) {
-        const double a = an, bb = bn;
-        if (kk + 1 < NB / 4) {
-          an = gc[(int64_t)(4 * (kk + 1)) * ldp];
-          bn = gr[(int64_t)(4 * (kk + 1)) * ldp];
-        }
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bb, acc, 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) st_a(&A[r + (lc + 4 * j) * ld], acc[j]);
-    if (go.k0 >= 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) gput(go, r, c + 4 * j, acc[j]);
-      gput_aug_dead(go, A, ld, R0, C0, tid, UTHREADS, L0);
-    }
-    return;
-  }
-  const int sk = tid >> 5, sm = (tid & 31) * 4;  // (the split mapping costs this kernel 12 VGPRs)
-  // 32-bit element offsets from the (scalar) panel bases: the loads take a
-  // scalar base + vector offset (no 64-bit address VGPRs; -1 ms per C2
-  // evaluation, profiles/r03_v4_group_ab.txt)
-  const int roff = (int)((R0 + sm) + (int64_t)sk * ldp), coff = (int)((C0 + sm) + (int64_t)sk * ldp);
-  double2 rw0, rw1, rp0, rp1;
-  {
-    const double *w = (from_w ? Rb : Ra) + roff, *pp = (from_w ? Cb : Ca) + coff;
-    rw0 = *reinterpret_cast<const double2 *>(w);
-    rw1 = *reinterpret_cast<const double2 *>(w + 2);
-    rp0 = *reinterpret_cast<const double2 *>(pp);
-    rp1 = *reinterpret_cast<const double2 *>(pp + 2);
-  }
-  __builtin_amdgcn_sched_barrier(0);  // keep the C-tile loads behind them
-  const int wr = wv & 1, wc = wv >> 1;
-  d4 acc[2][4];
-#pragma unroll
-  for (int ci = 0; ci < 2; ++ci)
-#pragma unroll
-    for (int ri = 0; ri < 4; ++ri) {
-      const int64_t r = R0 + 64 * wr + 16 * ri + lr;
-      const int64_t c = C0 + 32 * wc + 16 * ci + lk, lc = L0 + 32 * wc + 16 * ci + lk;
-      if (from_w) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[ci][ri][j] = wab[r * wrs + (c + 4 * j) * wcs];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[ci][ri][j] = ld_a(&A[r + (lc + 4 * j) * ld]);
-      }
-    }
-  *reinterpret_cast<double2 *>(&sW[0][sk][sm]) = rw0;
-  *reinterpret_cast<double2 *>(&sW[0][sk][sm + 2]) = rw1;
-  *reinterpret_cast<double2 *>(&sP[0][sk][sm]) = rp0;
-  *reinterpret_cast<double2 *>(&sP[0][sk][sm + 2]) = rp1;
-  __syncthreads();
-  // chunk ch of segment seg (0: panel a, 1: panel b) uses LDS buffer ch & 1
-  // (NCH is even, so the parity runs on across the two segments)
-  for (int seg = from_w ? 1 : 0; seg < 2; ++seg) {
-    const double *sw = seg ? Rb : Ra, *sp = seg ? Cb : Ca;
-    for (int ch = 0; ch < NCH; ++ch) {
-      const int cur = ch & 1;
-      const bool more = ch + 1 < NCH || seg == 0;
-      if (more) {
-        const double *nw = (ch + 1 < NCH ? sw + (int64_t)(ch + 1) * BK * ldp : Rb) + roff;
-        const double *np = (ch + 1 < NCH ? sp + (int64_t)(ch + 1) * BK * ldp : Cb) + coff;
-        rw0 = *reinterpret_cast<const double2 *>(nw);
-        rw1 = *reinterpret_cast<const double2 *>(nw + 2);
-        rp0 = *reinterpret_cast<const double2 *>(np);
-        rp1 = *reinterpret_cast<const double2 *>(np + 2);
-      }
-#pragma unroll
-      for (int kk = 0; kk < BK / 4; ++kk) {
-        double a[2], b[4];
-#pragma unroll
-        for (int ci = 0; ci < 2; ++ci) a[ci] = sP[cur][4 * kk + lk][32 * wc + 16 * ci + lr];
-#pragma unroll
-        for (int ri = 0; ri < 4; ++ri) b[ri] = sW[cur][4 * kk + lk][64 * wr + 16 * ri + lr];
-#pragma unroll
-        for (int ci = 0; ci < 2; ++ci)
-#pragma unroll
-          for (int ri = 0; ri < 4; ++ri)
-            acc[ci][ri] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ci], b[ri], acc[ci][ri], 0, 0, 0);
-      }
-      if (more) {
-        *reinterpret_cast<double2 *>(&sW[cur ^ 1][sk][sm]) = rw0;
-        *reinterpret_cast<double2 *>(&sW[cur ^ 1][sk][sm + 2]) = rw1;
-        *reinterpret_cast<double2 *>(&sP[cur ^ 1][sk][sm]) = rp0;
-        *reinterpret_cast<double2 *>(&sP[cur ^ 1][sk][sm + 2]) = rp1;
-      }
-      __syncthreads();
-    }
-  }
-#pragma unroll
-  for (int ci = 0; ci < 2; ++ci)
-#pragma unroll
-    for (int ri = 0; ri < 4; ++ri) {
-      const int64_t r = R0 + 64 * wr + 16 * ri + lr;
-      const int64_t lc = L0 + 32 * wc + 16 * ci + lk;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) st_a(&A[r + (lc + 4 * j) * ld], acc[ci][ri][j]);
-    }
-  if (go.k0 >= 0) {
-#pragma unroll
-    for (int ci = 0; ci < 2; ++ci)
-#pragma unroll
-      for (int ri = 0; ri < 4; ++ri)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          gput(go, R0 + 64 * wr + 16 * ri + lr, C0 + 32 * wc + 16 * ci + lk + 4 * j, acc[ci][ri][j]);
-  }
-}
-
-// Two sweep steps per launch on a tile list (skip rule [kx0, kx1), gather
-// go on every tile).
-__global__ __launch_bounds__(UTHREADS, 2) void k_update_pair(
-    double *__restrict__ A, int64_t ld, const double *__restrict__ Ra,
-    const double *__restrict__ Ca, const double *__restrict__ Rb, const double *__restrict__ Cb,
-    int64_t ldp, int64_t ka0, int kx0, int kx1, const Tile *__restrict__ tiles, GatherOut go,
-    int G, int wcol) {
-  __shared__ __attribute__((aligned(16))) double sW[2][BK][LDL];
-  __shared__ __attribute__((aligned(16))) double sP[2][BK][LDL];
-  constexpr int KT = NB / UT;
-  int I, J;
-  if (tiles) {
-    const Tile tt = tiles[blockIdx.x];
-    I = tt.I;
-    J = tt.J;
-    if (I < 0) return;  // padding of the XCD order
-  } else {
-    const int t = blockIdx.x;
-    int i = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((i + 1) * (i + 2) / 2 <= t) ++i;
-    while (i * (i + 1) / 2 > t) --i;
-    I = i;
-    J = t - i * (i + 1) / 2;
-  }
-  if (kx0 >= 0 && ((I >= kx0 * KT && I < kx1 * KT) || (J >= kx0 * KT && J < kx1 * KT))) return;
-  update_pair_tile(I, J, sW, sP, A, ld, Ra, Ca, Rb, Cb, ldp, ka0, go, G, wcol != 0);
-}
-
-// Z sweep steps per launch (sweep_group() = 3 or 4; k_update_pair is Z = 2):
+// Several sweep steps per launch (up to Z = sweep_group_n(), 2 .. 4), so that
+// the C tile is read and written once per group of steps:
 // npan panels j = 0 .. npan-1 of blocks ka0 / NB + j, operands R[j] = W_j,
 // C[j] = Pn_j (single GPU), K = npan NB per tile.  A tile whose row or
 // column lies in one of those blocks is overwritten by the step of the
@@ -1742,10 +1315,8 @@ __global__ __launch_bounds__(UTHREADS, 2) void k_update_multi_r(double *__restri
   }
 }
 
-// CUs per shader engine a small-n bulk launch leaves to the panel chains
-// (k_update_multi_r): ACE_BULK_RESERVE (0 .. 2) overrides; default 1 up to
-// n = ACE_BULK_RESERVE_N, none above (there the bulk launches are the
-// critical path and need every CU).
+// The two regimes of run_sweep_heads (declarations: ace_internal.h), small n
+// up to n = ACE_BULK_RESERVE_N unless overridden
 bool q_first(int64_t naug) {
   static const int v = env_set("ACE_QFIRST") ? env_int("ACE_QFIRST", 0) != 0 : -1;
   if (v >= 0) return v != 0;
@@ -1889,7 +1460,7 @@ __global__ __launch_bounds__(256) void k_update_x(double *__restrict__ A, int64_
 // The latency-critical launches of the head path (run_sweep_heads) work on
 // QT x QT pieces of the 128-tiles, one per 256-thread workgroup: QT = 64, a
 // quarter (each wave 32 x 32, k_update_x's MFMA chain), or QT = 32
-// (ACE_QSPLIT, small n), a quarter of a quarter (each wave one 16 x 16 MFMA
+// (small n, the bulk-queue schedule), a quarter of a quarter (each wave one 16 x 16 MFMA
 // block): four times the workgroups, a quarter of each one's K loop.  Every
 // element's MFMA chain (operands, k order, accumulator start) is that of the
 // 128-tile kernels at either width: bit-identical.
@@ -2045,7 +1616,7 @@ __device__ __forceinline__ void update_q(double *__restrict__ A, int64_t ld, con
   // them as 64-bit arguments, and behind a closure's reference their range
   // (a 32-bit tile index times UT) is hidden from the interprocedural
   // constant propagation, which then gives every gput user -- k_update,
-  // k_update_pair, k_update_multi* -- the 64-bit form of lcol's division
+  // k_update_multi* -- the 64-bit form of lcol's division
   q_pipeline<QT>(
       acc, sW, sP, npan * NCH,
       [=](int t) {
@@ -2107,7 +1678,7 @@ __device__ __forceinline__ void update_q(double *__restrict__ A, int64_t ld, con
   ACE_WGT_MARK(1);
   pivot_sweep_blk<SUB + 2>(v, M, pv, tid);
   ACE_WGT_MARK(2);
-  pivot_store<4>(v, pv, tid, pivSW, piv, go.k0, flag);
+  pivot_store(v, pv, tid, pivSW, piv, go.k0, flag);
 }
 __global__ __launch_bounds__(256, 4) void k_update_q(double *__restrict__ A, int64_t ld, PanelSet ps,
                                                   int npan, int64_t ldp,
@@ -2263,95 +1834,66 @@ __global__ __launch_bounds__(256) void k_unpack_panel(const double *__restrict__
   }
 }
 
-// Pivot block sweep (4 x 64-column sub-sweeps, pivots -> piv / flag) and the
-// panel GEMM for the rows rank r consumes.  W's pivot rows and S[0] must
-// hold the panel's pivot rows.
-// ACE_CHAIN=0 selects the row-group k_panel (A/B switch; k_panel_split is
-// the default and bit-identical).
-static bool panel_split() {
-  static const bool v = env_int("ACE_CHAIN", 1) != 0;
-  return v;
-}
-
-// ACE_CHAIN_FUSE=1 (default): at small n (the bulk-reserve schedule) each
-// panel's four split sub-steps run as one k_panel_split4 launch
-// (bit-identical; C1 3.60 -> 3.52 ms, profiles/r06_chain_fuse_ab.txt); 0: four
-// k_panel_split launches
-static bool chain_fuse() {
-  static const bool v = env_int("ACE_CHAIN_FUSE", 1) != 0;
-  return v;
-}
-
-// ACE_PGEMM_TILES=0 selects the 64-row k_panel_gemm (A/B switch; the tile
-// form k_panel_gemm_t is the default and bit-identical)
-static bool pgemm_tiles() {
-  static const bool v = env_int("ACE_PGEMM_TILES", 1) != 0;
-  return v;
-}
-
 // ACE_DIAG_SKIP (compile-time, timing diagnostics only -- the results are
 // wrong): bit 1 skips the pivot sub-sweeps and panel updates, bit 2 the panel
 // GEMM
 #ifndef ACE_DIAG_SKIP
 #define ACE_DIAG_SKIP 0
 #endif
+
+// k_panel_split4 may be launched with `bytes` of dynamic LDS on the current
+// device.  The attribute is per device: it is requested once per device and
+// size (device_cu_count's cache).  false: not granted.
+static bool chain_xlds_granted(unsigned bytes) {
+  static unsigned granted[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  if (granted[dev] != bytes) {
+    if (hipFuncSetAttribute((const void *)k_panel_split4, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)bytes) != hipSuccess) {
+      (void)hipGetLastError();  // not the launches' error
+      return false;
+    }
+    granted[dev] = bytes;
+  }
+  return true;
+}
+
+// Pivot block sweep (4 x 64-column sub-sweeps, pivots -> piv / flag) and the
+// panel GEMM for the rows rank r consumes.  W's pivot rows and S[0] must
+// hold the panel's pivot rows.
 // pivot0: sub-block 0 was already swept (by the k_update_q launch that
-// gathered the panel); fuse_ctr (small n, ACE_CHAIN_FUSE): the four split
-// sub-steps in one k_panel_split4 launch, its grid barrier on *fuse_ctr
+// gathered the panel); fuse_ctr (small n): the four split sub-steps in one
+// k_panel_split4 launch, its grid barrier on *fuse_ctr, with xlds bytes of
+// extra LDS (placement only; without them where the device does not grant them)
 static void panel_chain(const double *Pn, double *W, int64_t ld, int64_t k0, double *SW,
                         double *const S[2], double *piv, int *flag, int G, int r,
                         hipStream_t st, bool pivot0 = false, bool no_gemm = false,
                         int *fuse_ctr = nullptr, unsigned xlds = 0) {
-  const bool split = panel_split();
   double *const SWb[2] = {SW, SW + SUB * SUB};  // ping-pong by sub-step
-  if (split && fuse_ctr && !(ACE_DIAG_SKIP & 1)) {
+  if (!(ACE_DIAG_SKIP & 1)) {
     if (!pivot0) launch_pivot(S[0], 0, SWb[0], piv, k0, flag, st);
-    if (xlds) {
-      static unsigned set = 0;
-      if (set != xlds && hipFuncSetAttribute((const void *)k_panel_split4,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)xlds) == hipSuccess)
-        set = xlds;
+    if (fuse_ctr) {
+      if (xlds && !chain_xlds_granted(xlds)) xlds = 0;
+      hipLaunchKernelGGL(k_panel_split4, dim3(NB / SUB, NB / SUB), dim3(256), xlds, st, W, ld, k0,
+                         SW, S[0], S[1], piv, flag, fuse_ctr);
+    } else {
+      for (int s = 0; s < NB / SUB; ++s)
+        hipLaunchKernelGGL(k_panel_split, dim3(NB / SUB, NB / SUB), dim3(256), 0, st, W, ld, k0, s,
+                           SWb[s & 1], S[s & 1], S[(s + 1) & 1], SW + 2 * SUB * SUB,
+                           SWb[(s + 1) & 1], piv, flag);
     }
-    hipLaunchKernelGGL(k_panel_split4, dim3(NB / SUB, NB / SUB), dim3(256), xlds, st, W, ld, k0, SW,
-                       S[0], S[1], piv, flag, fuse_ctr);
-  }
-  for (int s = 0; s < ((ACE_DIAG_SKIP & 1) || (split && fuse_ctr) ? 0 : NB / SUB); ++s) {
-    if (!split || (s == 0 && !pivot0))
-      launch_pivot(S[s & 1], s, SWb[s & 1], piv, k0 + (int64_t)s * SUB, flag, st);
-    if (split)
-      hipLaunchKernelGGL(k_panel_split, dim3(NB / SUB, NB / SUB), dim3(256), 0, st, W, ld, k0, s,
-                         SWb[s & 1], S[s & 1], S[(s + 1) & 1], SW + 2 * SUB * SUB,
-                         SWb[(s + 1) & 1], piv, flag);
-    else
-      hipLaunchKernelGGL(k_panel, dim3(NB / SUB), dim3(256), 0, st, W, ld, k0, s, SWb[s & 1],
-                         S[s & 1], S[(s + 1) & 1], k0);
   }
   if ((ACE_DIAG_SKIP & 2) || no_gemm) return;
-  if (pgemm_tiles())
-    hipLaunchKernelGGL(k_panel_gemm_t, dim3((unsigned)(ld / UT), NB / UT), dim3(UTHREADS), 0, st,
-                       W, Pn, ld, k0, G, r, 0, 1 << 30, 1 << 30);
-  else
-    hipLaunchKernelGGL(k_panel_gemm, dim3((unsigned)(ld / SUB)), dim3(512), 0, st, W, Pn, ld, k0,
-                       G, r);
+  hipLaunchKernelGGL(k_panel_gemm_t, dim3((unsigned)(ld / UT), NB / UT), dim3(UTHREADS), 0, st, W,
+                     Pn, ld, k0, G, r, 0, 1 << 30, 1 << 30);
 }
 
-// ACE_XGATHER: pair steps fuse each panel's gather into the lookahead cross
-// launch that writes its column block (GatherOut; default 1)
-static bool xgather() {
-  static const bool v = env_int("ACE_XGATHER", 1) != 0;
-  return v;
-}
-
-// gathered: P, W and S[0] of this panel were written by the cross launch
-static hipError_t panel_sweep(const SweepBufs &b, int buf, int64_t k0, hipStream_t st,
-                              bool gathered = false) {
-  const int64_t naug = b.ld;
-  if (!gathered)
-    hipLaunchKernelGGL(k_gather, dim3((unsigned)(naug / 64), NB / 64), dim3(256), 0, st, b.A, b.ld,
-                       k0, b.P[buf], b.W[buf], b.ld, b.S[0]);
-  // sweep the NB x NB pivot block in place, then every other panel row:
-  // W_i = Pn_i W_kk
+// one panel of the one-step schedule: gather, sweep the NB x NB pivot block
+// in place, then every other panel row W_i = Pn_i W_kk
+static hipError_t panel_sweep(const SweepBufs &b, int buf, int64_t k0, hipStream_t st) {
+  hipLaunchKernelGGL(k_gather, dim3((unsigned)(b.ld / 64), NB / 64), dim3(256), 0, st, b.A, b.ld,
+                     k0, b.P[buf], b.W[buf], b.ld, b.S[0]);
   panel_chain(b.P[buf], b.W[buf], b.ld, k0, b.SW, b.S, b.piv, b.flag, 1, 0, st);
   return hipGetLastError();
 }
@@ -2394,13 +1936,9 @@ int update_order_block() {
   return v;
 }
 
-bool cross_update_on_tiles() {
-  // 1: -0.2 ms per C2 evaluation against k_update_x (same box, 2 rounds:
-  // 81.03 / 81.26 vs 81.25 / 81.49 ms); bit-identical
-  static const bool v = env_int("ACE_XUPD", 1) != 0;
-  return v;
-}
-
+// The one-step schedule's lookahead cross on k_update's 128-tiles: -0.2 ms
+// per C2 evaluation against the 64-tile k_update_x (same box, 2 rounds: 81.03
+// / 81.26 vs 81.25 / 81.49 ms)
 std::vector<Tile> cross_update_tiles(int64_t naug, int steps, std::vector<int64_t> &off) {
   const int64_t nT = naug / UT;
   constexpr int KT = NB / UT;
@@ -2418,15 +1956,6 @@ std::vector<Tile> cross_update_tiles(int64_t naug, int steps, std::vector<int64_
     off.push_back((int64_t)all.size());
   }
   return all;
-}
-
-// ACE_TAIL_SORT=1 (default): per group, the bulk tile order with each XCD's
-// cheap tiles (copies, block a, the AUG row, skipped lookahead tiles) last;
-// -0.15 ms per C2 evaluation once the side chain is off the critical path
-// (profiles/r02_chain_ab.txt)
-bool tail_sort() {
-  static const bool v = env_int("ACE_TAIL_SORT", 1) != 0;
-  return v;
 }
 
 std::vector<Tile> pair_bulk_orders(int64_t naug, int steps, int64_t *len, int G, int r, int Z) {
@@ -2457,7 +1986,9 @@ std::vector<Tile> pair_bulk_orders(int64_t naug, int steps, int64_t *len, int G,
       const double rows = (I == nT - 1) ? 16.0 / UT : 1.0;
       return rows * (jm >= 0 ? z - 1 - jm : z);
     };
-    lists.push_back(bulk_curve() ? curve_update_order(base, cost) : xcd_update_order(base, S, cost));
+    // each XCD's cheap tiles last: -0.15 ms per C2 evaluation once the side
+    // chain is off the critical path (profiles/r02_chain_ab.txt)
+    lists.push_back(xcd_update_order(base, S, cost));
     *len = std::max<int64_t>(*len, (int64_t)lists.back().size());
   }
   // one length for every group (padding: whole rows of 8, so the XCD dealing
@@ -2491,45 +2022,6 @@ bool pair_steps() {
   // 1: 81.4 -> 79.5 ms per C2 evaluation (profiles/r02_chain_ab.txt)
   static const bool v = env_int("ACE_PAIR", 1) != 0;
   return v;
-}
-
-// ACE_SIDE2: pair steps run the second block's lookahead cross on a second
-// side stream, concurrently with the first block's panel chain (default 1)
-static bool side2_on() {
-  static const bool v = env_int("ACE_SIDE2", 1) != 0;
-  return v;
-}
-
-std::vector<Tile> pair_cross_tiles(int64_t naug, int steps, std::vector<int64_t> &off, int Z) {
-  const int64_t nT = naug / UT;
-  constexpr int KT = NB / UT;
-  const int ng = (steps + Z - 1) / Z;
-  const int S = update_order_block();
-  std::vector<Tile> all;
-  off.assign(3, 0);  // group 0 has no cross lists
-  auto in_blk = [&](int64_t t, int blk) { return t >= (int64_t)blk * KT && t < (int64_t)(blk + 1) * KT; };
-  for (int g = 1; g < ng; ++g) {
-    const int b0 = Z * g, b1 = std::min(Z * g + Z, steps);  // the group's blocks [b0, b1)
-    std::vector<Tile> ta, tb;
-    for (int64_t I = 0; I < nT; ++I)
-      for (int64_t J = 0; J <= I; ++J) {
-        if (in_blk(I, b0) || in_blk(J, b0)) {
-          ta.push_back(Tile{(int)I, (int)J});
-          continue;
-        }
-        for (int bb = b0 + 1; bb < b1; ++bb)
-          if (in_blk(I, bb) || in_blk(J, bb)) {
-            tb.push_back(Tile{(int)I, (int)J});
-            break;
-          }
-      }
-    for (auto *t : {&ta, &tb}) {
-      const std::vector<Tile> o = S > 0 ? xcd_update_order(*t, S) : *t;
-      all.insert(all.end(), o.begin(), o.end());
-      off.push_back((int64_t)all.size());
-    }
-  }
-  return all;
 }
 
 // Head / tail split of the group schedule's lookahead (run_sweep_heads).
@@ -2639,210 +2131,10 @@ std::vector<Tile> xcd_update_order(const std::vector<Tile> &tl, int S,
   return out;
 }
 
-// Index of (x, y) along the Hilbert curve of an n x n grid (n a power of 2)
-static int64_t hilbert_index(int64_t n, int64_t x, int64_t y) {
-  int64_t d = 0;
-  for (int64_t s = n / 2; s > 0; s /= 2) {
-    const int64_t rx = (x & s) ? 1 : 0, ry = (y & s) ? 1 : 0;
-    d += s * s * ((3 * rx) ^ ry);
-    if (ry == 0) {
-      if (rx == 1) {
-        x = n - 1 - x;
-        y = n - 1 - y;
-      }
-      std::swap(x, y);
-    }
-  }
-  return d;
-}
-
-bool bulk_curve() {
-  static const bool v = env_int("ACE_BULK_CURVE", 0) != 0;
-  return v;
-}
-
-std::vector<Tile> curve_update_order(const std::vector<Tile> &tl,
-                                     const std::function<double(const Tile &)> &cost) {
-  // The tiles along a Hilbert curve over the tile grid, cut into 8 pieces of
-  // equal estimated work, one per XCD: an XCD's ~64 tiles in flight are
-  // neighbours on the curve, a compact patch whose row and column panel
-  // blocks its L2 shares (the S x S super-blocks of xcd_update_order are
-  // dealt round-robin, so an XCD's in-flight tiles span ~16 super-columns)
-  constexpr int X = 8;
-  int64_t n = 1, m = 0;
-  for (const Tile &t : tl) m = std::max<int64_t>(m, std::max(t.I, t.J) + 1);
-  while (n < m) n *= 2;
-  std::vector<std::pair<int64_t, size_t>> key(tl.size());
-  for (size_t i = 0; i < tl.size(); ++i) key[i] = {hilbert_index(n, tl[i].J, tl[i].I), i};
-  std::sort(key.begin(), key.end());
-  // work estimate: the cost (segments) plus a launch-slot overhead
-  auto wt = [&](const Tile &t) { return (cost ? cost(t) : 1.0) + 0.02; };
-  double total = 0.0;
-  for (const Tile &t : tl) total += wt(t);
-  std::vector<std::vector<Tile>> q(X);
-  double acc = 0.0;
-  for (const auto &kv : key) {
-    const Tile &t = tl[kv.second];
-    const int x = std::min(X - 1, (int)(acc / total * X));
-    q[x].push_back(t);
-    acc += wt(t);
-  }
-  if (cost)  // each XCD's dearest tiles first (stable: curve order within a class)
-    for (auto &v : q)
-      std::stable_sort(v.begin(), v.end(),
-                       [&](const Tile &a, const Tile &b) { return cost(a) > cost(b); });
-  size_t len = 0;
-  for (auto &v : q) len = std::max(len, v.size());
-  std::vector<Tile> out(len * X, Tile{-1, -1});
-  for (int x = 0; x < X; ++x)
-    for (size_t i = 0; i < q[x].size(); ++i) out[i * X + x] = q[x][i];
-  return out;
-}
-
-// Two-panel launches on k_update_multi (default; ACE_MULTI2=0: k_update_pair)
-static bool multi2_on() {
-  static const bool v = env_int("ACE_MULTI2", 1) != 0;
-  return v;
-}
-
-// Z = b.Z sweep steps per bulk launch (Z = 2 is the round-2 pair form).
-// Group g = steps Z g .. Z g + z_g - 1 (the last one may be shorter), panels
-// in slots k % 2Z.
-//   side:  wait(bulk g-1 done) -> cross of group g+1's first block kb with
-//          group g's panels (gathers panel kb) -> its chain; side2
-//          meanwhile: the cross of the group's other blocks (not in kb) with
-//          group g's panels.  Then for j = 1 .. z-1: the cross of block
-//          kb + j with panels kb .. kb + j - 1 (gathers panel kb + j) -> its
-//          chain.  -> ready(g+1)
-//   main:  wait(ready g) -> the bulk launch of group g's panels over every
-//          tile outside group g+1's cross.
-// Launches of 1 / 2 panels run k_update / k_update_pair, 3 / 4 k_update_multi;
-// every element sees the single-step schedule's MFMA chains in the same
-// order, so the result is bit-identical to it (tests/test_gpu.py).
-static hipError_t run_sweep_groups(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
-                                   const SweepTiming *tm) {
-  const int64_t naug = b.ld;
-  const unsigned nT = (unsigned)(naug / UT);
-  const int steps = (int)(b.npad / NB);
-  const int Z = b.Z;
-  const int ng = (steps + Z - 1) / Z;
-  const bool two = sy && sy->side && sy->nev >= 2 * steps + 1;
-  hipStream_t side = two ? sy->side : st;
-  const bool two2 = two && side2_on() && sy->side2 && sy->nev >= 4 * steps + 4;
-  hipStream_t side2 = two2 ? sy->side2 : side;
-  auto zsize = [&](int g) { return std::min(Z, steps - Z * g); };
-  auto slot = [&](int k) { return k % (2 * Z); };
-  auto E1 = [&](int g) { return sy->ev[2 * steps + 1 + 2 * g]; };
-  auto E2 = [&](int g) { return sy->ev[2 * steps + 2 + 2 * g]; };
-  const bool xg = xgather();
-  auto gout = [&](int k) {
-    return xg ? GatherOut{b.P[slot(k)], b.W[slot(k)], b.S[0], (int64_t)k * NB, b.ld} : no_gather();
-  };
-  // npan steps from block kb on a tile list (null: the row-major grid of nt
-  // tiles), skipping blocks [kx0, kx1).  Two panels run k_update_multi too
-  // (77.1 against 78.1 ms per C2 evaluation with k_update_pair, same box, 3
-  // rounds, profiles/r03_v4_group_ab.txt); ACE_MULTI2=0 selects k_update_pair
-  const bool multi2 = multi2_on();
-  auto upd = [&](int npan, int kb, int kx0, int kx1, const Tile *tl, int64_t nt, GatherOut go,
-                 hipStream_t s_) {
-    if (nt <= 0) return;
-    const int64_t ka0 = (int64_t)kb * NB;
-    if (npan == 1) {  // (only ever without a skip range)
-      hipLaunchKernelGGL(k_update, dim3((unsigned)nt), dim3(UTHREADS), 0, s_, b.A, b.ld,
-                         b.W[slot(kb)], b.P[slot(kb)], b.W[slot(kb)], b.ld, ka0, -1, tl, 1, go);
-    } else if (npan == 2 && !multi2) {
-      hipLaunchKernelGGL(k_update_pair, dim3((unsigned)nt), dim3(UTHREADS), 0, s_, b.A, b.ld,
-                         b.W[slot(kb)], b.P[slot(kb)], b.W[slot(kb + 1)], b.P[slot(kb + 1)], b.ld,
-                         ka0, kx0, kx1, tl, go, 1, 0);
-    } else {
-      PanelSet ps;
-      for (int j = 0; j < 4; ++j) {
-        ps.R[j] = j < npan ? b.W[slot(kb + j)] : nullptr;
-        ps.C[j] = j < npan ? b.P[slot(kb + j)] : nullptr;
-      }
-      hipLaunchKernelGGL(k_update_multi<false>, dim3((unsigned)nt), dim3(UTHREADS), 0, s_, b.A,
-                         b.ld, ps, npan, b.ld, ka0, kx0, kx1, tl, go, 1);
-    }
-  };
-  // blocks kb + 1 .. kb + z - 1 of a group from its own panels, each followed
-  // by its chain (on `side`)
-  auto inner = [&](int kb, int z) -> hipError_t {
-    for (int j = 1; j < z; ++j) {
-      const int k = kb + j - 1;  // xoff list k: the tiles with I or J in block k + 1
-      const int64_t x0 = b.xoff[k], nx = b.xoff[k + 1] - x0;
-      upd(j, kb, -1, -1, b.xtiles + x0, nx, gout(kb + j), side);
-      const hipError_t r = panel_sweep(b, slot(kb + j), (int64_t)(kb + j) * NB, side, xg);
-      if (r != hipSuccess) return r;
-    }
-    return hipSuccess;
-  };
-  hipError_t e;
-  if (two) {
-    if (!sy->ready_recorded) {
-      e = hipEventRecord(sy->ev[2 * steps], st);  // inputs ready
-      if (e != hipSuccess) return e;
-    }
-    if ((e = hipStreamWaitEvent(side, sy->ev[2 * steps], 0)) != hipSuccess) return e;
-  }
-  // group 0: its first panel is gathered by its chain (nothing wrote it yet)
-  if ((e = panel_sweep(b, slot(0), 0, side)) != hipSuccess) return e;
-  if ((e = inner(0, zsize(0))) != hipSuccess) return e;
-  if (two && (e = hipEventRecord(sy->ev[0], side)) != hipSuccess) return e;
-  int used = 0;
-  for (int g = 0; g < ng; ++g) {
-    const int kg = Z * g;
-    const bool more = g + 1 < ng;
-    const int kb = Z * (g + 1), zb = more ? zsize(g + 1) : 0;
-    if (two && (e = hipStreamWaitEvent(st, sy->ev[2 * g], 0)) != hipSuccess) return e;
-    if (more) {
-      if (two) {
-        if ((e = hipEventRecord(sy->ev[2 * g + 1], st)) != hipSuccess) return e;  // bulk g-1 done
-        if ((e = hipStreamWaitEvent(side, sy->ev[2 * g + 1], 0)) != hipSuccess) return e;
-      }
-      const int64_t pa = b.poff[2 * (g + 1)], na = b.poff[2 * (g + 1) + 1] - pa;
-      const int64_t pb = b.poff[2 * (g + 1) + 1], nb = b.poff[2 * (g + 1) + 2] - pb;
-      if (nb > 0 && two2) {
-        if ((e = hipEventRecord(E1(g + 1), side)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(side2, E1(g + 1), 0)) != hipSuccess) return e;
-      }
-      upd(zsize(g), kg, -1, -1, b.ptiles + pa, na, gout(kb), side);
-      if (nb > 0) {
-        upd(zsize(g), kg, -1, -1, b.ptiles + pb, nb, no_gather(), side2);
-        if (two2 && (e = hipEventRecord(E2(g + 1), side2)) != hipSuccess) return e;
-      }
-      if ((e = panel_sweep(b, slot(kb), (int64_t)kb * NB, side, xg)) != hipSuccess) return e;
-      if (nb > 0 && two2 && (e = hipStreamWaitEvent(side, E2(g + 1), 0)) != hipSuccess) return e;
-      if ((e = inner(kb, zb)) != hipSuccess) return e;
-      if (two && (e = hipEventRecord(sy->ev[2 * (g + 1)], side)) != hipSuccess) return e;
-    }
-    const bool timed = tm && tm->ev && used + 2 <= tm->nev;
-    if (timed) (void)hipEventRecord(tm->ev[used], st);
-    const int64_t grid = b.gorder ? b.glen : (b.order ? b.norder : (int64_t)nT * (nT + 1) / 2);
-    const Tile *ord = b.gorder ? b.gorder + (int64_t)g * b.glen : b.order;
-    const int kx0 = more ? kb : -1, kx1 = more ? kb + zb : -1;
-    upd(zsize(g), kg, kx0, kx1, ord, grid, no_gather(), st);
-    if (timed) {
-      (void)hipEventRecord(tm->ev[used + 1], st);
-      if (tm->flops)
-        tm->flops[used / 2] =
-            update_gemm_tiles_group(naug, (int64_t)kg * NB, zsize(g), kx0, kx1) * 2.0 * UT * UT * NB;
-      used += 2;
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if (tm && tm->used) *tm->used = used;
-  return hipSuccess;
-}
-
-// ACE_HEADS=1: the group schedule with its lookahead split into a head path
-// and a tail path (run_sweep_heads)
-bool heads_on() {
-  static const bool v = env_int("ACE_HEADS", 1) != 0;
-  return v;
-}
-
-// The group schedule with the lookahead split by what the next chain needs
-// (lists from group_head_tiles; group g+1 = blocks [kb, kb + z)):
+// The default schedule: Z = b.Z sweep steps per bulk launch (group g = steps
+// Z g .. Z g + z_g - 1, the last one may be shorter; panels in slots k % 2Z),
+// the lookahead split by what the next chain needs (lists from
+// group_head_tiles; group g+1 = blocks [kb, kb + z)):
 //   side (head path, the critical one): group g's panels on Q (gathers panel
 //     kb's head rows) -> for each panel k = kb + j: pivot + sub-steps ->
 //     panel GEMM of the rows in blocks (k, kb + z) -> panel k on Q_{j+1}
@@ -2852,10 +2144,11 @@ bool heads_on() {
 //     [after k's head GEMM] T_{j+1}: panels kb .. k on block k + 1's cross
 //     minus its head -> ... -> ready2(g+1)
 //   main:  wait(ready g, ready2 g) -> the bulk launch of group g.
-// Every tile sees the same panels in the same order with the same per-launch
-// rule as run_sweep_groups, so the result is bit-identical to it; the head
-// path is a chain of small launches (Q: z(z KT + 1) KT / 2 tiles) instead of
-// whole block-column crosses.
+// The head path is a chain of small launches (Q: z(z KT + 1) KT / 2 tiles),
+// where whole block-column crosses before each chain lost (C2 76.6 -> 75.9
+// ms, profiles/r03_v5_heads_ab.txt).  Every element sees the one-step
+// schedule's MFMA chains (run_sweep_steps) in the same order, fp64 kept in
+// registers between a launch's panels: bit-identical to it (tests/test_gpu.py).
 static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
                                   const SweepTiming *tm) {
   const int64_t naug = b.ld;
@@ -2887,7 +2180,9 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
     p = b.htiles + b.hoff[i];
     n = b.hoff[i + 1] - b.hoff[i];
   };
-  const bool multi2 = multi2_on();
+  // npan steps from block kb on a tile list, skipping blocks [kx0, kx1).  Two
+  // panels run k_update_multi too (77.1 against 78.1 ms per C2 evaluation with
+  // a two-panel kernel of its own, profiles/r03_v4_group_ab.txt)
   auto upd = [&](int npan, int kb, int kx0, int kx1, const Tile *tl, int64_t nt, GatherOut go,
                  hipStream_t s_) {
     if (nt <= 0) return;
@@ -2895,10 +2190,6 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
     if (npan == 1) {
       hipLaunchKernelGGL(k_update, dim3((unsigned)nt), dim3(UTHREADS), 0, s_, b.A, b.ld,
                          b.W[slot(kb)], b.P[slot(kb)], b.W[slot(kb)], b.ld, ka0, -1, tl, 1, go);
-    } else if (npan == 2 && !multi2) {
-      hipLaunchKernelGGL(k_update_pair, dim3((unsigned)nt), dim3(UTHREADS), 0, s_, b.A, b.ld,
-                         b.W[slot(kb)], b.P[slot(kb)], b.W[slot(kb + 1)], b.P[slot(kb + 1)], b.ld,
-                         ka0, kx0, kx1, tl, go, 1, 0);
     } else {
       PanelSet ps;
       for (int j = 0; j < 4; ++j) {
@@ -2909,39 +2200,35 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
                          b.ld, ps, npan, b.ld, ka0, kx0, kx1, tl, go, 1);
     }
   };
-  // head-path launches on Q lists: 64 x 64 quarters (k_update_q, ACE_HEADQ=1,
-  // default) or the 128-tile kernels
-  static const bool hq = env_int("ACE_HEADQ", 1) != 0;
-  // panels k >= 1 are gathered by k_update_q launches, which sweep their D_0
-  // (the blocked pivot only: the same code as k_pivot's, bit-identical)
-  const bool fused_pivot = hq && ACE_PIVOT_BLK;
-  // Small n (with the bulk queue): the latency-critical launches on 32 x 32
-  // pieces (k_update_q4 / k_panel_gemm_q4, bit-identical): every Q launch,
-  // the head panel GEMMs and each group's last tail panel GEMM -- C1 3.59 ->
-  // 3.41 ms (profiles/r06_qsplit_ab.txt).  ACE_QSPLIT: 1 (default) all of
-  // them, 3 the Q launches only, 2 the group-boundary Q only, 0 none.  One
-  // D_0 counter per panel after the chain counters (zero when allocated,
-  // reset by the last piece).
-  static const int qsplit = env_int("ACE_QSPLIT", 1);
-  int *const qctr = (qsplit > 0 && b.bq && b.breserve > 0)
-                        ? b.bq + (int64_t)((steps + Z - 1) / Z) * BQ_INTS + 2 * steps
-                        : nullptr;
-  auto qupd = [&](int npan, int kb, const Tile *tl, int64_t nt, GatherOut go, hipStream_t s_,
-                  bool boundary = false) {
+  // The small-n regime (n <= ACE_BULK_RESERVE_N by default; ACE_BULK_RESERVE
+  // selects it at any n): the chains, not the bulk launches, are the critical
+  // path.  The bulk launches run as a persistent queue that leaves CUs to
+  // the chains (k_update_multi_r), and with it
+  //   * the latency-critical head launches work on 32 x 32 pieces
+  //     (k_update_q4 / k_panel_gemm_q4): every Q launch, the head panel GEMMs
+  //     and each group's last tail panel GEMM -- C1 3.59 -> 3.41 ms against
+  //     64 x 64 (profiles/r06_qsplit_ab.txt);
+  //   * each panel's four split sub-steps run as one k_panel_split4 launch;
+  //   * each group's last tail panel GEMM runs on the head stream (tlast below).
+  // bq_layout: after the queues, k_panel_split4's counters (fctr + 2 k) and
+  // one D_0 counter of k_update_q4 per panel (qctr + k), zero between launches.
+  const bool small = b.bq && b.breserve > 0;
+  const BqLayout bql = bq_layout(steps, Z);
+  int *const fctr = small ? b.bq + bql.fctr : nullptr;
+  int *const qctr = small ? b.bq + bql.qctr : nullptr;
+  // head-path launches on Q lists, on 64 x 64 quarters (k_update_q) or, small
+  // n, 32 x 32 pieces.  A launch that gathers a panel (every panel k >= 1)
+  // also sweeps its D_0 (k_update_q's fused pivot): that panel's chain then
+  // starts at sub-step 0's panel update.
+  auto qupd = [&](int npan, int kb, const Tile *tl, int64_t nt, GatherOut go, hipStream_t s_) {
     if (nt <= 0) return;
-    if (!hq) {
-      upd(npan, kb, -1, -1, tl, nt, go, s_);
-      return;
-    }
     PanelSet ps;
     for (int j = 0; j < 4; ++j) {
       ps.R[j] = j < npan ? b.W[slot(kb + j)] : nullptr;
       ps.C[j] = j < npan ? b.P[slot(kb + j)] : nullptr;
     }
-    // a launch that gathers a panel also sweeps its D_0 (k_update_q's fused
-    // pivot): that panel's chain then starts at sub-step 0's panel update
-    const bool fp = fused_pivot && go.k0 >= 0;
-    if (qctr && (qsplit != 2 || boundary))  // small n: 32 x 32 pieces (k_update_q4)
+    const bool fp = go.k0 >= 0;
+    if (small)
       hipLaunchKernelGGL(k_update_q4, dim3((unsigned)(16 * nt)), dim3(256), 0, s_, b.A, b.ld, ps,
                          npan, b.ld, tl, go, fp ? b.SW : nullptr, fp ? b.piv : nullptr,
                          fp ? b.flag : nullptr, qctr + (go.k0 >= 0 ? go.k0 / NB : 0));
@@ -2955,10 +2242,9 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
   auto pgemm = [&](int k, int r0, int r1, bool head, hipStream_t s_, bool last = false) {
     const int n = head ? r1 - r0 : (int)nT - (r1 - r0);
     if (n <= 0) return;
-    if (!head && last && qctr && qsplit == 1) {
+    if (!head && last && small) {
       // the group's last tail GEMM is on the path to the next group's Q: on
-      // 32 x 32 pieces (k_panel_gemm_q's chain, k_panel_gemm_t's result), the
-      // rows before and after the head
+      // 32 x 32 pieces, the rows before and after the head
       if (r0 > 0)
         hipLaunchKernelGGL(k_panel_gemm_q4, dim3((unsigned)(2 * r0 * (UT / XT)), 2 * (NB / XT)),
                            dim3(256), 0, s_, b.W[slot(k)], b.P[slot(k)], b.ld, (int64_t)k * NB, 0);
@@ -2967,41 +2253,31 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
                            dim3(256), 0, s_, b.W[slot(k)], b.P[slot(k)], b.ld, (int64_t)k * NB, r1);
       return;
     }
-    if (head && ACE_PGEMM_HEADQ && qctr && qsplit == 1)
+    if (head && small)
       hipLaunchKernelGGL(k_panel_gemm_q4, dim3((unsigned)(2 * n * (UT / XT)), 2 * (NB / XT)), dim3(256),
                          0, s_, b.W[slot(k)], b.P[slot(k)], b.ld, (int64_t)k * NB, r0);
-    else if (head && ACE_PGEMM_HEADQ)
+    else if (head)
       hipLaunchKernelGGL(k_panel_gemm_q, dim3((unsigned)(n * (UT / XT)), NB / XT), dim3(256), 0, s_,
                          b.W[slot(k)], b.P[slot(k)], b.ld, (int64_t)k * NB, r0);
     else
       hipLaunchKernelGGL(k_panel_gemm_t, dim3((unsigned)n, NB / UT), dim3(UTHREADS), 0, s_,
-                         b.W[slot(k)], b.P[slot(k)], b.ld, (int64_t)k * NB, 1, 0, head ? r0 : 0,
-                         head ? 1 << 30 : r0, head ? 1 << 30 : r1);
+                         b.W[slot(k)], b.P[slot(k)], b.ld, (int64_t)k * NB, 1, 0, 0, r0, r1);
   };
-  // small n: each panel's four split sub-steps in one launch (k_panel_split4),
-  // its barrier counter after the bulk queues
-  int *const fctr = (b.bq && b.breserve > 0 && chain_fuse()) ? b.bq + (int64_t)ng * BQ_INTS : nullptr;
   // Small n: each fused chain launch with 13 KB of extra LDS, so that no
   // bulk / cross / tail workgroup (73.7 KB) fits beside a chain workgroup
   // (77.3 KB): the chain runs alone on its 16 CUs instead of sharing each
   // with an MFMA-bound workgroup (2x slower).  With the head launches on
-  // 32 x 32 pieces (ACE_QSPLIT) C1 3.34 -> 3.10 ms (profiles/r06_chain_xlds_ab.txt;
+  // 32 x 32 pieces C1 3.34 -> 3.10 ms (profiles/r06_chain_xlds_ab.txt;
   // before them only the contention moved, r06_c1_chain_isolation_ab.txt).
-  // Placement only: bit-identical.  ACE_CHAIN_XLDS=B overrides the bytes (0:
-  // off), ACE_CHAIN_XLDS_J the panel mask within a group (default all),
-  // ACE_CHAIN_XLDS_G0=0 leaves group 0's chains (beside the assembly) as they were.
+  // Placement only: the results do not depend on it.  ACE_CHAIN_XLDS=B
+  // overrides the bytes (0: off).
   static const unsigned xlds = (unsigned)std::max(0, env_int("ACE_CHAIN_XLDS", 13312));
-  static const int xlds_j = env_int("ACE_CHAIN_XLDS_J", -1);
-  static const bool xlds_g0 = env_int("ACE_CHAIN_XLDS_G0", 1) != 0;
   auto chain = [&](int k, hipStream_t s_) {  // [pivot +] sub-steps of panel k (gathered)
-    const int j = k % Z, G = k / Z;
     panel_chain(b.P[slot(k)], b.W[slot(k)], b.ld, (int64_t)k * NB, b.SW, b.S, b.piv, b.flag, 1, 0,
-                s_, fused_pivot && k > 0, true, fctr ? fctr + 2 * k : nullptr,
-                (fctr && qctr && (G > 0 || xlds_g0) && ((xlds_j >> j) & 1)) ? xlds : 0u);
+                s_, k > 0, true, small ? fctr + 2 * k : nullptr, small ? xlds : 0u);
   };
   hipError_t e;
-  if (b.bq && b.breserve > 0 &&
-      (e = hipMemsetAsync(b.bq, 0, (size_t)ng * BQ_INTS * sizeof(int), st)) != hipSuccess)
+  if (small && (e = hipMemsetAsync(b.bq, 0, (size_t)bql.fctr * sizeof(int), st)) != hipSuccess)
     return e;  // the bulk queues (k_update_multi_r), before any bulk launch
   if (!sy->ready_recorded) {
     e = hipEventRecord(sy->ev[2 * steps], st);  // inputs ready
@@ -3015,22 +2291,19 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
   // for every sub-step, 112 registers, 73 KB of LDS -- did not get group 0's
   // chains beside the assembly's second part: neutral,
   // profiles/r03_v5_heads_ab.txt.)
-  // Small n (ACE_QFIRST, default up to n = ACE_BULK_RESERVE_N): at a group
+  // Small n (default up to n = ACE_BULK_RESERVE_N; ACE_QFIRST overrides): at a group
   // boundary the next group's Q launch (its head square, K = Z NB) runs
   // alone -- the rest of the cross (side2) and the bulk launch (main) wait
   // for it.  There the chain is the critical path and the bulk is short; Q
   // beside both took 163 us instead of ~40 (C1 trace, profiles/r05_v4_*).
   const bool qfirst = q_first(naug);
   auto Eq = [&](int G) { return sy->ev[2 * steps + 1 + 2 * G]; };  // group G's Q done
-  // ACE_TAIL_LAST=1 (default): group G >= 1's last tail panel GEMM on the head stream
-  // after the tail path's last T update (Et(G), an event slot the direct-wait
-  // schedule leaves free); the next group's Q then follows it in stream order
-  // and waits for the tail path through Et(G) instead of E2(G)
-  static const bool tail_last_on = env_int("ACE_TAIL_LAST", 1) != 0;
-  // (small n: the chain-bound schedule with the bulk queue)
+  // Small n: group G's last tail panel GEMM on the head stream after the
+  // tail path's last T update (Et(G), an event slot the direct-wait schedule
+  // leaves free); the next group's Q then follows it in stream order and
+  // waits for the tail path through Et(G) instead of E2(G)
   auto tlast = [&](int G) {
-    return tail_last_on && qdirect && b.bq && b.breserve > 0 && zsize(G) >= 2 &&
-           !(G == 0 && sy->tail_split);
+    return small && qdirect && zsize(G) >= 2 && !(G == 0 && sy->tail_split);
   };
   auto Et = [&](int G) { return sy->ev[2 * G + 1]; };
   hipEvent_t const Ef = sy->ev[2 * steps - 1];  // group 0's tail path + filler (odd: free too)
@@ -3044,7 +2317,7 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
       const Tile *tl;
       int64_t nt;
       list(G, 0, tl, nt);
-      qupd(zsize(G - 1), Z * (G - 1), tl, nt, gout(kb), side, true);  // Q
+      qupd(zsize(G - 1), Z * (G - 1), tl, nt, gout(kb), side);  // Q
     }
     return qfirst ? hipEventRecord(Eq(G), side) : hipSuccess;
   };
@@ -3160,7 +2433,7 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
     const int64_t grid = b.gorder ? b.glen : (b.order ? b.norder : (int64_t)nT * (nT + 1) / 2);
     const Tile *ord = b.gorder ? b.gorder + (int64_t)g * b.glen : b.order;
     const int kx0 = more ? kb : -1, kx1 = more ? kb + zb : -1;
-    if (b.bq && b.breserve > 0 && ord && zsize(g) > 2) {
+    if (small && ord && zsize(g) > 2) {
       PanelSet ps;
       for (int j = 0; j < 4; ++j) {
         ps.R[j] = j < zsize(g) ? b.W[slot(kg + j)] : nullptr;
@@ -3188,70 +2461,41 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
   return hipSuccess;
 }
 
-hipError_t run_sweep(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
-                     const SweepTiming *tm) {
-  if (pair_steps() && b.ptiles && b.xtiles && b.P[2 * b.Z - 1] && b.npad / NB >= 2) {
-    // the group schedules (Z steps per bulk launch): head / tail lookahead
-    // (default) or the round-3 group lookahead (ACE_HEADS=0)
-    if (b.htiles && heads_on() && sy && sy->side && sy->side2 &&
-        sy->nev >= 5 * (int)(b.npad / NB) + 3)
-      return run_sweep_heads(b, st, sy, tm);
-    return run_sweep_groups(b, st, sy, tm);
-  }
+// The one-step reference schedule (ACE_PAIR=0, and any sweep of one step):
+// one k_update launch per step, panels in slots k & 1.  The bitwise referee
+// of run_sweep_heads (81.4 against 79.5 ms per C2 evaluation at two steps per
+// launch, profiles/r02_chain_ab.txt).
+//   side:  wait(bulk k-1 done) -> the cross of block k+1 with panel k (the
+//          lower tiles with I or J in block k+1, b.xtiles) -> panel k+1:
+//          gather, chain, panel GEMM -> ready(k+1)
+//   main:  wait(ready k) -> step k on every tile outside that cross.
+// ACE_STREAMS=1 runs both on one stream, in this order.
+static hipError_t run_sweep_steps(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
+                                  const SweepTiming *tm) {
   const int64_t naug = b.ld;
   const unsigned nT = (unsigned)(naug / UT);
   const int steps = (int)(b.npad / NB);
-  // ACE_LOOKAHEAD=0: one stream, no lookahead (diagnostic: the chain
-  // kernels then run alone, uncontended)
-  static const int look = env_int("ACE_LOOKAHEAD", 1);
-  const bool two = look && sy && sy->side && sy->nev >= 2 * steps + 1;
-  hipStream_t side = two ? sy->side : st;
+  hipStream_t side = sy->side;
   int used = 0;
   hipError_t e;
-  if (two) {
-    if (!sy->ready_recorded) {
-      e = hipEventRecord(sy->ev[2 * steps], st);  // inputs ready
-      if (e != hipSuccess) return e;
-    }
-    e = hipStreamWaitEvent(side, sy->ev[2 * steps], 0);
-    if (e != hipSuccess) return e;
-  }
-  e = panel_sweep(b, 0, 0, side);
-  if (e != hipSuccess) return e;
-  if (two) {
-    e = hipEventRecord(sy->ev[0], side);
-    if (e != hipSuccess) return e;
-  }
+  if (!sy->ready_recorded && (e = hipEventRecord(sy->ev[2 * steps], st)) != hipSuccess)
+    return e;  // inputs ready
+  if ((e = hipStreamWaitEvent(side, sy->ev[2 * steps], 0)) != hipSuccess) return e;
+  if ((e = panel_sweep(b, 0, 0, side)) != hipSuccess) return e;
+  if ((e = hipEventRecord(sy->ev[0], side)) != hipSuccess) return e;
   for (int k = 0; k < steps; ++k) {
     const int buf = k & 1;
     const int64_t k0 = (int64_t)k * NB;
     const bool more = k + 1 < steps;
-    if (two) {
-      e = hipStreamWaitEvent(st, sy->ev[2 * k], 0);  // panel k done
-      if (e != hipSuccess) return e;
-    }
+    if ((e = hipStreamWaitEvent(st, sy->ev[2 * k], 0)) != hipSuccess) return e;  // panel k done
     if (more) {
-      if (two) {
-        e = hipEventRecord(sy->ev[2 * k + 1], st);  // bulk update k-1 done
-        if (e != hipSuccess) return e;
-        e = hipStreamWaitEvent(side, sy->ev[2 * k + 1], 0);
-        if (e != hipSuccess) return e;
-      }
-      if (b.xtiles) {  // the cross of block k+1 on k_update's 128-tiles
-        const int64_t x0 = b.xoff[k], nx = b.xoff[k + 1] - x0;
-        hipLaunchKernelGGL(k_update, dim3((unsigned)nx), dim3(UTHREADS), 0, side, b.A, b.ld,
-                           b.W[buf], b.P[buf], b.W[buf], b.ld, k0, -1, b.xtiles + x0, 1,
-                           no_gather());
-      } else {
-        hipLaunchKernelGGL(k_update_x, dim3((unsigned)(naug / XT), 2 * (NB / XT)), dim3(256), 0,
-                           side, b.A, b.ld, b.W[buf], b.P[buf], b.W[buf], b.ld, k0, k + 1, 1, 0);
-      }
-      e = panel_sweep(b, buf ^ 1, k0 + NB, side);
-      if (e != hipSuccess) return e;
-      if (two) {
-        e = hipEventRecord(sy->ev[2 * (k + 1)], side);
-        if (e != hipSuccess) return e;
-      }
+      if ((e = hipEventRecord(sy->ev[2 * k + 1], st)) != hipSuccess) return e;  // bulk k-1 done
+      if ((e = hipStreamWaitEvent(side, sy->ev[2 * k + 1], 0)) != hipSuccess) return e;
+      const int64_t x0 = b.xoff[k], nx = b.xoff[k + 1] - x0;
+      hipLaunchKernelGGL(k_update, dim3((unsigned)nx), dim3(UTHREADS), 0, side, b.A, b.ld, b.W[buf],
+                         b.P[buf], b.W[buf], b.ld, k0, -1, b.xtiles + x0, 1, no_gather());
+      if ((e = panel_sweep(b, buf ^ 1, k0 + NB, side)) != hipSuccess) return e;
+      if ((e = hipEventRecord(sy->ev[2 * (k + 1)], side)) != hipSuccess) return e;
     }
     const bool timed = tm && tm->ev && used + 2 <= tm->nev;
     if (timed) (void)hipEventRecord(tm->ev[used], st);
@@ -3264,11 +2508,24 @@ hipError_t run_sweep(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
           update_gemm_tiles(naug, k0, more ? k + 1 : -1, false) * 2.0 * UT * UT * NB;
       used += 2;
     }
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (tm && tm->used) *tm->used = used;
   return hipSuccess;
+}
+
+hipError_t run_sweep(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
+                     const SweepTiming *tm) {
+  const int steps = (int)(b.npad / NB);
+  // both schedules run on the caller's side streams (which may alias the
+  // main one) and events (SweepSync)
+  if (!sy || !sy->side || !sy->side2 || !b.xtiles || sy->nev < 5 * steps + 3)
+    return hipErrorInvalidValue;
+  if (pair_steps() && steps >= 2) {
+    if (!b.htiles || !b.gorder || !b.P[2 * b.Z - 1]) return hipErrorInvalidValue;
+    return run_sweep_heads(b, st, sy, tm);
+  }
+  return run_sweep_steps(b, st, sy, tm);
 }
 
 // ---- sharded step pieces (driven by ace_shard.cpp) --------------------------

@@ -73,7 +73,7 @@ class TorchComm:
 
 def pivot_block(Dblk):
     """Sweep of the NB x NB pivot block in SUB-column sub-steps (k_pivot +
-    k_panel restricted to the pivot rows): returns W_kk = -D^-1 and the
+    k_panel_split on the pivot rows): returns W_kk = -D^-1 and the
     pivots."""
     nb = Dblk.shape[0]
     W = Dblk.copy()
@@ -131,7 +131,7 @@ class RankState:
         return low, send[:row_slots(k, G)]
 
     def unpack_chain(self, k, low, recv):
-        """k_unpack_panel + pivot chain + k_panel_gemm for the rows r consumes."""
+        """k_unpack_panel + pivot chain + k_panel_gemm_t for the rows r consumes."""
         G, k0, naug = self.G, k * NB, self.naug
         P = np.zeros((naug, NB))
         P[k0:, :] = low

@@ -11,7 +11,7 @@ NB, SUB, UT, AUG = 256, 64, 128, 128
 
 def sweep_lower(A, npad, nb=NB, sub=SUB, ut=UT):
     """In place on A (naug x naug, only the lower triangle is read), mirroring
-    k_gather / k_pivot / k_panel / k_update.  Returns the pivots."""
+    k_gather / k_pivot / k_panel_split / k_panel_gemm_t / k_update.  Returns the pivots."""
     naug = A.shape[0]
     piv = np.zeros(npad)
     nT = naug // ut

@@ -459,61 +459,31 @@ def test_update_tile_order_is_bitwise_neutral(A, tmp_path):
     assert np.array_equal(mine, outs["4"])
 
 
-def test_cross_update_on_tiles_is_bitwise_neutral(A, tmp_path):
-    """The lookahead cross update on k_update's 128-tiles (ACE_XUPD=1) runs
-    the same MFMA chain per element as k_update_x's 64-tiles: the inverse
-    is bit-identical."""
-    import os
-    import subprocess
-    import sys
-    from additivecausalexpansion_amd.synthetic import make_problem
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    n = 1500
-    y, X, Z, th, _ = make_problem(n, 4, 5, seed=19)
-    K = A.kernmat_SE_symmetric_cpp(X, Z, th)["full"]
-    inp = str(tmp_path / "k.npz")
-    np.savez(inp, K=K, s=th[0])
-    outs = {}
-    for v in ("0", "1"):
-        out = str(tmp_path / f"inv{v}.npy")
-        env = dict(os.environ, ACE_XUPD=v)
-        run_child(_ORDER_SNIPPET.format(root=root, inp=inp, out=out), env=env, timeout=100)
-        outs[v] = np.load(out)
-    assert np.array_equal(outs["0"], outs["1"])
-    assert np.array_equal(A.invkernel_cpp(K, th[0])["inv"], outs["0"])
+# the n > 8192 production regime (Z = 4, the plain bulk grid, Q beside the
+# rest of the lookahead), selected at sizes that take seconds
+LARGE_N_REGIME = {"ACE_GROUP": "4", "ACE_BULK_RESERVE": "0", "ACE_QFIRST": "0"}
 
 
 @pytest.mark.parametrize("n", [1100, 1500, 2600])
-def test_pair_steps_are_bitwise_neutral(A, tmp_path, n):
-    """Two sweep steps per bulk launch (k_update_pair, ACE_PAIR=1) run every
-    element's MFMA chain over the same k order as one step per launch: the
-    inverse is bit-identical.  n = 1100: 5 steps (a last single step), 1500: 6.
-    So are the second block's cross on its own stream (ACE_SIDE2=0 runs it on
-    the panel stream), the cost-sorted bulk order (ACE_TAIL_SORT=1), the
-    gather fused into the cross launches (ACE_XGATHER=0: k_gather), one
-    stream for everything (ACE_LOOKAHEAD=0), the panel GEMM on 128-tiles
-    (ACE_PGEMM_TILES=0: the 64-row k_panel_gemm).  Three and four steps per
-    bulk launch (ACE_GROUP=3 / 4, k_update_multi; groups 3+2 / 4+1 at n =
-    1100, 3+3 / 4+2 at 1500, 3+3+3+2 / 4+4+3 at 2600) are bit-identical too,
-    with and without the fused gather, the second side stream and lookahead,
-    and so is the head / tail split of the group lookahead (ACE_HEADS=1 at
-    Z = 2, 3, 4), with its small-n bulk launches as a persistent queue that
-    leaves 1 (default below n = 8192) or 2 CUs per engine to the chains, or
-    as the plain grid (ACE_BULK_RESERVE=0), and with the next group's Q launch
-    run before (default below n = 8192) or beside (ACE_QFIRST=0) the bulk
-    launch and the rest of the cross.  Round 6: each panel's four split
-    sub-steps in one launch with a grid barrier between them
-    (k_panel_split4, ACE_CHAIN_FUSE=1, default with the small-n bulk
-    queue) against four k_panel_split launches (0); the bulk tiles in
-    Hilbert-curve pieces per XCD (ACE_BULK_CURVE=1); the small-n head
-    launches on 32 x 32 pieces (ACE_QSPLIT, default 1) against 64 x 64 (0),
-    the Q launches only (3) and the group-boundary Q only (2); each group's
-    last tail panel GEMM on the head stream (ACE_TAIL_LAST, default 1) or on
-    the tail stream (0); the fused chains alone on their CUs (extra LDS,
-    ACE_CHAIN_XLDS, default) or sharing them (0)."""
+def test_sweep_schedules_are_bitwise_neutral(A, tmp_path, n):
+    """The default schedule (run_sweep_heads: Z sweep steps per bulk launch,
+    head / tail lookahead) runs every element's MFMA chain over the same k
+    order as the one-step reference schedule (ACE_PAIR=0, `single`): the
+    inverse is bit-identical.  n = 1100: 5 steps, 1500: 6, 2600: 11, so the
+    groups are 2+2+1 / 3+2 / 4+1, 2+2+2 / 3+3 / 4+2 and 2 x 5 + 1 / 3+3+3+2 /
+    4+4+3 at Z = 2 / 3 / 4 (ACE_GROUP).  `default` is the small-n regime:
+    Z = 3, the bulk launches as a persistent queue that leaves 1 CU per
+    engine to the chains, and with it the head launches on 32 x 32 pieces,
+    each panel's four sub-steps in one k_panel_split4 launch and the last
+    tail panel GEMM on the head stream; the same at Z = 2 and 4, with 2 CUs
+    reserved, and with the plain grid instead (ACE_BULK_RESERVE=0: 64 x 64
+    head pieces, four k_panel_split launches, k_panel_gemm_t tails).  The
+    next group's Q launch runs before (default at these n) or beside
+    (ACE_QFIRST=0) the bulk launch and the rest of the cross; the fused
+    chains run alone on their CUs (extra LDS, ACE_CHAIN_XLDS, default) or
+    share them (0).  `large_n_regime` is exactly what n > 8192 runs, and
+    `large_n_regime3` the same at Z = 3."""
     import os
-    import subprocess
-    import sys
     from additivecausalexpansion_amd.synthetic import make_problem
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     y, X, Z, th, _ = make_problem(n, 4, 5, seed=23)
@@ -521,43 +491,17 @@ def test_pair_steps_are_bitwise_neutral(A, tmp_path, n):
     inp = str(tmp_path / "k.npz")
     np.savez(inp, K=K, s=th[0])
     outs = {}
-    z2 = {"ACE_GROUP": "2", "ACE_HEADS": "0"}  # the round-2 / round-3 Z = 2 schedules
-    variants = {"single": {"ACE_PAIR": "0"}, "pair": {"ACE_PAIR": "1", **z2},
-                "one_side": {"ACE_PAIR": "1", "ACE_SIDE2": "0", **z2},
-                "tail": {"ACE_PAIR": "1", "ACE_TAIL_SORT": "1", **z2},
-                "gather": {"ACE_PAIR": "1", "ACE_XGATHER": "0", **z2},
-                "one_stream": {"ACE_PAIR": "1", "ACE_LOOKAHEAD": "0", **z2},
-                "pgemm_rows": {"ACE_PAIR": "1", "ACE_PGEMM_TILES": "0", **z2},
-                "single_pgemm_rows": {"ACE_PAIR": "0", "ACE_PGEMM_TILES": "0"},
-                "pair_kernel": {"ACE_MULTI2": "0", **z2},
-                "group3": {"ACE_GROUP": "3", "ACE_HEADS": "0"},
-                "group4": {"ACE_GROUP": "4", "ACE_HEADS": "0"},
-                "group4_gather": {"ACE_GROUP": "4", "ACE_HEADS": "0", "ACE_XGATHER": "0"},
-                "group4_one_side": {"ACE_GROUP": "4", "ACE_HEADS": "0", "ACE_SIDE2": "0"},
-                "group4_one_stream": {"ACE_GROUP": "4", "ACE_HEADS": "0", "ACE_LOOKAHEAD": "0"},
-                "group3_untail": {"ACE_GROUP": "3", "ACE_HEADS": "0", "ACE_TAIL_SORT": "0"},
-                "heads2": {"ACE_GROUP": "2", "ACE_HEADS": "1"},
-                "heads3": {"ACE_GROUP": "3", "ACE_HEADS": "1"},
-                "heads4": {"ACE_GROUP": "4", "ACE_HEADS": "1"}, "default": {},
-                "heads4_pair": {"ACE_GROUP": "4", "ACE_HEADS": "1", "ACE_MULTI2": "0"},
-                "heads4_q128": {"ACE_GROUP": "4", "ACE_HEADS": "1", "ACE_HEADQ": "0"},
-                "heads3_q128": {"ACE_GROUP": "3", "ACE_HEADS": "1", "ACE_HEADQ": "0"},
+    variants = {"single": {"ACE_PAIR": "0"}, "default": {},
+                "heads2": {"ACE_GROUP": "2"},
+                "heads3": {"ACE_GROUP": "3"},
+                "heads4": {"ACE_GROUP": "4"},
                 "heads4_unreserved": {"ACE_BULK_RESERVE": "0"},
                 "heads4_reserve2": {"ACE_BULK_RESERVE": "2"},
                 "heads4_q_beside": {"ACE_QFIRST": "0"},
                 "heads4_q_beside_unreserved": {"ACE_QFIRST": "0", "ACE_BULK_RESERVE": "0"},
-                "chain_unfused": {"ACE_CHAIN_FUSE": "0"},
-                "chain_fused_reserve2": {"ACE_CHAIN_FUSE": "1", "ACE_BULK_RESERVE": "2"},
-                "heads3_chain_fused": {"ACE_GROUP": "3", "ACE_HEADS": "1", "ACE_CHAIN_FUSE": "1"},
-                "bulk_curve": {"ACE_BULK_CURVE": "1"},
-                "bulk_curve_unreserved": {"ACE_BULK_CURVE": "1", "ACE_BULK_RESERVE": "0"},
-                "qsplit_off": {"ACE_QSPLIT": "0"}, "qsplit_q": {"ACE_QSPLIT": "3"},
-                "qsplit_boundary": {"ACE_QSPLIT": "2"},
-                "heads3_qsplit_off": {"ACE_GROUP": "3", "ACE_HEADS": "1", "ACE_QSPLIT": "0"},
-                "tail_last_off": {"ACE_TAIL_LAST": "0"},
-                "tail_last_off_qsplit_off": {"ACE_TAIL_LAST": "0", "ACE_QSPLIT": "0"},
                 "chain_xlds_off": {"ACE_CHAIN_XLDS": "0"},
-                "chain_xlds_first_only": {"ACE_CHAIN_XLDS_J": "1", "ACE_CHAIN_XLDS_G0": "0"}}
+                "large_n_regime": LARGE_N_REGIME,
+                "large_n_regime3": {**LARGE_N_REGIME, "ACE_GROUP": "3"}}
     for name, ev in variants.items():
         out = str(tmp_path / f"inv_{name}.npy")
         env = dict(os.environ, **ev)
@@ -565,26 +509,6 @@ def test_pair_steps_are_bitwise_neutral(A, tmp_path, n):
         outs[name] = np.load(out)
     for name in variants:
         assert np.array_equal(outs["single"], outs[name]), name
-
-
-def test_split_panel_is_bitwise_neutral(A, tmp_path):
-    """The column-split panel update (k_panel_split, default) performs
-    k_panel's arithmetic in k_panel's order over (NB/64)^2 workgroups: the
-    inverse is bit-identical to the row-group k_panel (ACE_CHAIN=0)."""
-    import os
-    import subprocess
-    import sys
-    from additivecausalexpansion_amd.synthetic import make_problem
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    n = 1300
-    y, X, Z, th, _ = make_problem(n, 4, 5, seed=17)
-    K = A.kernmat_SE_symmetric_cpp(X, Z, th)["full"]
-    inp = str(tmp_path / "k.npz")
-    np.savez(inp, K=K, s=th[0])
-    out = str(tmp_path / "inv0.npy")
-    env = dict(os.environ, ACE_CHAIN="0")
-    run_child(_ORDER_SNIPPET.format(root=root, inp=inp, out=out), env=env, timeout=100)
-    assert np.array_equal(A.invkernel_cpp(K, th[0])["inv"], np.load(out))
 
 
 _MODEL_SNIPPET = """
@@ -607,38 +531,33 @@ np.save({out!r}, np.concatenate(outs))
 @pytest.mark.parametrize("n", [2000, 2600])
 def test_model_schedules_are_bitwise_neutral(tmp_path, n):
     """The fused model's para_update gives the same gradient and stats bit
-    for bit, over two evaluations, under the group schedule at two and four
-    steps per bulk launch (ACE_HEADS=0) and the head / tail lookahead at four
-    (the default above n = 8192) and two.  n = 2000: 8 steps; 2600: 11 (a
-    last single step).  Also the default schedule under the smaller stream
+    for bit, over two evaluations, under the one-step reference schedule
+    (ACE_PAIR=0, the baseline) and the head / tail schedule at two, three and
+    four steps per bulk launch, with no override at all (at these n: Z = 3 on
+    three streams with the small-n bulk queue) and under exactly what
+    n > 8192 runs (LARGE_N_REGIME).  n = 2000: 8 steps; 2600: 11 (a last
+    single step).  Also the no-override schedule under the smaller stream
     budgets (ACE_STREAMS=2: the tail path on the panel stream; 1: everything
     on the main stream), which run the same launch graph serialised in host
-    order.  (Round 6 removed the round-2 pair schedule's merged
-    and split cross variants this test covered before.)"""
+    order."""
     import os
-    import subprocess
-    import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    variants = {"single": {"ACE_PAIR": "0"}, "default": {},
+                "heads4": {"ACE_GROUP": "4"}, "heads3": {"ACE_GROUP": "3"},
+                "heads2": {"ACE_GROUP": "2"}, "large_n_regime": LARGE_N_REGIME,
+                "streams2": {"ACE_STREAMS": "2"}, "streams1": {"ACE_STREAMS": "1"}}
     outs = {}
-    for v in ("0", "group4", "heads4", "heads2", "streams2", "streams1"):
+    for v, ev in variants.items():
         out = str(tmp_path / f"m{v}.npy")
-        env = (dict(os.environ, ACE_STREAMS=v[-1]) if v.startswith("streams") else
-               dict(os.environ, ACE_GROUP="4", ACE_HEADS="0") if v == "group4" else
-               dict(os.environ, ACE_GROUP="4", ACE_HEADS="1") if v == "heads4" else
-               dict(os.environ, ACE_GROUP="2", ACE_HEADS="1") if v == "heads2" else
-               dict(os.environ, ACE_GROUP="2", ACE_HEADS="0"))
-        run_child(_MODEL_SNIPPET.format(root=root, n=n, out=out), env=env, timeout=100)
+        run_child(_MODEL_SNIPPET.format(root=root, n=n, out=out), env=dict(os.environ, **ev),
+                  timeout=100)
         outs[v] = np.load(out)
-    assert np.all(np.isfinite(outs["0"]))
-    # four steps per bulk launch: the assembly's first part covers the first
-    # group's four panels, its side path runs under the rest
-    assert np.array_equal(outs["0"], outs["group4"])
-    # the head / tail lookahead split (ACE_HEADS=1) at four and two steps
-    assert np.array_equal(outs["0"], outs["heads4"])
-    assert np.array_equal(outs["0"], outs["heads2"])
-    # the default (heads4) on two streams and on one
-    assert np.array_equal(outs["heads4"], outs["streams2"])
-    assert np.array_equal(outs["heads4"], outs["streams1"])
+    assert np.all(np.isfinite(outs["single"]))
+    for v in ("default", "heads4", "heads3", "heads2", "large_n_regime"):
+        assert np.array_equal(outs["single"], outs[v]), v
+    # the no-override schedule on two streams and on one
+    assert np.array_equal(outs["default"], outs["streams2"])
+    assert np.array_equal(outs["default"], outs["streams1"])
 
 
 _MODEL_SNIPPET_K = _MODEL_SNIPPET.replace('"Matern32"', '{kernel!r}')

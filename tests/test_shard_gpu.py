@@ -215,8 +215,7 @@ def test_sharded_pair_schedule_is_bitwise_neutral(tmp_path, world, n):
     default) and the one-step schedule (ACE_PAIR=0) give bit-identical
     results: every tile sees the same MFMA chains in the same order; and so
     does the exchange packing fused into the cross launches (default)
-    against separate pack launches (ACE_FUSE_PACK=0), and the pair launches
-    on k_update_multi (default) against k_update_pair (ACE_MULTI2=0).  The
+    against separate pack launches (ACE_FUSE_PACK=0).  The
     default runs the head / tail schedule (round 5: the single-GPU lists, the
     exchange split into a head broadcast and a tail broadcast + all-gather);
     ACE_SHARD_HEADS=0 the group schedule without the split.  n
@@ -228,7 +227,7 @@ def test_sharded_pair_schedule_is_bitwise_neutral(tmp_path, world, n):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = {}
     variants = {"step": {"ACE_PAIR": "0"}, "pair": {"ACE_FUSE_PACK": "0"}, "fused": {},
-                "pair_kernel": {"ACE_MULTI2": "0"}, "groups": {"ACE_SHARD_HEADS": "0"}}
+                "groups": {"ACE_SHARD_HEADS": "0"}}
     for v, extra in variants.items():
         out = str(tmp_path / f"s{v}.npz")
         env = dict(os.environ, **extra)
