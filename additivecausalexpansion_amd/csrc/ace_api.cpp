@@ -171,8 +171,8 @@ int ace_kernmat_sym(ace_ctx *ctx, int kind, int64_t n, int p, int B, const doubl
   upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
   alloc(ctx, dK, (size_t)(n * n) * sizeof(double), "alloc Kfull");
   if (Kel) alloc(ctx, dC, (size_t)(n * n * B) * sizeof(double), "alloc cube");
-  ck(ctx, launch_assembly(1, kind, s.PM, sb.view(n), sb.view(n), n, B, s.ZS, tab_view(dtab, s),
-                          0.0, dK.d(), n, Kel ? dC.d() : nullptr, ctx->stream),
+  ck(ctx, launch_assembly(1, kind, s.PM, sb.view(n), sb.view(n), B, s.ZS, tab_view(dtab, s), dK.d(),
+                          n, Kel ? dC.d() : nullptr, ctx->stream),
      "assembly");
   download(ctx, Kfull, dK.d(), (size_t)(n * n), "download Kfull");
   if (Kel) download(ctx, Kel, dC.d(), (size_t)(n * n * B), "download cube");
@@ -198,9 +198,8 @@ int ace_kernmat_cross(ace_ctx *ctx, int kind, int64_t n1, int64_t n2, int p, int
   upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
   alloc(ctx, dK, (size_t)(n1 * n2) * sizeof(double), "alloc Kfull");
   if (Kel) alloc(ctx, dC, (size_t)(n1 * n2 * B) * sizeof(double), "alloc cube");
-  ck(ctx, launch_assembly(2, kind, s.PM, s1.view(n1), s2.view(n2), 0, B, s.ZS,
-                          tab_view(dtab, s), 0.0, dK.d(), n1, Kel ? dC.d() : nullptr,
-                          ctx->stream),
+  ck(ctx, launch_assembly(2, kind, s.PM, s1.view(n1), s2.view(n2), B, s.ZS, tab_view(dtab, s),
+                          dK.d(), n1, Kel ? dC.d() : nullptr, ctx->stream),
      "assembly");
   download(ctx, Kfull, dK.d(), (size_t)(n1 * n2), "download Kfull");
   if (Kel) download(ctx, Kel, dC.d(), (size_t)(n1 * n2 * B), "download cube");
@@ -509,7 +508,7 @@ static hipError_t asm_fill(void *arg, hipStream_t st) {
                                  f->naug, st, f->queue, 0, f->slots);
 }
 
-// A = Kfull + sig I (lower 64-tiles, assembly mode 0) into w.A with the AUG
+// A = Kfull + sig I (lower 64-tiles, launch_assembly_mm) into w.A with the AUG
 // rows [y; 1] (y null: the 1 row only), then the sweep.  The first sweep
 // group's panels' columns are assembled first: that group's pivot chains and
 // lookahead crosses (side stream) then run under the rest of the assembly.
@@ -524,15 +523,14 @@ void assemble_and_sweep(ace_ctx *ctx, SweepWork &w, const Shape &s, const PairSi
   // leaves R CUs of every shader engine to the first group's head path
   // (DESIGN §5); the queue is reset before anything can join it
   const int R = asm_persist_reserve();
-  const bool persist = R > 0 && sy.side && sy.nev >= 5 * steps + 6 && pairs_use_mm(s.PM, false) &&
-                       mm_lds_ok(s.PM, s.B, s.kind, false);
+  const bool persist = R > 0 && sy.side && sy.nev >= 5 * steps + 6;
   // (the flag and the persistent assembly's queue are zeroed by the same launch)
   ck(ctx, launch_aug_init(w.A.d(), w.naug, w.npad, n, y, st, 1, 0, w.flag.i(), 1,
                           persist ? w.aq.i() : nullptr, persist ? 2 + 64 : 0),
      "aug init");
   if (ev_asm) ck(ctx, hipEventRecord(ev_asm[0], st), "event");
-  ck(ctx, launch_assembly(0, s.kind, s.PM, ps, ps, w.npad, s.B, s.ZS, tv, sig, w.A.d(), w.naug,
-                          nullptr, st, nullptr, 0, 1, 1),
+  ck(ctx, launch_assembly_mm(s.kind, s.PM, ps, w.npad, s.B, s.ZS, tv, sig, w.A.d(), w.naug,
+                             nullptr, st, nullptr, 0, 1, 1),
      "assembly (first panel)");
   if (sy.side && sy.nev >= 2 * steps + 1) {  // run_sweep's "inputs ready" event
     ck(ctx, hipEventRecord(sy.ev[2 * steps], st), "event");
@@ -556,8 +554,8 @@ void assemble_and_sweep(ace_ctx *ctx, SweepWork &w, const Shape &s, const PairSi
       sy.fill_arg = &fill;
     }
   } else {
-    ck(ctx, launch_assembly(0, s.kind, s.PM, ps, ps, w.npad, s.B, s.ZS, tv, sig, w.A.d(), w.naug,
-                            nullptr, st, nullptr, 0, 1, 2),
+    ck(ctx, launch_assembly_mm(s.kind, s.PM, ps, w.npad, s.B, s.ZS, tv, sig, w.A.d(), w.naug,
+                               nullptr, st, nullptr, 0, 1, 2),
        "assembly");
   }
   // with the persistent queue this marks the MAIN launch's end: the tiles
@@ -594,13 +592,6 @@ void build_grad_tiles(ace_ctx *ctx, int64_t n, DBuf &tiles, int64_t *ntiles, int
   *ndiag = ntr;
 }
 
-// ACE_NORMS=0: every pair tile computes its own slice norms (A/B switch;
-// the table is bit-identical)
-static bool slice_norms_on() {
-  static const bool v = env_int("ACE_NORMS", 1) != 0;
-  return v;
-}
-
 namespace {
 
 // One evaluation on the stream.  theta_dev != nullptr: theta is a device
@@ -627,7 +618,7 @@ void model_pipeline(ace_model *m, SweepWork &w, const double *theta, int use_mu,
     sig = std::exp(theta[0]);
   }
   const PairSide ps = m->train_side();
-  if (m->norms.p) {  // the slice norms once per point, for the assembly and the gradient
+  {  // the slice norms once per point, for the assembly and the gradient
     const int NS = s.kind == ACE_KERNEL_MATERN32 ? s.B + 1 : s.B;
     ck(ctx, launch_slice_norms(ps.X, s.PM, m->npad, s.B, NS, tv.wk,
                                s.kind == ACE_KERNEL_MATERN32 ? tv.wg + (s.B - 1) * s.PM : tv.wk,
@@ -832,8 +823,7 @@ int ace_model_create(ace_ctx *ctx, int kind, int64_t n, int p, int B, ace_model 
     const Shape &s = m->s;
     alloc(ctx, m->y, (size_t)m->npad * sizeof(double), "alloc y");
     alloc(ctx, m->tab, (size_t)(2 * s.B * s.PM + s.B + 1) * sizeof(double), "alloc tab");
-    if (slice_norms_on())
-      alloc(ctx, m->norms, (size_t)((s.B + 1) * m->npad) * sizeof(double), "alloc norms");
+    alloc(ctx, m->norms, (size_t)((s.B + 1) * m->npad) * sizeof(double), "alloc norms");
     alloc(ctx, m->alpha, (size_t)m->npad * sizeof(double), "alloc alpha");
     const int ldg = grad_part_cols(s.PM, s.B);
     alloc(ctx, m->gpart, (size_t)(m->ntiles * ldg) * sizeof(double), "alloc gpart");
@@ -890,7 +880,7 @@ int ace_model_set_data(ace_model *m, const double *y, const double *X, const dou
   // order and the blocks' slice masks are computed here, once.  2: the device
   // holds the points grouped by pattern (a symmetric relabelling of A: every
   // sum over training points is unchanged up to rounding); 1: the given
-  // order with its masks; 0, B = 1, or the all-VALU pair kernels: neither.
+  // order with its masks; 0 or B = 1: neither.
   const Shape &s = m->s;
   const int64_t n = m->n;
   const int zs = s.B - 1, mode = zskip_mode(n);
@@ -898,8 +888,7 @@ int ace_model_set_data(ace_model *m, const double *y, const double *X, const dou
   m->has_zmask = false;
   std::vector<double> Xp, Zp, yp((size_t)m->npad, 0.0);
   std::copy(y, y + n, yp.begin());
-  if (mode > 0 && zs >= 1 && zs <= 32 && pairs_use_mm(s.PM, false) &&
-      mm_lds_ok(s.PM, s.B, s.kind, false) && mm_lds_ok(s.PM, s.B, s.kind, true)) {
+  if (mode > 0 && zs >= 1 && zs <= 32) {
     const uint32_t all = zs >= 32 ? 0xffffffffu : ((uint32_t)1 << zs) - 1;
     std::vector<uint32_t> bm((size_t)(m->npad / AT), all);  // blocks of padding: every slice
     std::vector<int64_t> perm((size_t)n);

@@ -103,8 +103,8 @@ const double *values(ace_dmat *h) {
     const KernSrc &k = *h->src;
     const Shape &s = k.shape;
     alloc(ctx, h->buf, (size_t)(n1 * n2) * sizeof(double), "alloc Kfull");
-    ck(ctx, launch_assembly(1, s.kind, s.PM, k.s1->view(n1), k.s1->view(n1), n1, s.B, s.ZS,
-                            tab_view(k.tab, s), 0.0, h->buf.d(), n1, nullptr, st),
+    ck(ctx, launch_assembly(1, s.kind, s.PM, k.s1->view(n1), k.s1->view(n1), s.B, s.ZS,
+                            tab_view(k.tab, s), h->buf.d(), n1, nullptr, st),
        "assembly");
     sync(ctx);
   } else {
@@ -114,8 +114,8 @@ const double *values(ace_dmat *h) {
     alloc(ctx, full, (size_t)(n1 * n2) * sizeof(double), "alloc Kfull");
     alloc(ctx, h->buf, (size_t)(n1 * n2 * s.B) * sizeof(double), "alloc cube");
     const PairSide a = k.s1->view(n1), b = k.symmetric ? k.s1->view(n1) : k.s2->view(n2);
-    ck(ctx, launch_assembly(k.symmetric ? 1 : 2, s.kind, s.PM, a, b, 0, s.B, s.ZS,
-                            tab_view(k.tab, s), 0.0, full.d(), n1, h->buf.d(), st),
+    ck(ctx, launch_assembly(k.symmetric ? 1 : 2, s.kind, s.PM, a, b, s.B, s.ZS, tab_view(k.tab, s),
+                            full.d(), n1, h->buf.d(), st),
        "cube assembly");
     sync(ctx);
   }
@@ -145,9 +145,8 @@ const double *marginal_rows(ace_dmat *h, int64_t r0, int64_t nr, int64_t *ld, DB
     // the symmetric form's r < c ordering (mode 1) is only kept when the
     // block is the whole square matrix; row blocks use the cross form,
     // whose slice values agree with it to the last bit but the zero tests
-    ck(ctx, launch_assembly(symmetric && r0 == 0 && nr == h->rows ? 1 : 2, s.kind, s.PM, a, b, 0,
-                            B, s.ZS, tab_view(k.tab, s), 0.0, scratch.d(), nr, nullptr, st,
-                            nullptr, 0, 1, 0, b0, b1),
+    ck(ctx, launch_assembly(symmetric && r0 == 0 && nr == h->rows ? 1 : 2, s.kind, s.PM, a, b, B,
+                            s.ZS, tab_view(k.tab, s), scratch.d(), nr, nullptr, st, b0, b1),
        "marginal assembly");
   } else {
     // dense (or materialised) cube: the marginal slice sum is formed once and
@@ -326,9 +325,9 @@ int ace_dmat_read(const ace_dmat *hc, int64_t offset, int64_t count, double *out
         alloc(ctx, h->slice, (size_t)sl * sizeof(double), "alloc slice");
         h->slice_b = -1;
         const PairSide a = k.s1->view(h->rows), c = k.symmetric ? k.s1->view(h->rows) : k.s2->view(h->cols);
-        ck(ctx, launch_assembly(k.symmetric ? 1 : 2, s.kind, s.PM, a, c, 0, s.B, s.ZS,
-                                tab_view(k.tab, s), 0.0, h->slice.d(), h->rows, nullptr, ctx->stream,
-                                nullptr, 0, 1, 0, (int)b, (int)b + 1),
+        ck(ctx, launch_assembly(k.symmetric ? 1 : 2, s.kind, s.PM, a, c, s.B, s.ZS,
+                                tab_view(k.tab, s), h->slice.d(), h->rows, nullptr, ctx->stream,
+                                (int)b, (int)b + 1),
            "slice assembly");
       }
       download(ctx, out + (lo - offset), h->slice.d() + (lo - b * sl), (size_t)(hi - lo),
@@ -422,8 +421,8 @@ int ace_kernmat_cross_dev(ace_ctx *ctx, int kind, int64_t n1, int64_t n2, int p,
   std::unique_ptr<ace_dmat> E(new_handle(ctx, ace_dmat::CUBE, n1, n2, B));
   E->src = src;
   alloc(ctx, K->buf, (size_t)(n1 * n2) * sizeof(double), "alloc Kfull");
-  ck(ctx, launch_assembly(2, kind, s.PM, src->s1->view(n1), src->s2->view(n2), 0, B, s.ZS,
-                          tab_view(src->tab, s), 0.0, K->buf.d(), n1, nullptr, ctx->stream),
+  ck(ctx, launch_assembly(2, kind, s.PM, src->s1->view(n1), src->s2->view(n2), B, s.ZS,
+                          tab_view(src->tab, s), K->buf.d(), n1, nullptr, ctx->stream),
      "assembly");
   sync(ctx);
   *full = K.release();

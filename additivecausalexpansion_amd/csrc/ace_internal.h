@@ -33,6 +33,7 @@ constexpr int PMAX = 64;   // largest supported covariate count p
 constexpr int BMAX = 32;   // largest supported component count B
 
 // Feature-count buckets the pair kernels are compiled for.
+constexpr int PM_BUCKETS[] = {4, 8, 12, 16, 20, 24, 32, 48, PMAX};
 int pm_bucket(int p);  // smallest compiled bucket >= p, or -1
 
 // ---- column sharding ---------------------------------------------------------
@@ -90,32 +91,32 @@ struct PairSide {
 int zskip_mode(int64_t n);
 
 // ---- assembly --------------------------------------------------------------
-// mode 0: fused eval -- lower 64-tiles of the n_pad x n_pad block of A (ld),
-//         value K + sig on the diagonal, identity on padding rows/cols; if
-//         cube is non-null it receives the lower Kfull (same ld).
-// mode 1: symmetric ABI output -- full n x n Kfull (ld = n) + optional cube.
-// mode 2: cross ABI output -- n1 x n2 Kfull + optional cube.
-// part (mode 0 without a tile list): 0 all tiles, 1 the first two panels'
-// columns (J < 2 NB/AT), 2 the rest -- 1 then 2 lets the sweep's first
-// group of pivot chains (and the cross of block 1) run while part 2 runs.
-// b0 / b1 (modes 1 and 2, no cube): sum only slices [b0, b1) -- the
-// marginal kernels of prediction (src/pred_cpp.cpp:55-67); b1 < 0 means B.
-hipError_t launch_assembly(int mode, int kind, int PM, PairSide rows,
-                           PairSide cols, int64_t npad, int B, int ZS,
-                           TabView tab, double sig, double *out, int64_t ld,
-                           double *cube, hipStream_t st, const Tile *tiles = nullptr,
-                           int64_t ntiles = 0, int G = 1, int part = 0, int b0 = 0,
-                           int b1 = -1);
+// The ABI's kernel matrices (the fused model's assembly is
+// launch_assembly_mm below):
+// mode 1: symmetric output -- full n x n Kfull (ld = n) + optional cube.
+// mode 2: cross output -- n1 x n2 Kfull + optional cube.
+// b0 / b1 (no cube): sum only slices [b0, b1) -- the marginal kernels of
+// prediction (src/pred_cpp.cpp:55-67); b1 < 0 means B.
+hipError_t launch_assembly(int mode, int kind, int PM, PairSide rows, PairSide cols, int B, int ZS,
+                           TabView tab, double *out, int64_t ld, double *cube, hipStream_t st,
+                           int b0 = 0, int b1 = -1);
 // out[r] = sum over b in [b0, b1) of K_b(r, r) (symmetric kernel diagonal)
 hipError_t launch_kdiag(int kind, PairSide S, int ZS, TabView tab, int b0, int b1, double *out,
                         hipStream_t st);
 
-// MFMA-expansion variant of mode 0 (ace_pairs_mm.hip)
+// The fused model's assembly (ace_pairs_mm.hip): lower 64-tiles of the
+// npad x npad block of A (ld), value K + sig on the diagonal, identity on
+// padding rows / columns; kcopy, if non-null, receives the lower Kfull (same
+// ld).  tiles: a rank's own lower tiles (ntiles of them, G ranks).
+// part (without a tile list): 0 all tiles, 1 the first sweep group's panels'
+// columns, 2 the rest -- 1 then 2 lets the sweep's first group of pivot
+// chains and lookahead crosses run while part 2 runs; 3 part 2's diagonal
+// tiles alone (beside launch_assembly_persist).
 hipError_t launch_assembly_mm(int kind, int PM, PairSide S, int64_t npad, int B, int ZS,
                               TabView tab, double sig, double *out, int64_t ld,
                               double *kcopy, hipStream_t st, const Tile *tiles,
                               int64_t ntiles, int G, int part = 0);
-// the assembly's second part (part 2 of mode 0) as a persistent work queue
+// the assembly's second part (part 2 above) as a persistent work queue
 // that leaves `reserve` CU ids of shader engine 0 of every XCD free (queue:
 // two device ints, reset here on the stream)
 hipError_t launch_assembly_persist(int kind, int PM, PairSide S, int64_t npad, int B, int ZS,
@@ -123,9 +124,6 @@ hipError_t launch_assembly_persist(int kind, int PM, PairSide S, int64_t npad, i
                                    hipStream_t st, int *queue, int reserve, int fill = 0);
 // workgroup slots of one CU for the persistent assembly (0 if unknown)
 int assembly_persist_per_cu(int kind, int PM, int B);
-bool pairs_use_mm(int PM, bool grad);
-bool mm_lds_ok(int PM, int B, int kind, bool grad);
-bool cross_mm_lds_ok(int PM, int B, int kind);
 // mode 2 without a cube on the MFMA r2 expansion (k_cross_mm): R.n x C.n, ld
 hipError_t launch_cross_mm(int kind, int PM, PairSide R, PairSide C, int B, int ZS, TabView tab,
                            int b0, int b1, double *out, int64_t ld, hipStream_t st);
@@ -139,8 +137,7 @@ hipError_t launch_cross_slices_mm(int kind, int PM, PairSide R, PairSide C, int 
 // marginal kernel Km of slices [b0, b1) on the points S and the indicator
 // E[c][h] = (label[c] == h), labels in [-1, G), 1 <= G <= 64; Km is never
 // stored.  part: group_sums_parts(S.n) * S.n * G doubles of partial sums,
-// reduced in a fixed order (bitwise reproducible).  The VALU form runs when
-// the MFMA kernel's staging does not fit in LDS or ACE_PAIRS=valu is set.
+// reduced in a fixed order (bitwise reproducible).
 int group_sums_parts(int64_t n);
 hipError_t launch_group_sums(int kind, int PM, PairSide S, int B, int ZS, TabView tab, int b0,
                              int b1, const int *label, int G, double *part, double *R,
@@ -157,7 +154,8 @@ hipError_t launch_grad_mm(int kind, int PM, PairSide S, int B, int ZS, TabView t
 //        doubles per tile: [b*(PM+1) + i] (i < PM: length-scale sums,
 //        i == PM: lambda sums), then [B*(PM+1)] the trace of T.  Each tile's
 //        workgroup writes one contiguous run (launch_tile_sums reduces).
-// cube (if non-null, ld n): K_b read from the cube instead of recomputed.
+// cube (if non-null, ld n): up to PM = 48 K_b is read from it (k_grad);
+// without one, or above, the MFMA kernel recomputes K_b (launch_grad_mm).
 // tiles: the rank's list; ndiag >= 0 says its first ndiag entries are the
 // diagonal tiles (lets the MFMA kernel run them separately).
 __host__ __device__ constexpr int grad_part_cols(int PM, int B) { return B * (PM + 1) + 1; }

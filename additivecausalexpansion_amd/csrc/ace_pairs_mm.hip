@@ -37,40 +37,11 @@ namespace ace {
 // assembly 3 up to PM = 32 and 2 above (3 would spill at PM = 64).
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-// Pairs per scheduling group in the elementwise loops (a sched_barrier after
-// every ACE_MM_PG pairs bounds live ranges; 0 = no barriers).
-#ifndef ACE_MM_PG
-#define ACE_MM_PG 2
-#endif
-// Waves per SIMD the 512-thread gradient kernel is compiled for (register cap).
-#ifndef ACE_MM_GRAD_WPE
-#define ACE_MM_GRAD_WPE 4
-#endif
-// Most GEMM2 column blocks accumulated per pass of its k-loop (QG2: the
-// 512-thread form, whose register cap allowed one).
-#ifndef ACE_MM_QG
-#define ACE_MM_QG 4
-#endif
-#ifndef ACE_MM_QG2
-#define ACE_MM_QG2 1
-#endif
-// GEMM2's last column block when PM is not a multiple of 16 (p = 20: 4 live
-// features of 16): on v_mfma_f64_4x4x4_4b_f64 (ACE_GRAD_TAIL4=1, default),
-// one 4-feature group per instruction at 17 cycles instead of a 16-wide
-// block at 64 (profiles/r04_probe_mfma_f64.txt: 4 blocks of 4x4x4, A lane
-// 16k + 4m + i, B lane 16k + 4m + j, D lane 16i + 4m + j for block m).  The
-// GEMM1 result fragment is its A operand as it stands: lane (lr = 4m + i,
-// lk = k) holds U[row lr][column 4kk + k] for k-step kk.
-#ifndef ACE_GRAD_TAIL4
-#define ACE_GRAD_TAIL4 1
-#endif
-// timing diagnostics of k_grad_mm's slice loop (results wrong; see there)
-#ifndef ACE_DIAG_GRAD
-#define ACE_DIAG_GRAD 0
-#endif
+// Pairs per scheduling group in the elementwise loops: a sched_barrier after
+// every PAIR_GROUP pairs bounds live ranges.
+constexpr int PAIR_GROUP = 2;
 #define MM_PAIR_FENCE(cb, v) \
-  if (ACE_MM_PG > 0 && ((4 * (cb) + (v) + 1) % (ACE_MM_PG > 0 ? ACE_MM_PG : 1)) == 0) \
-    __builtin_amdgcn_sched_barrier(0)
+  if ((4 * (cb) + (v) + 1) % PAIR_GROUP == 0) __builtin_amdgcn_sched_barrier(0)
 
 #define SQRT3 1.7320508075688772
 
@@ -89,12 +60,13 @@ __device__ __forceinline__ double sgn_mm(double x) {
 
 // exp(x) without the library's special-case handling: every argument here is
 // lam - r2 (+ log|z| terms) or lam - sqrt3 t, finite and bounded above by the
-// amplitude parameter.  x = (32 m + j) ln2/32 + r, |r| <= ln2/64:
-// exp(x) = 2^m * 2^(j/32) * p(r), p the degree-6 Taylor polynomial
-// (truncation < 4e-18), 2^(j/32) from a 32-entry LDS table (correctly
-// rounded by the host's pow).  Arguments below about -745 give 0 like exp()
-// (v_cvt_i32_f64 saturates, so even huge negative ones); never called with
-// -inf (the SE path selects 0 for z = 0 before its log|z| terms matter).
+// amplitude parameter.  x = (N m + j) ln2/N + r, |r| <= ln2/(2 N):
+// exp(x) = 2^m * 2^(j/N) * p(r), p a degree-5 Taylor polynomial and 2^(j/N)
+// from an N-entry LDS table, correctly rounded; N = 32 for the gradient
+// (exp_tb5), 64 for the assembly and the cross tiles (exp_tb64).  Arguments
+// below about -745 give 0 like exp() (v_cvt_i32_f64 saturates, so even huge
+// negative ones); never called with -inf (the SE path selects 0 for z = 0
+// before its log|z| terms matter).
 __device__ const double kExp2Tab[32] = {
     1,
     1.0218971486541166,
@@ -129,23 +101,8 @@ __device__ const double kExp2Tab[32] = {
     1.9152065613971474,
     1.9571441241754002};
 
-__device__ __forceinline__ double exp_tb(double x, const double *tab) {
-  const double kf = __builtin_rint(x * 46.16624130844683);  // 32 / ln2
-  double r = fma(-kf, 0.02166084938653512, x);               // (ln2 / 32) hi
-  r = fma(-kf, 5.9631716539705866e-12, r);                   // (ln2 / 32) lo
-  const int ki = (int)kf;
-  double q = 1.0 / 720.0;
-  q = fma(q, r, 1.0 / 120.0);
-  q = fma(q, r, 1.0 / 24.0);
-  q = fma(q, r, 1.0 / 6.0);
-  q = fma(q, r, 0.5);
-  q = fma(q, r, 1.0);
-  q = fma(q, r, 1.0);
-  return __builtin_amdgcn_ldexp(q * tab[ki & 31], ki >> 5);
-}
-
-// exp_tb with a degree-5 polynomial (truncation < 2.3e-15 relative) for the
-// gradient's trace factors (the assembly keeps exp_tb: K enters the inverse)
+// the 32-entry table, |r| <= ln2/64 (truncation < 2.3e-15 relative): the
+// gradient's trace factors (K itself enters the inverse: exp_tb64 below)
 __device__ __forceinline__ double exp_tb5(double x, const double *tab) {
   const double kf = __builtin_rint(x * 46.16624130844683);
   double r = fma(-kf, 0.02166084938653512, x);
@@ -160,11 +117,6 @@ __device__ __forceinline__ double exp_tb5(double x, const double *tab) {
   return __builtin_amdgcn_ldexp(q * tab[ki & 31], ki >> 5);
 }
 
-// exp of the assembly and the cross tiles (K enters the inverse): 2 (default)
-// exp_tb64 below, 0 exp_tb
-#ifndef ACE_ASM_EXP
-#define ACE_ASM_EXP 2
-#endif
 // 2^(j/64), j = 0..63, correctly rounded (Python Decimal at 60 digits)
 __device__ const double kExp2Tab64[64] = {
     1.0, 1.0108892860517005, 1.0218971486541166, 1.0330248790212284,
@@ -184,9 +136,9 @@ __device__ const double kExp2Tab64[64] = {
     1.8340080864093424, 1.8539791250833855, 1.8741676341103, 1.8945759815869656,
     1.9152065613971474, 1.9360617934922943, 1.9571441241754002, 1.978456026387951,
 };
-// exp for the assembly (ACE_ASM_EXP=2, default): the 64-entry table, |r| <=
-// ln2/128, degree-5 Taylor (truncation < 3.6e-17 relative, below half an ulp
-// like exp_tb's degree 6) -- one FMA fewer per pair and slice than exp_tb
+// exp of the assembly and the cross tiles (K enters the inverse): the
+// 64-entry table, |r| <= ln2/128 (truncation < 3.6e-17 relative, below half
+// an ulp)
 __device__ __forceinline__ double exp_tb64(double x, const double *tab) {
   const double kf = __builtin_rint(x * 92.33248261689366);  // 64 / ln2
   double r = fma(-kf, 0.02166084938653512 * 0.5, x);          // (ln2 / 64) hi
@@ -200,10 +152,6 @@ __device__ __forceinline__ double exp_tb64(double x, const double *tab) {
   q = fma(q, r, 1.0);
   return __builtin_amdgcn_ldexp(q * tab[ki & 63], ki >> 6);
 }
-__device__ __forceinline__ double exp_asm(double x, const double *tab) {
-  return ACE_ASM_EXP == 2 ? exp_tb64(x, tab) : exp_tb(x, tab);
-}
-
 
 // sqrt(x), x >= 0 and normal or 0 (r2 values): hardware rsq (~2^-24
 // relative), one Goldschmidt step and one correction -- 0 ulp against the
@@ -259,11 +207,11 @@ template <int KIND>
 __device__ __forceinline__ double kval_nb(double r2, double lam, double zlo, double zhi,
                                           double lzlo, double lzhi, const double *etab) {
   if (KIND == 0) {
-    const double kz = (sgn_mm(zlo) * sgn_mm(zhi)) * exp_asm(((lam - r2) + lzlo) + lzhi, etab);
+    const double kz = (sgn_mm(zlo) * sgn_mm(zhi)) * exp_tb64(((lam - r2) + lzlo) + lzhi, etab);
     return sel_f64(zlo == 0.0 || zhi == 0.0, 0.0, kz);
   } else {
     const double t = sqrt_pk_pos(r2);
-    const double e = (1.0 + SQRT3 * t) * exp_asm(lam - SQRT3 * t, etab);
+    const double e = (1.0 + SQRT3 * t) * exp_tb64(lam - SQRT3 * t, etab);
     return (e * zlo) * zhi;
   }
 }
@@ -325,12 +273,13 @@ struct MmLayout {
 // loop) when that fits in 40 KB, else two buffers and a barrier per slice.
 // Per slice: [NWV][PM + 1] (x part of every feature, sum T K) and the
 // column sums of U of the four row blocks, [4][64].
-__host__ __device__ inline MmLayout mm_layout(int PM, int B, int KIND, bool grad, int nwave = 4) {
-  MmLayout o;
+__host__ __device__ constexpr MmLayout mm_layout(int PM, int B, int KIND, bool grad,
+                                                 int nwave = 4) {
+  MmLayout o{};
   const int NS = (grad && KIND == 1) ? B + 1 : B;
   int off = 0;
   o.etab = off;
-  off += (!grad && ACE_ASM_EXP == 2) ? 64 : 32;
+  off += grad ? 32 : 64;  // kExp2Tab / kExp2Tab64
   o.xj = off;
   off += 64 * xj_pitch(PM);
   o.xi = off;
@@ -398,7 +347,7 @@ __device__ __forceinline__ MmLds mm_stage(double *lds, PairSide S, int B, int ZS
     L.Z[tid - 64] = 1.0;
     if (KIND == 0) L.LZ[tid - 64] = 0.0;
   }
-  if (!GRAD && ACE_ASM_EXP == 2) {
+  if (!GRAD) {
     if (tid < 64) L.E[tid] = kExp2Tab64[tid];
   } else if (tid < 32) {
     L.E[tid] = kExp2Tab[tid];
@@ -406,9 +355,10 @@ __device__ __forceinline__ MmLds mm_stage(double *lds, PairSide S, int B, int ZS
   for (int e = tid; e < NS * PM; e += NT) L.W[e] = (e < B * PM) ? wk[e] : wlast[e - B * PM];
   __syncthreads();
   // norms: from the per-evaluation table (launch_slice_norms, the same
-  // arithmetic once per point instead of once per tile: bit-identical), or
-  // task = (side, slice, point), same accumulation order as the per-slice
-  // loops they replace (i ascending, fma(x^2, w, s)).  (Round 5: issuing
+  // arithmetic once per point instead of once per tile: bit-identical), or,
+  // for callers without a table (the sharded model, the standalone ABI
+  // gradient), task = (side, slice, point), same accumulation order as the
+  // per-slice loops they replace (i ascending, fma(x^2, w, s)).  (Round 5: issuing
   // every staging load before the first LDS store, as in k_panel_split's
   // prologue, measured 2.47 -> 2.53 ms for the assembly at C2 and left the
   // gradient tiles' prologue at 13 us -- there the tile's other workgroup
@@ -528,9 +478,8 @@ hipError_t launch_slice_norms(const double *X, int PM, int64_t np, int B, int NS
 }
 
 // ---------------------------------------------------------------------------
-// Fused assembly (mode 0): lower 64-tiles of A (sigma on the diagonal,
-// identity on padding) and of the Kfull copy; same outputs as
-// k_assembly<PM, KIND, 0>.
+// Fused assembly: lower 64-tiles of A (sigma on the diagonal, identity on
+// padding) and of the Kfull copy.
 // ---------------------------------------------------------------------------
 // tile columns of the assembly's first part (model_pipeline): the first
 // sweep group's panels' columns (sweep_group() blocks), at most all of them
@@ -675,9 +624,7 @@ __global__ __launch_bounds__(ASM_NT, PM <= 32 ? 3 : 2) void k_asm_mm(
 // cross term one GEMM1 (K = PM) on v_mfma_f64_16x16x4f64, K_b per pair on
 // the VALU in the GEMM's fragment layout; both sides' slice norms computed
 // per tile (i ascending, fma(x^2, w, s), as k_slice_norms).  Out of range
-// rows / columns are staged as zeros and never written.  Replaces
-// k_assembly<PM, KIND, 2> (lane = row, p FMAs per pair and slice on the
-// VALU: 10.8 TF/s at n = 16384, nx = 4096).
+// rows / columns are staged as zeros and never written.
 // ---------------------------------------------------------------------------
 // The two-sided tile (k_cross_mm, k_cross_slices_mm, k_group_mm).  Its LDS
 // is the assembly's layout with the row side's 64 points XI behind it at the
@@ -731,8 +678,7 @@ __device__ __forceinline__ void cross_stage_tab(double *E, double *Zc, double *L
   if (tid < 64) {
     Zc[tid - 64] = 1.0;
     if (KIND == 0) LZc[tid - 64] = 0.0;
-    if (ACE_ASM_EXP == 2) E[tid] = kExp2Tab64[tid];
-    else if (tid < 32) E[tid] = kExp2Tab[tid];
+    E[tid] = kExp2Tab64[tid];
   }
   for (int e = tid; e < B * PM; e += 256) W[e] = tab.wk[e];
 }
@@ -899,7 +845,7 @@ __global__ __launch_bounds__(ASM_NT, PM <= 24 ? 4 : PM <= 32 ? 3 : 2) void k_asm
 }
 
 // ---------------------------------------------------------------------------
-// Fused gradient traces (same outputs as k_grad2): per slice b (descending),
+// Fused gradient traces: per slice b (descending),
 //   GEMM1  G = X_J (w_b X_I)^T          -> r2, K_b, U = T K_b [/ (1 + sqrt(3 r~2_b))]
 //   GEMM2  V = U X_J                    -> for every feature i
 //          sum_rc U d_i^2 = sum_r x_ri^2 R_r + sum_c x_ci^2 C_c - 2 sum_r x_ri V_ri
@@ -974,7 +920,7 @@ __device__ __forceinline__ double add_xor32(double v) {
 //   the 16 lanes of a row group (log2 16 shuffle levels), the four row
 //   blocks' sums meet in LDS and sum_c x_ci^2 C_c is formed once per slice.
 template <int PM, int KIND, int CB, bool PS, bool DG>
-__global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2)) void k_grad_mm(
+__global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? 4 : 2)) void k_grad_mm(
     PairSide S, int B, int ZS, TabView tab, const double *__restrict__ A, int64_t ld, double sA,
     const double *__restrict__ alpha, double *__restrict__ gpart, int64_t ldg,
     const Tile *__restrict__ tiles, int G, int64_t t0) {
@@ -985,14 +931,21 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
   constexpr bool XIL = PM <= 32;             // row covariates staged in LDS
   constexpr int NV = PM + 1;
   constexpr int NQ = (PM + 15) / 16;         // GEMM2 16-wide column blocks
-  // the last block's PM % 16 features on 4x4x4 MFMAs (NT4 groups of 4); not
-  // in the Matern two-buffer form (large B), where it would spill at 128 VGPRs
-  constexpr bool TAIL4 = ACE_GRAD_TAIL4 && (PM % 16) != 0 && (PS || KIND == 0);
+  // GEMM2's last column block when PM is not a multiple of 16 (p = 20: 4 live
+  // features of 16): on v_mfma_f64_4x4x4_4b_f64, one 4-feature group (NT4 of
+  // them) per instruction at 17 cycles instead of a 16-wide block at 64
+  // (profiles/r04_probe_mfma_f64.txt: 4 blocks of 4x4x4, A lane 16k + 4m + i,
+  // B lane 16k + 4m + j, D lane 16i + 4m + j for block m).  The GEMM1 result
+  // fragment is its A operand as it stands: lane (lr = 4m + i, lk = k) holds
+  // U[row lr][column 4kk + k] for k-step kk.  Not in the Matern two-buffer
+  // form (large B), where it would spill at 128 VGPRs
+  constexpr bool TAIL4 = (PM % 16) != 0 && (PS || KIND == 0);
   constexpr int NT4 = TAIL4 ? (PM % 16) / 4 : 0;
   constexpr int NQF = TAIL4 ? NQ - 1 : NQ;   // blocks on v_mfma_f64_16x16x4f64
-  // GEMM2 column blocks per pass of its k-loop (one at CB = 2: register cap)
-  constexpr int QG0 = CB == 2 ? (NQF < ACE_MM_QG2 ? NQF : ACE_MM_QG2) : (NQF < ACE_MM_QG ? NQF : ACE_MM_QG);
-  constexpr int QG = QG0 > 0 ? QG0 : 1;  // (NQF = 0: the loop below does not run)
+  // GEMM2 column blocks per pass of its k-loop: at most 4, one at CB = 2
+  // (register cap); NQF = 0: the loop below does not run
+  constexpr int QGMAX = CB == 2 ? 1 : 4;
+  constexpr int QG = NQF < 1 ? 1 : NQF < QGMAX ? NQF : QGMAX;
   constexpr int RS = PM + 1;                 // partial row: [x part | T K]
   constexpr int PER = NWV * RS + 4 * 64;     // per-slice partials (+ column sums)
   constexpr int NKK = 4 * CB;                // GEMM2 k-steps (the wave's columns / 4)
@@ -1117,7 +1070,7 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
           const int cl = 16 * cb + lk + 4 * v;
           double r2 = fmax(fma(-2.0, acc[cb][v], sr + nc[cl]), 1e-300);
           if (DG && C0 + cbase + cl == r) r2 = 1e-300;
-          const double tt = (ACE_DIAG_GRAD & 4) ? r2 : sqrt_gs(r2);
+          const double tt = sqrt_gs(r2);
           fc[cb][v] = fma(SQRT3, tt, 1.0);  // one rounding, as in the slice loop
         }
     }
@@ -1157,11 +1110,6 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
   // of ones / zeros; exact), so no per-pair code tests b: a lane's pairs are
   // one straight-line block the scheduler can interleave (a b == 0 test made
   // every pair its own basic block, running its dependent fp64 chain alone)
-  // ACE_DIAG_GRAD (timing diagnostics only, results wrong): 1 runs no slice,
-  // 2 only the last slice; bits 4 / 8 / 16 / 32 drop the sqrt / exp /
-  // reciprocal / GEMM2 of the Matern slice loop; bit 64 the per-slice
-  // partials' combination after the loop (column-sum combine + feature dots)
-  const int bstop = (ACE_DIAG_GRAD & 3) == 1 ? B : (ACE_DIAG_GRAD & 3) == 2 ? B - 1 : 0;
   // Skipped slices (tile_slices): every U of the slice is a zero of either
   // sign, so its partial sums are written as 0.0 here and its Red buffer
   // stays unwritten (the combines below pass over it).  nrun: slices run so
@@ -1169,7 +1117,7 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
   // still lies between two uses of a buffer.
   int nrun = 0;
 #pragma unroll 1
-  for (int b = B - 1; b >= bstop; --b) {
+  for (int b = B - 1; b >= 0; --b) {
     if (!slice_on(act, b)) {
       if (tid < NV) gpart[t * ldg + (int64_t)b * NV + tid] = 0.0;
       continue;
@@ -1214,11 +1162,11 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
                             exp_tb5(((lam - r2) + (rlo ? lzr : lzc)) + (rlo ? lzc : lzr), L.E);
           kb = sel_f64(zlo == 0.0 || zhi == 0.0, 0.0, kz);
         } else {
-          const double tt = (ACE_DIAG_GRAD & 4) ? r2 : sqrt_gs(r2);
+          const double tt = sqrt_gs(r2);
           // (an explicit fma -- what the compiler contracted 1 + sqrt3 t to
           // anyway -- so that the factor pass above forms the same bits)
           f = fma(SQRT3, tt, 1.0);
-          const double e = (ACE_DIAG_GRAD & 8) ? f * (lam - SQRT3 * tt) : f * exp_tb5(lam - SQRT3 * tt, L.E);
+          const double e = f * exp_tb5(lam - SQRT3 * tt, L.E);
           // z = 0 gives a zero product (of either sign: it only enters sums)
           kb = (e * zlo) * zhi;
         }
@@ -1228,7 +1176,7 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
         if (KIND == 0) {
           u = tk;
         } else {
-          u = (ACE_DIAG_GRAD & 16) ? tk * fc[cb][v] : tk * rcp_nr_mm(fc[cb][v]);
+          u = tk * rcp_nr_mm(fc[cb][v]);
           fc[cb][v] = f;
         }
         acc[cb][v] = u;
@@ -1244,7 +1192,7 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
     __builtin_amdgcn_s_setprio(2);
     // GEMM2: V = U X_J, QG column blocks per pass of the k-loop
 #pragma unroll
-    for (int q0 = 0; q0 < ((ACE_DIAG_GRAD & 32) ? 0 : NQF); q0 += QG) {
+    for (int q0 = 0; q0 < NQF; q0 += QG) {
       d4 a2[QG];
 #pragma unroll
       for (int j = 0; j < QG; ++j) a2[j] = d4{0.0, 0.0, 0.0, 0.0};
@@ -1279,7 +1227,7 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
         if (lk == 0 && nn < PM) red[w * RS + nn] = part;
       }
     }
-    if (TAIL4 && !(ACE_DIAG_GRAD & 32)) {
+    if (TAIL4) {
       // V[row 4 m4 + i4][feature 16 NQF + 4 t + j4] = sum_c U X_J over the
       // wave's columns: 4x4x4 MFMAs, k-step kk = columns 4 kk .. 4 kk + 3
       double a4[NT4 > 0 ? NT4 : 1];
@@ -1361,7 +1309,7 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
   double *str = L.Red + L.red_slices * PER;
   if (lane == 0) str[w] = tr;
   __syncthreads();
-  if (per_slice && !(ACE_DIAG_GRAD & 64)) {  // all slices' partials at once
+  if (per_slice) {  // all slices' partials at once
     // each slice's four row-block column sums added once (same expression,
     // so bit-identical), not once per feature
     for (int e = tid; e < B * 64; e += NT) {
@@ -1388,13 +1336,45 @@ __global__ __launch_bounds__(64 * 4 * (4 / CB), (CB == 2 ? ACE_MM_GRAD_WPE : 2))
 // Column blocks per wave of the gradient kernel: CB = 2 (512 threads, 8
 // pairs per lane, 4 waves per SIMD) wherever it fits 128 VGPRs without
 // spilling -- every SE case and Matern up to PM = 32 -- else CB = 4.
-// ACE_MM_GRAD_CB=4 forces the 256-thread form (A/B switch).
-#ifndef ACE_MM_GRAD_CB
-#define ACE_MM_GRAD_CB 2
-#endif
 __host__ __device__ constexpr int grad_cb(int PM, int kind) {
-  return (ACE_MM_GRAD_CB == 2 && (kind == 0 || PM <= 32)) ? 2 : 4;
+  return (kind == 0 || PM <= 32) ? 2 : 4;
 }
+
+// Dynamic LDS of the four tile kernels, in bytes.  The two-sided tile
+// (k_cross_mm, k_cross_slices_mm) is the assembly's layout plus the row
+// side's 64 points; k_group_mm adds the tile's 64 labels.
+constexpr size_t asm_mm_lds(int PM, int B, int kind) {
+  return (size_t)mm_layout(PM, B, kind == 0 ? 0 : 1, false).total * sizeof(double);
+}
+constexpr size_t grad_mm_lds(int PM, int B, int kind) {
+  return (size_t)mm_layout(PM, B, kind == 0 ? 0 : 1, true, 4 * (4 / grad_cb(PM, kind))).total *
+         sizeof(double);
+}
+constexpr size_t cross_mm_lds(int PM, int B, int kind) {
+  return asm_mm_lds(PM, B, kind) + 64 * xj_pitch(PM) * sizeof(double);
+}
+constexpr size_t group_mm_lds(int PM, int B, int kind) {
+  return cross_mm_lds(PM, B, kind) + 64 * sizeof(int);
+}
+
+// Every supported shape (check_shape: p <= PMAX, B <= BMAX) fits the 160 KB
+// of LDS a gfx950 workgroup can use (up to 80 KB two workgroups share a CU;
+// above it one, at large B and p), so no launcher tests its request.  Every
+// B is tried, not only BMAX: the gradient's partial buffers go from B to two
+// once they pass 40 KB, so its total is not monotone in B.  The maxima, all
+// SE at PM = 64 and B = 32: assembly 115712 B, gradient 127936 B, cross
+// 148992 B, grouped sums 149248 B.
+constexpr size_t LDS_MAX = 160 * 1024;
+constexpr bool mm_lds_fits() {
+  for (int PM : PM_BUCKETS)
+    for (int B = 1; B <= BMAX; ++B)
+      for (int kind = 0; kind < 2; ++kind)
+        if (asm_mm_lds(PM, B, kind) > LDS_MAX || grad_mm_lds(PM, B, kind) > LDS_MAX ||
+            cross_mm_lds(PM, B, kind) > LDS_MAX || group_mm_lds(PM, B, kind) > LDS_MAX)
+          return false;
+  return true;
+}
+static_assert(mm_lds_fits(), "a supported shape's tile staging exceeds the 160 KB of LDS");
 
 // f(std::integral_constant<int, PM>) for the instantiated covariate buckets,
 // f(std::integral_constant<int, KIND>) for the kernel family (0 SE, else
@@ -1469,26 +1449,12 @@ static hipError_t grad_mm_launch(PairSide S, int B, int ZS, TabView tab, const d
                                  int64_t ld, double sA, const double *alpha, double *gpart,
                                  hipStream_t st, const Tile *tiles, int64_t nslot, int64_t ndiag,
                                  int G) {
-  constexpr int CB = grad_cb(PM, KIND);
-  constexpr int NT = 64 * 4 * (4 / CB);
-  const MmLayout o = mm_layout(PM, B, KIND, true, NT / 64);
-  const size_t lds = (size_t)o.total * sizeof(double);
-  return o.red_slices == B
+  const size_t lds = grad_mm_lds(PM, B, KIND);
+  return mm_layout(PM, B, KIND, true, 4 * (4 / grad_cb(PM, KIND))).red_slices == B
              ? grad_mm_launch_dg<PM, KIND, true>(S, B, ZS, tab, A, ld, sA, alpha, gpart, st, tiles,
                                                  nslot, ndiag, G, lds)
              : grad_mm_launch_dg<PM, KIND, false>(S, B, ZS, tab, A, ld, sA, alpha, gpart, st,
                                                   tiles, nslot, ndiag, G, lds);
-}
-
-// Whether the per-tile staging of the MFMA kernels fits the 160 KB of LDS
-// a gfx950 workgroup can use (up to 80 KB two workgroups share a CU; above
-// it one, at large B and p).  Every supported shape (B <= 32, p <= 64)
-// fits: the largest, SE at PM = 64 and B = 32, stages 127 KB.
-bool mm_lds_ok(int PM, int B, int kind, bool grad) {
-  const int nwave = grad ? 4 * (4 / grad_cb(PM, kind)) : 4;
-  return (int64_t)mm_layout(PM, B, kind == 0 ? 0 : 1, grad, nwave).total *
-             (int64_t)sizeof(double) <=
-         160 * 1024;
 }
 
 hipError_t launch_grad_mm(int kind, int PM, PairSide S, int B, int ZS, TabView tab,
@@ -1518,7 +1484,7 @@ static hipError_t asm_mm_launch(PairSide S, int64_t npad, int B, int ZS, TabView
                        : part == 3 ? nt - JB
                                    : nt * (nt + 1) / 2;
   if (nblk == 0) return hipSuccess;
-  const size_t lds = (size_t)mm_layout(PM, B, KIND, false).total * sizeof(double);
+  const size_t lds = asm_mm_lds(PM, B, KIND);
   return launch_lds(k_asm_mm<PM, KIND>, dim3((unsigned)nblk), dim3(ASM_NT), lds, st, S, B, ZS, tab,
                     sig, out, ld, kcopy, tiles, G, part, nt, JB);
 }
@@ -1530,7 +1496,7 @@ static hipError_t asm_mm_persist_launch(PairSide S, int64_t npad, int B, int ZS,
   const int64_t nt = npad / AT, JB = asm_first_cols((int)nt);
   const int64_t nblk = (nt - JB) * (nt - JB - 1) / 2;  // strictly lower tiles of part 2
   if (nt - JB <= 0) return hipSuccess;
-  const size_t lds = (size_t)mm_layout(PM, B, KIND, false).total * sizeof(double);
+  const size_t lds = asm_mm_lds(PM, B, KIND);
   // part 2's diagonal tiles (the r == c / r < c path) as a plain grid first;
   // a filler launch (fill: `slots` more workgroups on another stream, none
   // reserved) only joins the queue of the running one
@@ -1559,7 +1525,7 @@ static int asm_mm_slots(int kind, int B) {
   }
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return 0;
-  const size_t lds = (size_t)mm_layout(PM, B, kind == 0 ? 0 : 1, false).total * sizeof(double);
+  const size_t lds = asm_mm_lds(PM, B, kind);
   const void *f = kind == 0 ? (const void *)k_asm_mm_q<PM, 0> : (const void *)k_asm_mm_q<PM, 1>;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, f, ASM_NT, lds) != hipSuccess) return 0;
   // never more than the register file holds (the occupancy API can report
@@ -1611,20 +1577,12 @@ hipError_t launch_assembly_persist(int kind, int PM, PairSide S, int64_t npad, i
   });
 }
 
-// k_cross_mm's LDS: the assembly's layout plus the row side's points
-static size_t cross_mm_lds(int PM, int B, int kind) {
-  return (size_t)(mm_layout(PM, B, kind == 0 ? 0 : 1, false).total + 64 * xj_pitch(PM)) *
-         sizeof(double);
-}
-bool cross_mm_lds_ok(int PM, int B, int kind) { return cross_mm_lds(PM, B, kind) <= 160 * 1024; }
-
 hipError_t launch_cross_mm(int kind, int PM, PairSide R, PairSide C, int B, int ZS, TabView tab,
                            int b0, int b1, double *out, int64_t ld, hipStream_t st) {
   return with_pm(PM, [&](auto pm) {
     constexpr int P = decltype(pm)::value;
     if (R.n <= 0 || C.n <= 0 || b1 <= b0) return hipSuccess;
     const size_t lds = cross_mm_lds(P, B, kind);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((C.n + AT - 1) / AT), (unsigned)((R.n + AT - 1) / AT));
     return with_kind(kind, [&](auto kd) {
       return launch_lds(k_cross_mm<P, decltype(kd)::value>, grid, dim3(256), lds, st, R, C, B, ZS,
@@ -1701,7 +1659,6 @@ hipError_t launch_cross_slices_mm(int kind, int PM, PairSide R, PairSide C, int 
     constexpr int P = decltype(pm)::value;
     if (R.n <= 0 || C.n <= 0) return hipSuccess;
     const size_t lds = cross_mm_lds(P, B, kind);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((C.n + AT - 1) / AT), (unsigned)((R.n + AT - 1) / AT));
     return with_kind(kind, [&](auto kd) {
       return launch_lds(k_cross_slices_mm<P, decltype(kd)::value>, grid, dim3(256), lds, st, R, C,
@@ -1810,56 +1767,6 @@ __global__ __launch_bounds__(256, 2) void k_group_mm(PairSide S, int B, int ZS, 
 }
 
 
-// The same reduction on the VALU alone (the staging of k_group_mm does not
-// fit in LDS, or ACE_PAIRS=valu): one thread per row of the strip, r2 as the
-// plain weighted sum of squared differences, the row's G sums in LDS.
-template <int KIND>
-__global__ __launch_bounds__(64) void k_group_valu(PairSide S, int PM, int B, int ZS, TabView tab,
-                                                  int b0, int b1, const int *__restrict__ label,
-                                                  int G, int tpw, double *__restrict__ part,
-                                                  int64_t ldp) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double *const E = lds, *const sR = lds + 64;
-  const int tid = threadIdx.x;
-  const int64_t js = blockIdx.x, r = (int64_t)blockIdx.y * AT + tid;
-  const int64_t c0 = js * tpw * AT;
-  const int64_t c1 = (c0 + (int64_t)tpw * AT < S.n) ? c0 + (int64_t)tpw * AT : S.n;
-  if (ACE_ASM_EXP == 2) E[tid] = kExp2Tab64[tid];
-  else if (tid < 32) E[tid] = kExp2Tab[tid];
-  for (int h = 0; h < G; ++h) sR[tid * G + h] = 0.0;
-  __syncthreads();
-  if (r >= S.n) return;
-  const double *xr = S.X + r * PM;
-  for (int64_t c = c0; c < c1; ++c) {
-    const int lab = label[c];
-    if (lab < 0) continue;
-    const double *xc = S.X + c * PM;
-    double k = 0.0;
-    for (int b = b0; b < b1; ++b) {
-      const double *wv = tab.wk + b * PM;
-      double r2 = 0.0;
-      for (int i = 0; i < PM; ++i) {
-        const double d = xr[i] - xc[i];
-        r2 = fma(d * d, wv[i], r2);
-      }
-      if (KIND == 1) r2 = fmax(r2, 1e-300);
-      double zr = 1.0, zc = 1.0, lzr = 0.0, lzc = 0.0;
-      if (b > 0) {
-        zr = S.Z[r * ZS + b - 1];
-        zc = S.Z[c * ZS + b - 1];
-        if (KIND == 0) {
-          lzr = S.LZ[r * ZS + b - 1];
-          lzc = S.LZ[c * ZS + b - 1];
-        }
-      }
-      k += kval_nb<KIND>(r2, tab.lam[b], zr, zc, lzr, lzc, E);
-    }
-    sR[tid * G + lab] += k;
-  }
-  double *const P = part + js * ldp * G;
-  for (int h = 0; h < G; ++h) P[r + (int64_t)h * ldp] = sR[tid * G + h];
-}
-
 // out[e] = sum over s < nparts of part[s count + e], s ascending
 __global__ __launch_bounds__(256) void k_sum_parts(const double *__restrict__ part, int nparts,
                                                    int64_t count, double *__restrict__ out) {
@@ -1868,11 +1775,6 @@ __global__ __launch_bounds__(256) void k_sum_parts(const double *__restrict__ pa
   double s = part[e];
   for (int p = 1; p < nparts; ++p) s += part[(int64_t)p * count + e];
   out[e] = s;
-}
-
-// k_group_mm's LDS: k_cross_mm's plus the tile's 64 labels
-static size_t group_mm_lds(int PM, int B, int kind) {
-  return cross_mm_lds(PM, B, kind) + 64 * sizeof(int);
 }
 
 // column tiles per workgroup: about 1024 workgroups over the strips
@@ -1897,16 +1799,12 @@ hipError_t launch_group_sums(int kind, int PM, PairSide S, int B, int ZS, TabVie
   const int tpw = group_tpw(S.n);
   const int nparts = group_sums_parts(S.n);
   const dim3 grid((unsigned)nparts, (unsigned)nt);
-  const hipError_t e = with_kind(kind, [&](auto kd) {
-    constexpr int KIND = decltype(kd)::value;
-    if (pairs_use_mm(PM, false) && group_mm_lds(PM, B, kind) <= 160 * 1024)
-      return with_pm(PM, [&](auto pm) {
-        return launch_lds(k_group_mm<decltype(pm)::value, KIND>, grid, dim3(256),
-                          group_mm_lds(PM, B, kind), st, S, B, ZS, tab, b0, b1, label, G, tpw,
-                          part, S.n);
-      });
-    return launch_lds(k_group_valu<KIND>, grid, dim3(64), (size_t)(64 + 64 * G) * sizeof(double),
-                      st, S, PM, B, ZS, tab, b0, b1, label, G, tpw, part, S.n);
+  const hipError_t e = with_pm(PM, [&](auto pm) {
+    return with_kind(kind, [&](auto kd) {
+      return launch_lds(k_group_mm<decltype(pm)::value, decltype(kd)::value>, grid, dim3(256),
+                        group_mm_lds(PM, B, kind), st, S, B, ZS, tab, b0, b1, label, G, tpw, part,
+                        S.n);
+    });
   });
   if (e != hipSuccess) return e;
   const int64_t count = S.n * G;

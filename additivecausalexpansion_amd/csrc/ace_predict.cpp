@@ -311,8 +311,8 @@ void predict_impl(ace_model *m, const double *theta, int64_t nx, const double *X
     tc.Z += c0 * s.ZS;
     tc.LZ += c0 * s.ZS;
     // kernmat_*_cpp(X2, X, Z2, Z): test side first
-    ck(ctx, launch_assembly(2, s.kind, s.PM, tc, train, 0, B, s.ZS, tv, 0.0, scratch.d(), nc,
-                            nullptr, st, nullptr, 0, 1, 0, b0, b1),
+    ck(ctx, launch_assembly(2, s.kind, s.PM, tc, train, B, s.ZS, tv, scratch.d(), nc, nullptr, st,
+                            b0, b1),
        "cross assembly");
     *ld = nc;
     return scratch.d();
@@ -322,8 +322,8 @@ void predict_impl(ace_model *m, const double *theta, int64_t nx, const double *X
   };
   op.kxx = [&](int64_t *ld, DBuf &scratch) -> const double * {
     alloc(ctx, scratch, (size_t)(nx * nx) * sizeof(double), "alloc K_xx");
-    ck(ctx, launch_assembly(1, s.kind, s.PM, test.view(nx), test.view(nx), 0, B, s.ZS, tv, 0.0,
-                            scratch.d(), nx, nullptr, st, nullptr, 0, 1, 0, b0, b1),
+    ck(ctx, launch_assembly(1, s.kind, s.PM, test.view(nx), test.view(nx), B, s.ZS, tv,
+                            scratch.d(), nx, nullptr, st, b0, b1),
        "symmetric assembly");
     *ld = nx;
     return scratch.d();
@@ -407,21 +407,12 @@ int64_t coef_chunk(int B) {
 }
 
 // Kc ((tc.n B) x n, ld tc.n B): slice b of the chunk's test point c in row
-// c + tc.n b.  tc carries a basis of ones: k_cross_slices_mm ignores it, the
-// all-VALU form (ACE_PAIRS=valu, or staging beyond LDS) is mode 2 one slice
-// at a time, which multiplies by it.
+// c + tc.n b.  k_cross_slices_mm does not read tc's basis.
 void slice_assembly(ace_ctx *ctx, const Shape &s, PairSide tc, PairSide train, TabView tv,
                     double *Kc) {
-  const int64_t ldk = tc.n * s.B;
-  if (pairs_use_mm(s.PM, false) && cross_mm_lds_ok(s.PM, s.B, s.kind)) {
-    ck(ctx, launch_cross_slices_mm(s.kind, s.PM, tc, train, s.B, s.ZS, tv, Kc, ldk, ctx->stream),
-       "slice assembly");
-    return;
-  }
-  for (int b = 0; b < s.B; ++b)
-    ck(ctx, launch_assembly(2, s.kind, s.PM, tc, train, 0, s.B, s.ZS, tv, 0.0, Kc + tc.n * b, ldk,
-                            nullptr, ctx->stream, nullptr, 0, 1, 0, b, b + 1),
-       "slice assembly");
+  ck(ctx, launch_cross_slices_mm(s.kind, s.PM, tc, train, s.B, s.ZS, tv, Kc, tc.n * s.B,
+                                 ctx->stream),
+     "slice assembly");
 }
 
 // ace_model_coef_cross: the cube Kc (nx x n x B), chunked like the pass
@@ -480,8 +471,7 @@ void coef_once(ace_model *m, const double *theta, int64_t nx, const double *X2, 
   DBuf dtab, dw, dsv, ddiag, dscal, dtmp, dpart, dres;
   upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
   const TabView tv = tab_view(dtab, s);
-  // a test side of ones: the slice kernel ignores it, the all-VALU fallback
-  // (mode 2 one slice at a time) multiplies by it
+  // (the slice kernel does not read the test side's basis; upload_side wants one)
   SideBufs test;
   std::vector<double> ones((size_t)(nx * s.ZS), 1.0);
   upload_side(ctx, test, s, X2, ones.data(), nx, nx);

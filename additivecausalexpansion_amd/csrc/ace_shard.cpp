@@ -1126,8 +1126,8 @@ void shard_eval(ShardModel *m, const double *theta, int use_mu, int which, bool 
       const PairSide ps = R.side.view(n);
       const int64_t t0 = part ? R.nasm1 : 0, nt = part ? R.nasm - R.nasm1 : R.nasm1;
       if (nt > 0)
-        ck(ctx, launch_assembly(0, s.kind, s.PM, ps, ps, npad, s.B, s.ZS, tv, sig, R.A[which].d(),
-                                naug, nullptr, st, (const Tile *)R.tasm.p + t0, nt, m->G),
+        ck(ctx, launch_assembly_mm(s.kind, s.PM, ps, npad, s.B, s.ZS, tv, sig, R.A[which].d(), naug,
+                                   nullptr, st, (const Tile *)R.tasm.p + t0, nt, m->G),
            "assembly");
       if (part == 0) {
         ck(ctx, launch_aug_init(R.A[which].d(), naug, npad, n, R.y.d(), st, m->G, R.r), "aug init");

@@ -88,7 +88,7 @@ from referee_ld import LD
 U = 2.0 ** -53
 TINY = 2.0 ** -1070
 DENORM_ULP = 2.0 ** -1074
-# csrc/ace_pairs.hip kBuckets: the feature counts the pair kernels are compiled for
+# csrc/ace_internal.h PM_BUCKETS: the feature counts the pair kernels are compiled for
 BUCKETS = (4, 8, 12, 16, 20, 24, 32, 48, 64)
 
 REGIMES = ("base", "dups", "neardup", "neardup_ulp", "binary", "short", "long", "ramp30", "ramp450",

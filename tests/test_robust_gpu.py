@@ -20,7 +20,7 @@ posterior form is well above COV_TOL of its terms.
 """
 import numpy as np
 
-from conftest import record_error, run_child
+from conftest import record_error
 import pytest
 from robust_ref import indicator, levels_ref, step_post
 from test_gpu import close
@@ -207,8 +207,11 @@ def _check_gcov(got, c, label, G, what):
 
 @pytest.mark.parametrize("kernel", ["SE", "Matern32"])
 @pytest.mark.parametrize("n,p,B,nx,G", [(130, 1, 1, 9, 1), (400, 3, 2, 150, 3),
-                                        (700, 20, 10, 257, 64), (400, 3, 6, 150, 17)])
+                                        (700, 20, 10, 257, 64), (400, 3, 6, 150, 17),
+                                        (70, 50, 32, 65, 17)])
 def test_grouped_sums_match_oracle(A, O, kernel, n, p, B, nx, G):
+    """The last shape (PM = 64, B = 32) is k_group_mm's largest request of
+    dynamic LDS, 149248 B for SE."""
     c = case(A, O, kernel, n, p, B, nx)
     m = c["m"]
     label = _labels(nx, G)
@@ -359,52 +362,6 @@ def test_grouped_sums_are_bitwise_reproducible(A, O, kernel):
     r1 = m.robust_treatment(c["th"], c["X2"], c["dZ2"], c["zx"], STD_Y, STD_Z, N_STEPS)
     r2 = m.robust_treatment(c["th"], c["X2"], c["dZ2"], c["zx"], STD_Y, STD_Z, N_STEPS)
     assert np.array_equal(r1["avg"], r2["avg"], equal_nan=True)
-
-
-_VALU_SNIPPET = """
-import sys, numpy as np
-sys.path.insert(0, {root!r})
-sys.path.insert(0, {root!r} + "/tests")
-import additivecausalexpansion_amd as A
-from oracle import ace_oracle as O
-from test_predict_gpu import _fit_state, _test_points
-from additivecausalexpansion_amd.synthetic import make_problem
-out, grads = [], []
-for kernel in ("SE", "Matern32"):
-    m, y, X, Z, th, sy, inv = _fit_state(O, kernel, 400, 3, 2, seed=7, A=A, mix=False)
-    X2, Z2 = _test_points(3, 2, 150, seed=77)
-    lab = (np.arange(150) % 4 - 1).astype(np.int32)
-    g = m.predict_marginal_groups(th, X2, np.asfortranarray(Z2 * 0.7 + 0.1), 1.7, 0.8, 3, lab)
-    out.append(g["gcov"])
-    # the VALU gradient on the model's XCD-dealt tile list (padding entries)
-    grads.append(m.para_update(2, make_problem(400, 3, 2, seed=7)[3].copy())[0])
-np.save({out!r}, np.stack(out))
-np.save({out!r} + ".grad.npy", np.stack(grads))
-"""
-
-
-def test_grouped_sums_valu_form(tmp_path, A, O):
-    """ACE_PAIRS=valu: the all-VALU form of the same reduction (the form that
-    runs when the MFMA kernel's staging does not fit in LDS), one child for
-    both kernels, against the same oracle bound.  The child's model runs the
-    VALU assembly and gradient too, whose tile list carries padding entries."""
-    import os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = str(tmp_path / "valu.npy")
-    run_child(_VALU_SNIPPET.format(root=root, out=out), env=dict(os.environ, ACE_PAIRS="valu"),
-              timeout=100)
-    got = np.load(out)
-    for j, kernel in enumerate(("SE", "Matern32")):
-        c = case(A, O, kernel, 400, 3, 2, 150)
-        _check_gcov(got[j], c, _labels(150, 3), 3, f"groups valu {kernel}")
-    # the child's VALU gradient kernels against this process's MFMA ones
-    from additivecausalexpansion_amd.synthetic import make_problem
-    grads = np.load(out + ".grad.npy")
-    y, X, Z, th0, sy = make_problem(400, 3, 2, seed=7)
-    for j, kernel in enumerate(("SE", "Matern32")):
-        m = A.DeviceModel(kernel, 400, 3, 2)
-        m.set_data(y, X, Z, sy)
-        close(grads[j], m.para_update(2, th0.copy())[0], 1e-6, 1e-9)
 
 
 # --------------------------------------------------------------------------

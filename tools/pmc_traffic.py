@@ -27,7 +27,6 @@ KERNELS = {
     "k_update_x": "ace::k_update_x(",
     "k_gather": "ace::k_gather(",
     "k_panel_gemm": "ace::k_panel_gemm(",
-    "k_grad2": "ace::k_grad2<",
     "k_asm_mm": "ace::k_asm_mm<",
     "k_asm_mm_q": "ace::k_asm_mm_q<",
     "k_grad_mm": "ace::k_grad_mm<",

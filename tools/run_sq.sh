@@ -1,5 +1,5 @@
 # SQ counter passes over a short C2 bench (one rocprofv3 run per pass);
-# $1 = output subdir, further args go to bench.py.  Env (e.g. ACE_PAIRS) is
+# $1 = output subdir, further args go to bench.py.  Env (e.g. ACE_ZSKIP) is
 # inherited.
 set -o pipefail
 out=$GRAFT_REPO_ROOT/gpurun_out/$1
