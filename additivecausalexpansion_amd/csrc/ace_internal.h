@@ -291,9 +291,14 @@ double update_gemm_tiles(int64_t naug, int64_t k0, int kx, bool look);
 double sweep_flops(int64_t naug, int64_t npad);
 
 // ---- sharded sweep (one rank's view; ace_shard.cpp drives the steps) --------
-// Step k on rank r:  shard_pack -> [exchange: broadcast `low` from rank k%G,
-// all-gather recv slot r -> recv] -> shard_unpack_chain (panel k on every rank,
-// pivot chain run redundantly, W for the rows r consumes) -> updates.
+// Step k on rank r:  pack -> [exchange: broadcast `low` from rank k%G,
+// all-gather recv slot r -> recv] -> unpack + pivot chain (panel k on every
+// rank, the chain run redundantly, W for the rows r consumes) -> updates.
+// The one-step schedule (ACE_PAIR=0, or one step): shard_pack, one exchange,
+// shard_unpack_chain, shard_update_cross / shard_update_main per step.  The
+// head schedule (default): shard_update_group launches of Z steps that also
+// pack the next panel, the exchange and the unpack split into the group's
+// head rows and the rest (shard_*_part), shard_chain and shard_pgemm.
 struct ShardSweep {
   double *A;          // local column blocks, naug x (nloc * NB), ld = naug
   int64_t ld;         // naug
@@ -312,9 +317,7 @@ struct ShardSweep {
 };
 int shard_row_slots(int k, int G);
 hipError_t shard_pack(const ShardSweep &b, int k, hipStream_t st);
-// own_done: the packing cross launch already wrote the rank's own panel rows
-hipError_t shard_unpack_chain(const ShardSweep &b, int k, int buf, hipStream_t st,
-                              bool own_done = false);
+hipError_t shard_unpack_chain(const ShardSweep &b, int k, int buf, hipStream_t st);
 // cross tiles of block k+1 with panel k (buffer buf)
 hipError_t shard_update_cross(const ShardSweep &b, int k, int buf, hipStream_t st);
 // every own tile except the cross of block kx (kx < 0: none)

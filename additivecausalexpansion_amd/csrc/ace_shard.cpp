@@ -8,13 +8,19 @@
 // One evaluation on rank r:
 //   assembly      own lower 64-tiles (+ identity padding, sigma diagonal)
 //   sweep step k  pack -> exchange -> unpack + pivot chain -> update
-//                 exchange = RCCL group { broadcast of panel rows >= k0 from
-//                 rank k % G, all-gather of the row pieces A[k, j<k] }; the
+//                 exchange = RCCL group { broadcast of panel rows from rank
+//                 k % G, all-gather of the row pieces A[k, j<k] }; the
 //                 NB x NB pivot sweep runs redundantly on every rank (it is
 //                 one workgroup of latency) so no second collective carries
-//                 D^-1 or the pivots.  Lookahead as on one GPU: the cross of
-//                 block k+1 is updated first, then pack/exchange/chain of
-//                 panel k+1 run on the side stream under the bulk update.
+//                 D^-1 or the pivots.  Two schedules (run_sweep_sharded):
+//                 the head / tail schedule, Z steps per bulk launch, the
+//                 lookahead's cross launches packing the next panel, its
+//                 exchange split into a head broadcast (the group's rows, in
+//                 front of the pivot chain) and a tail broadcast + all-gather
+//                 (second communicator, beside the chain); and the one-step
+//                 schedule (ACE_PAIR=0, or a sweep of one step), one exchange
+//                 of all rows >= k0 and one update launch per step, the
+//                 former's bitwise referee.
 //   alpha         AUG rows of own columns -> all-reduce (u, v, corner)
 //   gradient      own 64-tiles of T = -A^-1 - alpha alpha^T
 //   reduce        one all-reduce of the gradient sums (the RMSE residual is
@@ -58,8 +64,7 @@ struct Rccl {
   ncclResult_t (*GroupStart)() = nullptr;
   ncclResult_t (*GroupEnd)() = nullptr;
   const char *(*GetErrorString)(ncclResult_t) = nullptr;
-  // optional: the head schedule's second communicator (null: that schedule
-  // is not used over RCCL)
+  // the head schedule's second communicator (NCCL >= 2.18)
   ncclResult_t (*CommSplit)(ncclComm_t, int, int, ncclComm_t *, ncclConfig_t *) = nullptr;
 
   Rccl() {
@@ -85,8 +90,8 @@ struct Rccl {
     ACE_SYM(GroupStart, "ncclGroupStart");
     ACE_SYM(GroupEnd, "ncclGroupEnd");
     ACE_SYM(GetErrorString, "ncclGetErrorString");
+    ACE_SYM(CommSplit, "ncclCommSplit");
 #undef ACE_SYM
-    CommSplit = reinterpret_cast<decltype(CommSplit)>(dlsym(h, "ncclCommSplit"));
     ok = true;
   }
 };
@@ -158,12 +163,6 @@ struct RankState {
   DBuf tupd, tasm, tgrad;  // device tile lists
   int64_t nupd = 0, nasm = 0, nasm1 = 0, ngrad = 0, ndiag = 0;  // nasm1: first-part tiles
   std::vector<Tile> hupd;  // host copy (flop accounting)
-  // pair schedule: own lookahead cross tiles (XCD-dealt), one device list
-  // with host offsets -- xoff[k] .. xoff[k + 1]: tiles with I or J in block
-  // k + 1 (the single-step cross with panel k); poff[2 g], poff[2 g + 1]:
-  // group g's pair cross, block 2 g first, then block 2 g + 1 minus block 2 g
-  DBuf tx, tp;
-  std::vector<int64_t> xoff, poff;
   // head schedule: the own tiles of group_head_tiles' lists (device, host
   // offsets hoff[G 2Z + m]) and the head part's exchange buffer (Z NB x NB)
   DBuf th, lowh;
@@ -179,7 +178,7 @@ struct ShardModel {
   Shape s{};
   int64_t n = 0, npad = 0, naug = 0, ntr = 0;
   int G = 1, rank = 0;
-  int Z = 2;          // sweep steps per bulk launch of the group schedule (sweep_group())
+  int Z = 2;          // sweep steps per bulk launch of the head schedule (sweep_group_n())
   bool sim = true;    // every rank simulated in this process (device copies)
   // timing-only proxy (-DACE_DIAG_SHARD_PROXY builds, unique_id NULL): rank
   // `rank` of `world` alone, scheduled as an RCCL rank (lookahead on the
@@ -191,9 +190,10 @@ struct ShardModel {
   ace_comm_ops ops{};
   HostStage stage;  // pinned staging of the host-callback collectives
   ncclComm_t comm = nullptr;
-  // head schedule (run_sweep_sharded_heads): its tail exchanges run on a
-  // second communicator, so they are never ordered behind the head path's
-  // (one communicator's collectives execute in issue order on any stream)
+  // head schedule (run_sweep_sharded_heads; pair_steps() and >= 2 steps,
+  // else the one-step schedule): its tail exchanges run on a second
+  // communicator, so they are never ordered behind the head path's (one
+  // communicator's collectives execute in issue order on any stream)
   bool heads = false;
   ncclComm_t comm2 = nullptr;
   std::vector<std::unique_ptr<RankState>> ranks;  // 1 (RCCL) or G (simulated)
@@ -301,53 +301,6 @@ double update_flops_group(const std::vector<Tile> &tl, int64_t naug, int64_t ka0
   return cnt * 2.0 * UT * UT * NB;
 }
 
-// The rank's own lookahead cross lists of the group schedule (RankState):
-// per step k the tiles with I or J in block k + 1 (xoff), per group g >= 1
-// (blocks kb = Z g .. kb + z - 1) the cross of block kb (poff[2 g]) and the
-// rest of the group's cross (poff[2 g + 1]).
-void build_cross_lists(ace_ctx *ctx, RankState &R, int64_t naug, int steps, int G, int Z) {
-  constexpr int KT = NB / UT;
-  const std::vector<Tile> own = own_tiles(naug / UT, UT, G, R.r);
-  auto in_blk = [&](int t, int blk) { return t >= blk * KT && t < (blk + 1) * KT; };
-  const int S = update_order_block();
-  auto deal = [&](const std::vector<Tile> &t) { return S > 0 ? xcd_update_order(t, S) : t; };
-  std::vector<Tile> x, pr;
-  R.xoff.assign(1, 0);
-  for (int k = 0; k + 1 < steps; ++k) {
-    std::vector<Tile> t;
-    for (const Tile &q : own)
-      if (in_blk(q.I, k + 1) || in_blk(q.J, k + 1)) t.push_back(q);
-    const std::vector<Tile> o = deal(t);
-    x.insert(x.end(), o.begin(), o.end());
-    R.xoff.push_back((int64_t)x.size());
-  }
-  const int ng = (steps + Z - 1) / Z;
-  R.poff.assign(2 * ng + 1, 0);
-  for (int g = 1; g < ng; ++g) {
-    const int b0 = Z * g, b1 = std::min(steps, Z * (g + 1));  // blocks [b0, b1)
-    std::vector<Tile> ta, tb;
-    for (const Tile &q : own) {
-      if (in_blk(q.I, b0) || in_blk(q.J, b0)) {
-        ta.push_back(q);
-        continue;
-      }
-      for (int bb = b0 + 1; bb < b1; ++bb)
-        if (in_blk(q.I, bb) || in_blk(q.J, bb)) {
-          tb.push_back(q);
-          break;
-        }
-    }
-    R.poff[2 * g] = (int64_t)pr.size();
-    const std::vector<Tile> oa = deal(ta), ob = deal(tb);
-    pr.insert(pr.end(), oa.begin(), oa.end());
-    R.poff[2 * g + 1] = (int64_t)pr.size();
-    pr.insert(pr.end(), ob.begin(), ob.end());
-    R.poff[2 * g + 2] = (int64_t)pr.size();
-  }
-  upload_tiles(ctx, R.tx, x);
-  upload_tiles(ctx, R.tp, pr);
-}
-
 // The head schedule's tile lists on rank R: group_head_tiles' lists (the
 // single-GPU head / tail split, ace_sweep.hip) restricted to the rank's own
 // tiles (column block owned), offsets hoff[G 2Z + m].
@@ -367,93 +320,27 @@ void build_head_lists(ace_ctx *ctx, RankState &R, int64_t naug, int steps, int G
   upload_tiles(ctx, R.th, mine);
 }
 
-// ACE_SHARD_HEADS=0: the sharded sweep keeps the group schedule without the
-// head / tail split (run_sweep_sharded); default on
-bool shard_heads_on() {
-  static const bool v = env_int("ACE_SHARD_HEADS", 1) != 0;
-  return v;
-}
-
 // ---- collectives over the local ranks -------------------------------------
-// Panel exchange of step k on stream st.
-void exchange(ShardModel &m, int k, hipStream_t st) {
-  ace_ctx *ctx = m.ctx;
-  if (m.G == 1 && !m.live()) return;  // one simulated rank: the identity
-  const int64_t k0 = (int64_t)k * NB;
-  const size_t nlow = (size_t)((m.naug - k0) * NB);
-  const int slots = shard_row_slots(k, m.G);
-  const size_t nrow = (size_t)slots * NB * NB;
-  const int root = k % m.G;
-  // the all-gather operand of rank r is slot r of recv (in place)
-  auto own = [&](RankState &R) { return R.recv.d() + (size_t)R.r * nrow; };
-  if (m.host) {
-    RankState &R = *m.ranks[0];
-    host_bcast(ctx, m.ops, m.stage, R.low.d(), nlow, root, st);
-    ++m.calls[ACE_COMM_BROADCAST];
-    if (nrow > 0) {
-      host_allgather(ctx, m.ops, m.stage, own(R), R.recv.d(), nrow, m.G, st);
-      ++m.calls[ACE_COMM_ALLGATHER];
-    }
-    return;
-  }
-  if (m.proxy) {  // the bytes this rank receives, as device copies
-    RankState &R = *m.ranks[0];
-    if (R.r != root) {
-      alloc(ctx, m.proxy_buf, nlow * sizeof(double), "alloc proxy");
-      ck(ctx, hipMemcpyAsync(m.proxy_buf.p, R.low.p, nlow * sizeof(double), hipMemcpyDeviceToDevice, st),
-         "proxy broadcast");
-    }
-    if (nrow > 0)
-      for (int q = 0; q < m.G; ++q)
-        if (q != R.r)
-          ck(ctx, hipMemcpyAsync(R.recv.d() + (size_t)q * nrow, own(R), nrow * sizeof(double),
-                                 hipMemcpyDeviceToDevice, st),
-             "proxy all-gather");
-    return;
-  }
-  if (!m.sim) {
-    RankState &R = *m.ranks[0];
-    nck(ctx, rccl().GroupStart(), "ncclGroupStart");
-    nck(ctx, rccl().Broadcast(R.low.p, R.low.p, nlow, ncclDouble, root, m.comm, st),
-        "ncclBroadcast");
-    ++m.calls[ACE_COMM_BROADCAST];
-    if (nrow > 0) {
-      nck(ctx, rccl().AllGather(own(R), R.recv.p, nrow, ncclDouble, m.comm, st), "ncclAllGather");
-      ++m.calls[ACE_COMM_ALLGATHER];
-    }
-    nck(ctx, rccl().GroupEnd(), "ncclGroupEnd");
-    ++m.calls[ACE_COMM_GROUPS];
-    return;
-  }
-  RankState &src = *m.ranks[(size_t)root];
-  for (auto &Rp : m.ranks) {
-    RankState &R = *Rp;
-    if (R.r != root)
-      ck(ctx, hipMemcpyAsync(R.low.p, src.low.p, nlow * sizeof(double), hipMemcpyDeviceToDevice, st),
-         "sim broadcast");
-    if (nrow > 0)
-      for (auto &Sp : m.ranks)
-        if (Sp->r != R.r)
-          ck(ctx, hipMemcpyAsync(R.recv.d() + (size_t)Sp->r * nrow, own(*Sp), nrow * sizeof(double),
-                                 hipMemcpyDeviceToDevice, st),
-             "sim all-gather");
-  }
-}
-
-// The head schedule's two exchanges of panel k: head = the owner's column
-// rows [k0, hend) (rows x NB doubles in lowh, broadcast, on the head path's
-// stream); tail = the rows [hend, naug) (in low, broadcast) and the row
-// pieces (all-gather), on the tail path's stream and the second communicator
-// (host-callback groups: both through the callbacks, each blocking the host
-// between its stream's drain before and after, so the host issues the head
-// and tail exchanges one at a time, in the same order on every rank).
-void exchange_part(ShardModel &m, int k, bool head, int64_t rows, hipStream_t st) {
+// An exchange of panel k on stream st: a broadcast of rows x NB doubles of
+// the buffer `low` from the block's owner, rank k % G, and, with `gather`, the
+// all-gather of the row pieces A[k, j < k], one RCCL group on communicator c.
+// The one-step schedule's exchange: the column rows [k0, naug) in low, the
+// row pieces gathered, the first communicator.  The head schedule's two:
+// head = the rows [k0, hend) in lowh, on the head path's stream and the first
+// communicator; tail = the rows [hend, naug) in low and the row pieces, on
+// the tail path's stream and the second communicator (host-callback groups:
+// both through the callbacks, each blocking the host between its stream's
+// drain before and after, so the host issues the head and tail exchanges one
+// at a time, in the same order on every rank).
+void exchange(ShardModel &m, int k, DBuf RankState::*low, int64_t rows, bool gather, ncclComm_t c,
+              hipStream_t st) {
   ace_ctx *ctx = m.ctx;
   if (m.G == 1 && !m.live()) return;  // one simulated rank: the identity
   const size_t nlow = (size_t)(rows * NB);
-  const size_t nrow = head ? 0 : (size_t)shard_row_slots(k, m.G) * NB * NB;
+  const size_t nrow = gather ? (size_t)shard_row_slots(k, m.G) * NB * NB : 0;
   const int root = k % m.G;
-  auto lowp = [&](RankState &R) { return head ? R.lowh.d() : R.low.d(); };
+  auto lowp = [&](RankState &R) { return (R.*low).d(); };
+  // the all-gather operand of rank r is slot r of recv (in place)
   auto own = [&](RankState &R) { return R.recv.d() + (size_t)R.r * nrow; };
   if (m.host) {
     RankState &R = *m.ranks[0];
@@ -484,7 +371,6 @@ void exchange_part(ShardModel &m, int k, bool head, int64_t rows, hipStream_t st
   }
   if (!m.sim) {
     RankState &R = *m.ranks[0];
-    ncclComm_t c = head ? m.comm : m.comm2;
     nck(ctx, rccl().GroupStart(), "ncclGroupStart");
     if (nlow > 0) {
       nck(ctx, rccl().Broadcast(lowp(R), lowp(R), nlow, ncclDouble, root, c, st), "ncclBroadcast");
@@ -577,13 +463,9 @@ void rccl_warmup(ShardModel &m) {
 }
 
 // ---- the sharded sweep -------------------------------------------------------
-bool fuse_pack() {
-  static const bool v = env_int("ACE_FUSE_PACK", 1) != 0;
-  return v;
-}
-
-// One step per update launch, lookahead only over RCCL (ACE_PAIR=0: the
-// round-2 schedule, kept for A/B and for npad < 2 NB).
+// One step per update launch, lookahead only over RCCL (ACE_PAIR=0, or a
+// sweep of one step: the bitwise referee of the head schedule and the only
+// form for npad < 2 NB).
 void run_sweep_sharded_steps(ShardModel &m, int which, bool timed) {
   ace_ctx *ctx = m.ctx;
   hipStream_t st = ctx->stream;
@@ -602,7 +484,7 @@ void run_sweep_sharded_steps(ShardModel &m, int which, bool timed) {
   };
   auto prepare = [&](int k, int buf) {  // panel k into buffer buf, on `side`
     for (auto &b : v) ck(ctx, shard_pack(b, k, side), "shard pack");
-    exchange(m, k, side);
+    exchange(m, k, &RankState::low, m.naug - (int64_t)k * NB, true, m.comm, side);
     for (auto &b : v) ck(ctx, shard_unpack_chain(b, k, buf, side), "shard panel");
   };
   rec(2 * steps, st);  // inputs ready
@@ -637,27 +519,6 @@ void run_sweep_sharded_steps(ShardModel &m, int which, bool timed) {
   }
 }
 
-// Z sweep steps per bulk launch (Z = sweep_group_n()), the group schedule
-// without the head / tail split on each rank's own tiles.  Group g = steps Z g .. Z g + z - 1, panels in slots k % (2 Z):
-//   main:  wait(ready g) -> k_update_multi over the own tiles outside group
-//          g+1's cross (group g's z panels, K = z NB per tile) -> bulkdone(g)
-//   side:  wait(bulkdone g-1) -> group g's panels on block kb's cross (the
-//          launch that finalises block kb also packs step kb's exchange
-//          buffers) -> prepare(kb) [exchange, unpack + pivot chain + W] ->
-//          [wait side2] for j = 1 .. z-1: panels kb .. kb+j-1 on block
-//          kb+j's cross (packing kb+j) -> prepare(kb+j) -> ready(g+1)
-//   side2: group g's panels on the rest of group g+1's cross, concurrently
-//          with block kb's chain
-// Every mode runs the lookahead: RCCL exchanges on the side stream; the
-// simulated group's device copies on the side stream (all simulated ranks
-// share the three streams, so their bulk launches overlap the side path as
-// one rank's do); the host-callback group synchronises the side stream and
-// exchanges on the host while the already enqueued bulk launch runs.  The
-// bulk launch of group g is enqueued before the side path of group g+1 so
-// that a blocking (host) exchange overlaps it.  Every tile sees the
-// single-step schedule's MFMA chains in the same order (k_update_multi's
-// per-tile rule): bit-identical to run_sweep_sharded_steps
-// (tests/test_shard_gpu.py).
 // The single-GPU head / tail schedule (run_sweep_heads) on each
 // rank's own tiles, with the exchange split the same way.  Group G = blocks
 // [kb, kb + z), hend = (kb + z) NB:
@@ -674,9 +535,13 @@ void run_sweep_sharded_steps(ShardModel &m, int which, bool timed) {
 //   main: [ready g, ready2 g] -> the bulk launch of group g.
 // A panel's pivot chain then waits only for its head rows: the full column
 // cross, the row-piece all-gather and the panel GEMM of every other row run
-// beside it.  Every tile sees the same launches' MFMA chains as in
-// run_sweep_heads (the same lists, restricted to the rank's tiles):
-// bit-identical to the single-GPU model (tests/test_shard_gpu.py).
+// beside it.  Every mode runs the three streams: RCCL exchanges and the
+// simulated group's device copies are stream work (all simulated ranks share
+// the streams); the host-callback group drains the exchange's stream and
+// exchanges on the host while the already enqueued launches run.  Every tile
+// sees the same launches' MFMA chains as in run_sweep_heads (the same lists,
+// restricted to the rank's tiles): bit-identical to the single-GPU model and
+// to run_sweep_sharded_steps (tests/test_shard_gpu.py).
 void run_sweep_sharded_heads(ShardModel &m, int which, bool timed) {
   ace_ctx *ctx = m.ctx;
   const int steps = (int)(m.npad / NB);
@@ -734,7 +599,7 @@ void run_sweep_sharded_heads(ShardModel &m, int which, bool timed) {
       for (size_t q = 0; q < v.size(); ++q)
         ck(ctx, shard_pack_part(v[q], k, k0, he, m.ranks[q]->lowh.d(), 0, he - k0, false, side),
            "shard head pack");
-    exchange_part(m, k, true, he - k0, side);
+    exchange(m, k, &RankState::lowh, he - k0, false, m.comm, side);
     for (size_t q = 0; q < v.size(); ++q)
       ck(ctx, shard_unpack_part(v[q], k, k % NS, k0, he, m.ranks[q]->lowh.d(), 0, he - k0, packed, side),
          "shard head unpack");
@@ -745,7 +610,7 @@ void run_sweep_sharded_heads(ShardModel &m, int which, bool timed) {
       for (size_t q = 0; q < v.size(); ++q)
         ck(ctx, shard_pack_part(v[q], k, he, naug, m.ranks[q]->low.d(), he - k0, naug - he, true, side2),
            "shard tail pack");
-    exchange_part(m, k, false, naug - he, side2);
+    exchange(m, k, &RankState::low, naug - he, true, m.comm2, side2);
     for (size_t q = 0; q < v.size(); ++q) {
       ck(ctx, shard_unpack_part(v[q], k, k % NS, 0, k0, m.ranks[q]->low.d(), 0, 0, packed, side2),
          "shard tail unpack");
@@ -826,115 +691,10 @@ void run_sweep_sharded_heads(ShardModel &m, int which, bool timed) {
 }
 
 void run_sweep_sharded(ShardModel &m, int which, bool timed) {
-  ace_ctx *ctx = m.ctx;
-  const int steps = (int)(m.npad / NB);
-  const int Z = m.Z;
-  if (m.heads && steps >= 2) {
+  if (m.heads)
     run_sweep_sharded_heads(m, which, timed);
-    return;
-  }
-  if (!pair_steps() || steps < 2 || Z < 2 || !m.ranks[0]->P[2 * Z - 1].p) {
+  else
     run_sweep_sharded_steps(m, which, timed);
-    return;
-  }
-  const int NS = 2 * Z;  // panel slots
-  hipStream_t st = ctx->stream, side = ctx->side, side2 = ctx->side2;
-  const int ng = (steps + Z - 1) / Z;
-  auto zsize = [&](int g) { return std::min(Z, steps - Z * g); };
-  std::vector<ShardSweep> v;
-  for (auto &R : m.ranks) v.push_back(sweep_view(m, *R, which));
-  // events: [0] inputs, ready(g) 1.., bulkdone(g) 1+ng.., side2 start / done,
-  // [4 ng + 1] the assembly done
-  auto EV = [&](int i) { return m.ev[(size_t)i]; };
-  const int E_IN = 0;
-  auto E_READY = [&](int g) { return 1 + g; };
-  auto E_BULK = [&](int g) { return 1 + ng + g; };
-  auto E_S2A = [&](int g) { return 1 + 2 * ng + g; };
-  auto E_S2B = [&](int g) { return 1 + 3 * ng + g; };
-  const int E_ASM = 1 + 4 * ng;  // the whole assembly (part 2 included) done
-  auto rec = [&](int i, hipStream_t s_) { ck(ctx, hipEventRecord(EV(i), s_), "event"); };
-  auto wait = [&](hipStream_t s_, int i) { ck(ctx, hipStreamWaitEvent(s_, EV(i), 0), "event wait"); };
-  // the cross launch that finalises block k's tiles also writes the exchange
-  // buffers of step k (ACE_FUSE_PACK=0: separate k_pack_* launches)
-  const bool fuse = fuse_pack();
-  auto prepare = [&](int k, bool packed) {  // panel k into slot k % NS, on `side`
-    if (!packed)
-      for (auto &b : v) ck(ctx, shard_pack(b, k, side), "shard pack");
-    exchange(m, k, side);
-    for (auto &b : v) ck(ctx, shard_unpack_chain(b, k, k % NS, side, packed), "shard panel");
-  };
-  // blocks kb + 1 .. kb + z - 1 of a group from its own panels, each followed
-  // by its exchange and chain (on `side`)
-  auto inner = [&](int kb, int z) {
-    for (int j = 1; j < z; ++j) {
-      const int k = kb + j - 1;  // xoff list k: the own tiles with I or J in block k + 1
-      for (size_t q = 0; q < v.size(); ++q) {
-        RankState &R = *m.ranks[q];
-        const int64_t x0 = R.xoff[(size_t)k], nx = R.xoff[(size_t)k + 1] - x0;
-        ck(ctx, shard_update_group(v[q], kb, j, NS, -1, -1, (const Tile *)R.tx.p + x0, nx, side,
-                                   fuse ? kb + j : -1),
-           "shard cross update");
-      }
-      prepare(kb + j, fuse);
-    }
-  };
-  // E_IN: recorded by shard_eval after the first group's panels' columns,
-  // the AUG rows and the flag (the rest of the assembly runs on under it)
-  wait(side, E_IN);
-  prepare(0, false);
-  inner(0, zsize(0));
-  rec(E_READY(0), side);
-  m.upd_used = 0;
-  rec(E_ASM, st);  // group 1's cross tiles include assembly part-2 tiles
-  for (int g = 0; g < ng; ++g) {
-    const int kg = Z * g;
-    const bool more = g + 1 < ng;
-    const int kb = Z * (g + 1), zb = more ? zsize(g + 1) : 0;
-    wait(st, E_READY(g));
-    const bool tm = timed && m.upd_used + 2 <= (int)m.ev_upd.size();
-    const int kx0 = more ? kb : -1, kx1 = more ? kb + zb : -1;
-    for (size_t j = 0; j < v.size(); ++j) {
-      RankState &R = *m.ranks[j];
-      if (tm && j == 0) ck(ctx, hipEventRecord(m.ev_upd[(size_t)m.upd_used], st), "event");
-      ck(ctx, shard_update_group(v[j], kg, zsize(g), NS, kx0, kx1, (const Tile *)R.tupd.p, R.nupd,
-                                 st),
-         "shard group update");
-      if (tm && j == 0) {
-        ck(ctx, hipEventRecord(m.ev_upd[(size_t)m.upd_used + 1], st), "event");
-        m.upd_flops[(size_t)m.upd_used / 2] =
-            update_flops_group(R.hupd, m.naug, (int64_t)kg * NB, zsize(g), kx0, kx1);
-        m.upd_used += 2;
-      }
-    }
-    rec(E_BULK(g), st);
-    if (!more) break;
-    // side path of group g + 1 (its cross tiles were last touched by bulk g-1)
-    wait(side, g > 0 ? E_BULK(g - 1) : E_ASM);
-    const bool rest = zb > 1;
-    if (rest) {  // the rest of group g+1's cross on side2, concurrently
-      rec(E_S2A(g + 1), side);
-      wait(side2, E_S2A(g + 1));
-      for (size_t j = 0; j < v.size(); ++j) {
-        RankState &R = *m.ranks[j];
-        const int64_t p0 = R.poff[(size_t)(2 * (g + 1) + 1)], np = R.poff[(size_t)(2 * (g + 1) + 2)] - p0;
-        ck(ctx, shard_update_group(v[j], kg, zsize(g), NS, -1, -1, (const Tile *)R.tp.p + p0, np,
-                                   side2),
-           "shard group cross");
-      }
-      rec(E_S2B(g + 1), side2);
-    }
-    for (size_t j = 0; j < v.size(); ++j) {
-      RankState &R = *m.ranks[j];
-      const int64_t p0 = R.poff[(size_t)(2 * (g + 1))], np = R.poff[(size_t)(2 * (g + 1) + 1)] - p0;
-      ck(ctx, shard_update_group(v[j], kg, zsize(g), NS, -1, -1, (const Tile *)R.tp.p + p0, np, side,
-                                 fuse ? kb : -1),
-         "shard group cross");
-    }
-    prepare(kb, fuse);
-    if (rest) wait(side, E_S2B(g + 1));
-    inner(kb, zb);
-    rec(E_READY(g + 1), side);
-  }
 }
 
 }  // namespace
@@ -982,8 +742,7 @@ ShardModel *shard_create_any(ace_ctx *ctx, const Shape &s, int64_t n, int world,
   const int steps = (int)(npad / NB);
   // the head schedule in every mode (the host-callback group's head and tail
   // exchanges block the host one at a time, in issue order)
-  m->heads = shard_heads_on() && pair_steps() && steps >= 2 && m->Z >= 2 &&
-             (m->sim || m->proxy || m->host || rccl().CommSplit);
+  m->heads = pair_steps() && steps >= 2;
   if (m->heads && m->comm)
     nck(ctx, rccl().CommSplit(m->comm, 0, rank, &m->comm2, nullptr), "ncclCommSplit");
   if (m->comm) rccl_warmup(*m);
@@ -998,14 +757,13 @@ ShardModel *shard_create_any(ace_ctx *ctx, const Shape &s, int64_t n, int world,
     const int64_t nloc = ncols_local(naug, world, 0);
     alloc(ctx, R->A[0], (size_t)(naug * nloc) * sizeof(double), "alloc local A");
     ck(ctx, hipMemsetAsync(R->A[0].p, 0, R->A[0].bytes, ctx->stream), "memset A");
-    // group schedule: 2 Z panel slots (k % 2Z); the one-step schedule: 2
-    const int nslot = pair_steps() && steps >= 2 ? 2 * m->Z : 2;
+    // head schedule: 2 Z panel slots (k % 2Z); the one-step schedule: 2
+    const int nslot = m->heads ? 2 * m->Z : 2;
     for (int b = 0; b < nslot; ++b) {
       alloc(ctx, R->P[b], (size_t)(naug * NB) * sizeof(double), "alloc panel");
       alloc(ctx, R->W[b], (size_t)(naug * NB) * sizeof(double), "alloc panel");
     }
     for (int b = 0; b < 2; ++b) alloc(ctx, R->S[b], (size_t)(SUB * NB) * sizeof(double), "alloc S");
-    if (nslot > 2) build_cross_lists(ctx, *R, naug, steps, world, m->Z);
     if (m->heads) {
       build_head_lists(ctx, *R, naug, steps, world, m->Z);
       alloc(ctx, R->lowh, (size_t)(m->Z * NB * NB) * sizeof(double), "alloc head exchange");
@@ -1025,7 +783,7 @@ ShardModel *shard_create_any(ace_ctx *ctx, const Shape &s, int64_t n, int world,
     R->nupd = (int64_t)R->hupd.size();
     upload_tiles(ctx, R->tupd, R->hupd);
     std::vector<Tile> ta = own_tiles(npad / AT, AT, world, R->r);
-    // the first group's panels' columns first (the group schedule's first
+    // the first group's panels' columns first (the head schedule's first
     // side path runs under the rest of the assembly, as model_pipeline's)
     const int jb = m->Z * NB / AT;
     R->nasm1 = std::stable_partition(ta.begin(), ta.end(), [&](const Tile &t) { return t.J < jb; }) -
@@ -1051,11 +809,10 @@ ShardModel *shard_create_any(ace_ctx *ctx, const Shape &s, int64_t n, int world,
     alloc(ctx, R->augvec, (size_t)(2 * npad + 8) * sizeof(double), "alloc aug vector");
     m->ranks.push_back(std::move(R));
   }
-  // lookahead events: the step schedule's 2 steps + 1, the pair schedule's
-  // 4 ngroups + 2
-  const int ngr = (steps + m->Z - 1) / std::max(1, m->Z);
-  m->ev.assign((size_t)std::max({2 * steps + 1, 4 * ((steps + 1) / 2) + 2, 4 + 5 * ngr + 2 * steps}),
-               nullptr);
+  // lookahead events: the step schedule's 2 steps + 1, the head schedule's
+  // 4 + 5 ngroups + 2 steps (E_IN .. E_BULK)
+  const int ngr = (steps + m->Z - 1) / m->Z;
+  m->ev.assign((size_t)std::max(2 * steps + 1, 4 + 5 * ngr + 2 * steps), nullptr);
   for (auto &e : m->ev) ck(ctx, hipEventCreateWithFlags(&e, ACE_SYNC_EVENT_FLAGS), "event");
   m->ev_upd.assign((size_t)(2 * steps), nullptr);
   m->upd_flops.assign((size_t)steps, 0.0);

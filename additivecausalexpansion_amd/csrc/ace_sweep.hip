@@ -652,7 +652,7 @@ struct GatherOut {
   // block rows >= k0 into low (ld h, the pivot block's upper part mirrored)
   // and the rank's row pieces A[k-block, j-block], j < k, into send (slot =
   // local block index).  P / W / S0 (when set) receive the panel rows the
-  // rank owns, so that shard_unpack_chain only fills the rows of other ranks.
+  // rank owns, so that shard_unpack_part only fills the rows of other ranks.
   double *low = nullptr, *send = nullptr;
   int64_t h = 0;
   int G = 1;
@@ -2549,13 +2549,12 @@ hipError_t shard_pack(const ShardSweep &b, int k, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t shard_unpack_chain(const ShardSweep &b, int k, int buf, hipStream_t st, bool own_done) {
-  const int64_t k0 = (int64_t)k * NB, naug = b.ld;
-  if (!(own_done && b.G == 1))
-    hipLaunchKernelGGL(k_unpack_panel, dim3((unsigned)(naug / 64), NB / 64), dim3(256), 0, st,
-                       b.low, b.recv, shard_row_slots(k, b.G), b.G, k0, naug, b.P[buf], b.W[buf],
-                       b.ld, b.S[0], own_done ? 1 : 0, b.r);
-  panel_chain(b.P[buf], b.W[buf], b.ld, k0, b.SW, b.S, b.piv, b.flag, b.G, b.r, st);
+// every row of panel k from low and recv (shard_unpack_part's whole range:
+// k_unpack_panel's defaults), then the pivot chain and the panel GEMM
+hipError_t shard_unpack_chain(const ShardSweep &b, int k, int buf, hipStream_t st) {
+  const hipError_t e = shard_unpack_part(b, k, buf, 0, b.ld, b.low, 0, -1, false, st);
+  if (e != hipSuccess) return e;
+  panel_chain(b.P[buf], b.W[buf], b.ld, (int64_t)k * NB, b.SW, b.S, b.piv, b.flag, b.G, b.r, st);
   return hipGetLastError();
 }
 
@@ -2598,7 +2597,7 @@ hipError_t shard_update_group(const ShardSweep &b, int kb, int npan, int nslot, 
 // ---- the sharded head schedule's pieces (run_sweep_sharded_heads) ---------
 // Owner of block k: column rows [i_lo, i_hi) (>= k0) of its block into low
 // (row offset lr0, ld hh); with rows: also every rank's row pieces A[k, j < k]
-// into its all-gather slot (panel 0 / the unfused path).
+// into its all-gather slot (panel 0: no cross launch packs it).
 hipError_t shard_pack_part(const ShardSweep &b, int k, int64_t i_lo, int64_t i_hi, double *low,
                            int64_t lr0, int64_t hh, bool rows, hipStream_t st) {
   const int64_t k0 = (int64_t)k * NB, naug = b.ld;

@@ -208,31 +208,28 @@ np.savez({out!r}, g1=g1, s1=s1, g2=g2, s2=s2, inv=m.inverse())
 """
 
 
-@pytest.mark.parametrize("world,n", [(1, 2000), (3, 1700), (4, 2300)])
+@pytest.mark.parametrize("world,n", [(1, 2000), (3, 1700), (4, 2300), (2, 500), (3, 700)])
 def test_sharded_pair_schedule_is_bitwise_neutral(tmp_path, world, n):
-    """The sharded sweep's pair-step lookahead schedule (two steps per bulk
-    launch, second side stream, single-step cross on 128-tiles; ACE_PAIR=1,
-    default) and the one-step schedule (ACE_PAIR=0) give bit-identical
-    results: every tile sees the same MFMA chains in the same order; and so
-    does the exchange packing fused into the cross launches (default)
-    against separate pack launches (ACE_FUSE_PACK=0).  The
-    default runs the head / tail schedule (round 5: the single-GPU lists, the
-    exchange split into a head broadcast and a tail broadcast + all-gather);
-    ACE_SHARD_HEADS=0 the group schedule without the split.  n
-    gives 8, 7 (an odd last group) and 9 sweep steps; the simulated group
-    runs the lookahead with all ranks on the shared streams."""
+    """The sharded sweep's two schedules give bit-identical results: the
+    default head / tail schedule (Z steps per bulk launch, the single-GPU
+    head / tail lists on each rank's own tiles, the exchange packed by the
+    lookahead's cross launches and split into a head broadcast and a tail
+    broadcast + all-gather, three streams) and its referee, the one-step
+    schedule (ACE_PAIR=0: separate pack launches, one exchange and one
+    update launch per step).  Every tile sees the same MFMA chains in the
+    same order.  n gives 8, 7 (an odd last group) and 9 sweep steps, and the
+    two smallest sweeps of the head schedule: 2 steps (one group of two, the
+    smallest sweep that takes it) and 3 steps (one full group of Z = 3, no
+    group boundary); the simulated group runs the lookahead with all ranks
+    on the shared streams."""
     import os
-    import subprocess
-    import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = {}
-    variants = {"step": {"ACE_PAIR": "0"}, "pair": {"ACE_FUSE_PACK": "0"}, "fused": {},
-                "groups": {"ACE_SHARD_HEADS": "0"}}
+    variants = {"step": {"ACE_PAIR": "0"}, "default": {}}
     for v, extra in variants.items():
         out = str(tmp_path / f"s{v}.npz")
         env = dict(os.environ, **extra)
         run_child(_SCHED.format(root=root, n=n, world=world, out=out), env=env, timeout=100)
         outs[v] = np.load(out)
-    for v in ("pair", "fused", "groups"):
-        for k in ("g1", "s1", "g2", "s2", "inv"):
-            assert np.array_equal(outs["step"][k], outs[v][k]), (v, k)
+    for k in ("g1", "s1", "g2", "s2", "inv"):
+        assert np.array_equal(outs["step"][k], outs["default"][k]), k
