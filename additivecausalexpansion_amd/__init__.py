@@ -15,4 +15,4 @@ from .model import (  # noqa: F401
 from .r6 import R6KernelMatern32, R6KernelSE  # noqa: F401
 from .train import (  # noqa: F401
     AceFit, ace_train, ace_train_batch, coef_posterior, linear_spline, ns_spline, predict_ace,
-    response_surface, robust_treatment, set_basis, set_initial_parameters, square_spline)
+    predict_ace_batch, response_surface, robust_treatment, set_basis, set_initial_parameters, square_spline)

@@ -22,6 +22,7 @@ KIND = {"SE": ACE_KERNEL_SE, "Matern32": ACE_KERNEL_MATERN32}
 _D = ctypes.POINTER(ctypes.c_double)
 _I64 = ctypes.c_int64
 _I32 = ctypes.POINTER(ctypes.c_int32)
+_I64P = ctypes.POINTER(ctypes.c_int64)
 _vp = ctypes.c_void_p
 
 # name -> (restype, argtypes); must match include/ace_hip.h exactly
@@ -139,6 +140,10 @@ SIGNATURES = {
                                        ctypes.c_double, ctypes.c_int, ctypes.c_double, _D, _D,
                                        _I32, _I32, _I32]),
     "ace_batch_get_inverse": (ctypes.c_int, [_vp, _I64, _D]),
+    "ace_predict_batch": (ctypes.c_int, [_vp, _D, _I64P, _D, _D, _D, _D, _D, _D, _D]),
+    "ace_predict_marginal_batch": (ctypes.c_int, [_vp, _D, _I64P, _D, _D, _D, _D, _D, ctypes.c_int,
+                                                  _D, _D, _D, _D]),
+    "ace_set_inverse_batch": (ctypes.c_int, [_vp, _I64, _D]),
 }
 
 # ace_comm_ops (include/ace_hip.h): host-callback collectives

@@ -1,7 +1,9 @@
 // ace_batch.cpp -- host side of the batched engine (ace_batch_* of
 // include/ace_hip.h): per-model data slots, the scratch matrices, and the
 // training loop that enqueues k_batch_eval + k_batch_step pairs
-// (ace_batch.hip).
+// (ace_batch.hip), and batched prediction (ace_predict_batch,
+// ace_predict_marginal_batch, ace_set_inverse_batch; ace_batch_predict.hip,
+// DESIGN §16).
 #include <algorithm>
 
 #include "ace_batch.h"
@@ -26,6 +28,11 @@ struct ace_batch {
   DBuf theta, out;
   bool meta_dirty = true;      // dn / dstd behind the host copies
   bool has_inverse = false;
+  // prediction: per model, the non-positive-definite word of its own last
+  // para_update (0 / 1; 0 after ace_set_inverse_batch), and whether its
+  // inverse was installed from the host since its last set_data
+  DBuf dflag;
+  std::vector<char> installed;
 };
 
 namespace {
@@ -73,6 +80,102 @@ void ready(ace_batch *b) {
   b->meta_dirty = false;
 }
 
+// the result rows' non-positive-definite words into dflag: a model the train
+// loop skips keeps the word of its own last para_update there
+void keep_flags(ace_batch *b) {
+  ck(b->ctx,
+     hipMemcpy2DAsync(b->dflag.p, sizeof(double), b->out.d() + b->P + 3, (size_t)b->ldo * sizeof(double),
+                      sizeof(double), (size_t)b->M, hipMemcpyDeviceToDevice, b->ctx->stream),
+     "keep flags");
+}
+
+// The packed test side of a batched prediction on the device, the launch, and
+// the per-point sums back on the host: res = [a | kd | q] (N each), gcov (3 M).
+struct PredBatchArgs {
+  const double *theta, *X2, *Zt, *Z_x;
+  const int64_t *off;
+  bool marginal;
+  int ate;
+};
+
+void predict_batch_run(ace_batch *b, const PredBatchArgs &q, std::vector<double> &res,
+                       std::vector<double> &gcov) {
+  ace_ctx *ctx = b->ctx;
+  const Shape &s = b->s;
+  const int64_t M = b->M;
+  arg(ctx, q.theta && q.off && (s.p == 0 || q.X2) && (s.B == 1 || q.Zt), "null argument");
+  arg(ctx, q.off[0] == 0, "off[0] must be 0");
+  for (int64_t j = 0; j < M; ++j)
+    arg(ctx, q.off[j + 1] > q.off[j] && q.off[j + 1] - q.off[j] < (int64_t(1) << 30),
+        "off must increase: every model needs nx_j >= 1 test points");
+  ready(b);
+  for (int64_t j = 0; j < M; ++j)
+    arg(ctx, b->has_inverse || b->installed[(size_t)j],
+        "no resident inverse: call ace_batch_para_update() or ace_set_inverse_batch() first");
+  const int64_t N = q.off[M];
+  if (q.ate)
+    for (int64_t i = 0; i < N; ++i)
+      arg(ctx, q.Z_x[i] == 0.0 || q.Z_x[i] == 1.0, "Z_x must be 0 or 1 (binary treatment)");
+  need_bytes(ctx, (double)N * (s.PM + 2.0 * s.ZS + 4.0) * 8.0);
+  std::vector<double> xr((size_t)(N * s.PM), 0.0), zr((size_t)(N * s.ZS), 0.0);
+  for (int64_t j = 0; j < M; ++j) {
+    const int64_t o = q.off[j], nx = q.off[j + 1] - o;
+    if (s.p > 0) {
+      std::vector<double> t = pack_rows(q.X2 + o * s.p, nx, s.p, s.PM);
+      std::copy(t.begin(), t.end(), xr.begin() + o * s.PM);
+    }
+    if (s.B > 1) {
+      std::vector<double> t = pack_rows(q.Zt + o * (s.B - 1), nx, s.B - 1, s.ZS);
+      std::copy(t.begin(), t.end(), zr.begin() + o * s.ZS);
+    }
+  }
+  DBuf dX, dZ, dLZ, dzx, doff, dres;
+  upload(ctx, dX, xr.data(), xr.size(), "upload X2");
+  upload(ctx, dZ, zr.data(), zr.size(), "upload Z2");
+  alloc(ctx, dLZ, zr.size() * sizeof(double), "alloc log|Z2|");
+  if (s.kind == ACE_KERNEL_SE)
+    ck(ctx, launch_log_abs(dZ.d(), dLZ.d(), (int64_t)zr.size(), ctx->stream), "log_abs");
+  if (q.ate) upload(ctx, dzx, q.Z_x, (size_t)N, "upload Z_x");
+  alloc(ctx, doff, (size_t)(M + 1) * sizeof(int64_t), "alloc off");
+  upload_bytes(ctx, doff.p, q.off, (size_t)(M + 1) * sizeof(int64_t), "upload off");
+  upload_bytes(ctx, b->theta.p, q.theta, (size_t)(M * b->P) * sizeof(double), "upload theta");
+  alloc(ctx, dres, (size_t)(3 * N + 3 * M) * sizeof(double), "alloc results");
+  BatchPredView v;
+  v.M = (int)M;
+  v.nmax = (int)b->nmax;
+  v.p = s.p;
+  v.B = s.B;
+  v.PM = s.PM;
+  v.ZS = s.ZS;
+  v.marginal = q.marginal ? 1 : 0;
+  v.ate = q.ate ? 1 : 0;
+  v.ld = b->ld;
+  v.n = b->dn.i();
+  v.y = b->y.d();
+  v.X = b->X.d();
+  v.Z = b->Z.d();
+  v.LZ = b->LZ.d();
+  v.A = b->A.d();
+  v.flag = b->dflag.d();
+  v.theta = b->theta.d();
+  v.ldt = b->P;
+  v.off = static_cast<const int64_t *>(doff.p);
+  v.X2 = dX.d();
+  v.Z2 = dZ.d();
+  v.LZ2 = dLZ.d();
+  v.zx = q.ate ? dzx.d() : nullptr;
+  v.a = dres.d();
+  v.kd = dres.d() + N;
+  v.q = dres.d() + 2 * N;
+  v.gcov = dres.d() + 3 * N;
+  ck(ctx, launch_batch_predict(s.kind, v, ctx->stream), "batch predict");
+  res.resize((size_t)(3 * N));
+  gcov.assign((size_t)(3 * M), 0.0);
+  download(ctx, res.data(), dres.d(), res.size(), "download sums");
+  if (q.ate) download(ctx, gcov.data(), dres.d() + 3 * N, gcov.size(), "download group sums");
+  sync(ctx);
+}
+
 }  // namespace
 
 extern "C" {
@@ -105,6 +208,7 @@ int ace_batch_create(ace_ctx *ctx, int kind, int64_t M, int64_t nmax, int p, int
     b->ldo = b->P + 4;
     b->n.assign((size_t)M, 0);
     b->std_y.assign((size_t)M, 1.0);
+    b->installed.assign((size_t)M, 0);
     const double dM = (double)M;
     need_bytes(ctx, dM * (double)(b->ld * b->ld) * 16.0 + dM * (double)nmax * (s.PM + 2.0 * s.ZS + 1) * 8.0);
     alloc(ctx, b->dn, (size_t)M * sizeof(int), "alloc n");
@@ -116,6 +220,8 @@ int ace_batch_create(ace_ctx *ctx, int kind, int64_t M, int64_t nmax, int p, int
     alloc(ctx, b->A, (size_t)(M * b->ld * b->ld) * sizeof(double), "alloc batch scratch");
     alloc(ctx, b->theta, (size_t)(M * b->P) * sizeof(double), "alloc theta");
     alloc(ctx, b->out, (size_t)(M * b->ldo) * sizeof(double), "alloc results");
+    alloc(ctx, b->dflag, (size_t)M * sizeof(double), "alloc flags");
+    ck(ctx, hipMemsetAsync(b->dflag.p, 0, (size_t)M * sizeof(double), ctx->stream), "memset flags");
     ck(ctx, hipMemsetAsync(b->A.p, 0, b->A.bytes, ctx->stream), "memset scratch");
     ck(ctx, hipMemsetAsync(b->LZ.p, 0, b->LZ.bytes, ctx->stream), "memset LZ");
     sync(ctx);
@@ -165,6 +271,7 @@ int ace_batch_set_data(ace_batch *b, int64_t j, int64_t n_j, const double *y, co
   b->std_y[(size_t)j] = std_y;
   b->meta_dirty = true;
   b->has_inverse = false;
+  b->installed[(size_t)j] = 0;
   return ACE_OK;
   ACE_CATCH
 }
@@ -187,6 +294,7 @@ int ace_batch_para_update(ace_batch *b, int iter, double *theta, double *grad, d
   ck(ctx, launch_batch_eval(b->s.kind, view_of(b, b->A.d(), b->theta.d(), P, nullptr, 0, iter == 1),
                             ctx->stream),
      "batch eval");
+  keep_flags(b);
   std::vector<double> h((size_t)(M * b->ldo));
   download(ctx, h.data(), b->out.d(), h.size(), "download results");
   sync(ctx);
@@ -267,6 +375,7 @@ int ace_batch_train(ace_batch *b, int optimizer, double learn_rate, double momen
     }
   }
   read_ctl();
+  keep_flags(b);  // before the final stats' evaluation overwrites the result rows
   bool any_ok = false;
   for (int64_t j = 0; j < M; ++j) {
     const int it = ctl[(size_t)(2 * j)], stop = ctl[(size_t)(2 * j + 1)];
@@ -313,7 +422,7 @@ int ace_batch_get_inverse(ace_batch *b, int64_t j, double *inv) {
   ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
   arg(ctx, inv != nullptr, "null argument");
   arg(ctx, j >= 0 && j < b->M, "model index out of range");
-  arg(ctx, b->has_inverse && b->n[(size_t)j] > 0, "no para_update yet");
+  arg(ctx, (b->has_inverse || b->installed[(size_t)j]) && b->n[(size_t)j] > 0, "no para_update yet");
   const int64_t n = b->n[(size_t)j], ld = b->ld;
   std::vector<double> h((size_t)(ld * n));  // the model's first n columns hold -A^-1 (lower)
   download(ctx, h.data(), b->A.d() + j * ld * ld, h.size(), "download inverse");
@@ -324,6 +433,78 @@ int ace_batch_get_inverse(ace_batch *b, int64_t j, double *inv) {
       inv[r + c * n] = v;
       inv[c + r * n] = v;
     }
+  return ACE_OK;
+  ACE_CATCH
+}
+
+int ace_set_inverse_batch(ace_batch *b, int64_t j, const double *inv) {
+  if (!b) return ACE_ERR_ARG;
+  ace_ctx *ctx = b->ctx;
+  ACE_TRY
+  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+  arg(ctx, inv != nullptr, "null argument");
+  arg(ctx, j >= 0 && j < b->M, "model index out of range");
+  arg(ctx, b->n[(size_t)j] > 0, "ace_batch_set_data() not called for this model");
+  const int64_t n = b->n[(size_t)j], ld = b->ld;
+  // the model's first n columns: -inv in the lower triangle, zero elsewhere
+  // (prediction reads the n x n part only; a para_update assembles all anew)
+  std::vector<double> h((size_t)(ld * n), 0.0);
+  for (int64_t c = 0; c < n; ++c)
+    for (int64_t r = c; r < n; ++r) h[(size_t)(r + c * ld)] = -inv[r + c * n];
+  upload_bytes(ctx, b->A.d() + j * ld * ld, h.data(), h.size() * sizeof(double), "upload inverse");
+  const double zero = 0.0;
+  upload_bytes(ctx, b->dflag.d() + j, &zero, sizeof(double), "clear flag");
+  b->installed[(size_t)j] = 1;
+  return ACE_OK;
+  ACE_CATCH
+}
+
+int ace_predict_batch(ace_batch *b, const double *theta, const int64_t *off, const double *X2,
+                      const double *Z2, const double *mean_y, const double *std_y, double *map,
+                      double *ci, double *var) {
+  if (!b) return ACE_ERR_ARG;
+  ace_ctx *ctx = b->ctx;
+  ACE_TRY
+  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+  arg(ctx, mean_y && std_y && map && ci && var, "null argument");
+  std::vector<double> res, gcov;
+  predict_batch_run(b, PredBatchArgs{theta, X2, Z2, nullptr, off, false, 0}, res, gcov);
+  const int64_t N = off[b->M];
+  for (int64_t j = 0; j < b->M; ++j) {
+    const int64_t o = off[j], nx = off[j + 1] - o;
+    const double *th = theta + j * b->P;
+    finish_pred(nx, res.data() + o, res.data() + N + o, res.data() + 2 * N + o, th[0], th[1],
+                mean_y[j], std_y[j], map + o, ci + 2 * o, var + o);
+  }
+  return ACE_OK;
+  ACE_CATCH
+}
+
+int ace_predict_marginal_batch(ace_batch *b, const double *theta, const int64_t *off,
+                               const double *X2, const double *dZ2, const double *Z_x,
+                               const double *std_y, const double *std_Z, int calculate_ate,
+                               double *map, double *ci, double *var, double *avg) {
+  if (!b) return ACE_ERR_ARG;
+  ace_ctx *ctx = b->ctx;
+  ACE_TRY
+  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+  arg(ctx, std_y && std_Z && map && ci && var, "null argument");
+  arg(ctx, !calculate_ate || (Z_x && avg), "calculate_ate needs Z_x and avg");
+  std::vector<double> res, gcov;
+  predict_batch_run(b, PredBatchArgs{theta, X2, dZ2, Z_x, off, true, calculate_ate ? 1 : 0}, res,
+                    gcov);
+  const int64_t N = off[b->M];
+  for (int64_t j = 0; j < b->M; ++j) {
+    const int64_t o = off[j], nx = off[j + 1] - o;
+    // the three quadratic forms from the two groups' covariance (g: untreated,
+    // treated), summed as ace_model_robust_treatment sums its groups
+    const double ctt = gcov[(size_t)(3 * j)], ctu = gcov[(size_t)(3 * j + 1)],
+                 cuu = gcov[(size_t)(3 * j + 2)];
+    const double post[3] = {((cuu + ctu) + ctu) + ctt, ctt, cuu};
+    finish_marginal(nx, res.data() + o, res.data() + N + o, res.data() + 2 * N + o, std_y[j],
+                    std_Z[j], calculate_ate ? Z_x + o : nullptr, calculate_ate ? post : nullptr,
+                    map + o, ci + 2 * o, var + o, calculate_ate ? avg + 12 * j : nullptr);
+  }
   return ACE_OK;
   ACE_CATCH
 }

@@ -34,9 +34,6 @@ namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-// threads of k_batch_eval: eight waves where the per-lane feature arrays leave
-// room for them (two waves per SIMD hide the scratch matrix's latency), four above
-__host__ __device__ constexpr int batch_threads(int PM) { return PM <= 16 ? 512 : 256; }
 constexpr int DP = BT + 1;  // pitch of the pivot block in LDS
 
 __device__ __forceinline__ double bsgn(double x) { return (double)((0.0 < x) - (x < 0.0)); }

@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 
 from . import native
-from ._lib import KIND, UNIQUE_ID_BYTES, AceError, check, default_context, fmat, lib, ptr
+from ._lib import _I64P, KIND, UNIQUE_ID_BYTES, AceError, check, default_context, fmat, lib, ptr
 
 
 class DeviceModel:
@@ -339,6 +339,99 @@ class BatchModel:
         out = np.empty((n, n), order="F")
         check(lib().ace_batch_get_inverse(self.handle, int(j), ptr(out)), self.ctx.handle)
         return out
+
+    def set_inverse(self, j, inv):
+        """ace_set_inverse_batch: inv (n_j x n_j, symmetric) becomes model j's
+        resident inverse (after its set_data)."""
+        n = self.n[int(j)] if 0 <= int(j) < self.M else 0
+        a = np.asfortranarray(np.asarray(inv, dtype=np.float64))
+        if n and a.shape != (n, n):
+            raise AceError(f"ACE_ERR_ARG: the inverse of model {j} must be {n} x {n}")
+        check(lib().ace_set_inverse_batch(self.handle, int(j), ptr(a)), self.ctx.handle)
+
+    def _pack_test(self, theta, X2s, Zts):
+        """theta (P x M), and the packed test side: off (M + 1), every model's
+        X2 block (nx_j x p) and basis block (nx_j x (B - 1)), column-major."""
+        th = np.asfortranarray(np.asarray(theta, dtype=np.float64))
+        if th.shape != (self.P, self.M) or len(X2s) != self.M or len(Zts) != self.M:
+            raise AceError(f"ACE_ERR_ARG: theta must be P x M = {self.P} x {self.M} and the test "
+                           "sides sequences of length M")
+        xs = [np.asfortranarray(np.asarray(x, dtype=np.float64)) for x in X2s]
+        xs = [x.reshape(-1, self.p, order="F") if self.p else x.reshape(-1, 0) for x in xs]
+        nx = [x.shape[0] for x in xs]
+        off = np.zeros(self.M + 1, dtype=np.int64)
+        off[1:] = np.cumsum(nx)
+        zs = []
+        for j, z in enumerate(Zts):
+            z = (np.asfortranarray(np.asarray(z, dtype=np.float64)) if self.B > 1
+                 else np.zeros((nx[j], 0)))
+            if z.size != nx[j] * (self.B - 1):
+                raise AceError(f"ACE_ERR_ARG: the test basis of model {j} must be nx_j x (B - 1) = "
+                               f"{nx[j]} x {self.B - 1}")
+            zs.append(z.reshape(nx[j], self.B - 1, order="F"))
+        cat = lambda blocks: np.ascontiguousarray(  # noqa: E731
+            np.concatenate([np.ravel(b, order="F") for b in blocks]) if blocks else np.empty(0))
+        return th, off, cat(xs), cat(zs)
+
+    def _per_model(self, v):
+        a = np.ravel(np.asarray(v, dtype=np.float64))
+        if a.size == 1:
+            a = np.full(self.M, a[0])
+        if a.size != self.M:
+            raise AceError("ACE_ERR_ARG: a moment must be a scalar or have length M")
+        return np.ascontiguousarray(a)
+
+    def predict(self, theta, X2s, Z2s, mean_y, std_y):
+        """ace_predict_batch: pred_cpp of every model in one launch, each with
+        its own resident inverse (Q6) and kernels at its column of theta.
+        X2s, Z2s: sequences of length M; mean_y, std_y: scalars or length M.
+        Returns a list of M dicts {"map", "ci", "var"}."""
+        th, off, x2, z2 = self._pack_test(theta, X2s, Z2s)
+        my, sy = self._per_model(mean_y), self._per_model(std_y)
+        N = int(off[-1])
+        mp, var, ci = np.empty(N), np.empty(N), np.empty(2 * N)
+        check(lib().ace_predict_batch(self.handle, ptr(th), off.ctypes.data_as(_I64P), ptr(x2),
+                                      ptr(z2), ptr(my), ptr(sy), ptr(mp), ptr(ci), ptr(var)),
+              self.ctx.handle)
+        return [self._split(off, j, mp, ci, var) for j in range(self.M)]
+
+    @staticmethod
+    def _split(off, j, mp, ci, var):
+        o, e = int(off[j]), int(off[j + 1])
+        return {"map": mp[o:e].copy(), "ci": ci[2 * o:2 * e].reshape(e - o, 2, order="F").copy(order="F"),
+                "var": var[o:e].copy()}
+
+    def predict_marginal(self, theta, X2s, dZ2s, Z_xs, std_y, std_Z, calculate_ate=False):
+        """ace_predict_marginal_batch: pred_marginal_cpp of every model in one
+        launch; with calculate_ate also "ate" / "att" / "atu" per model, as
+        DeviceModel.predict_marginal gives them (Z_xs: the binary treatment of
+        every model's test points)."""
+        th, off, x2, dz = self._pack_test(theta, X2s, dZ2s)
+        sy, sz = self._per_model(std_y), self._per_model(std_Z)
+        N = int(off[-1])
+        zx = avg = None
+        if calculate_ate:
+            if len(Z_xs) != self.M:
+                raise AceError("ACE_ERR_ARG: Z_xs must have length M")
+            zx = np.ascontiguousarray(np.concatenate([np.ravel(np.asarray(z, dtype=np.float64))
+                                                      for z in Z_xs]))
+            if zx.size != N:
+                raise AceError("ACE_ERR_ARG: Z_xs must hold one value per test point")
+            avg = np.empty((12, self.M), order="F")
+        mp, var, ci = np.empty(N), np.empty(N), np.empty(2 * N)
+        check(lib().ace_predict_marginal_batch(self.handle, ptr(th), off.ctypes.data_as(_I64P),
+                                               ptr(x2), ptr(dz), ptr(zx), ptr(sy), ptr(sz),
+                                               1 if calculate_ate else 0, ptr(mp), ptr(ci),
+                                               ptr(var), ptr(avg)), self.ctx.handle)
+        outs = []
+        for j in range(self.M):
+            out = self._split(off, j, mp, ci, var)
+            if calculate_ate:
+                for k, key in enumerate(("ate", "att", "atu")):
+                    a = avg[4 * k:4 * k + 4, j]
+                    out[key] = {"map": a[0], "ci": np.array([a[1], a[2]]), "var": a[3]}
+            outs.append(out)
+        return outs
 
     def close(self):
         if getattr(self, "handle", None):

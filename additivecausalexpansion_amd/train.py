@@ -243,7 +243,8 @@ def ace_train_batch(ys, Xs, Zs, pis=None, kernel="SE", basis="linear", n_knots=1
     of length M (multi-start: pass the same dataset M times).  The datasets
     must agree in p and in the basis dimension B.  Returns a list of AceFit;
     each carries its model's inverse of the last para_update on the host
-    (Q6), so predict_ace runs through the host-buffer path.  A model whose
+    (Q6), so predict_ace runs through the host-buffer path; predict_ace_batch
+    predicts for all of them in one batched call.  A model whose
     gradient becomes non-finite stops alone: nonfinite="raise" then raises
     AceError naming the models (ace_train's behaviour), nonfinite="none" puts
     None in their places and returns the other fits."""
@@ -323,10 +324,9 @@ def ace_train_batch(ys, Xs, Zs, pis=None, kernel="SE", basis="linear", n_knots=1
     return fits
 
 
-def predict_ace(obj, newX=None, newZ=None, marginal=False, return_average_treatments=False,
-                normalize=True):
-    """R/predict.ace.R:30-99 (predict.ace)."""
-    isbinary = obj["train_data"]["Zbinary"]
+def _test_points(obj, newX, newZ, normalize):
+    """predict.ace's argument handling (R/predict.ace.R:30-80): the normalised
+    test points (Xn, Zn) of one fit for the four newX / newZ cases."""
     X = obj["train_data"]["X"]
     px = X.shape[1]
     pz = obj["train_data"]["Z"].shape[1]
@@ -359,6 +359,18 @@ def predict_ace(obj, newX=None, newZ=None, marginal=False, return_average_treatm
             Zn = np.array(newZ, dtype=np.float64, order="F", copy=True).reshape(-1, pz, order="F")
         if normalize:
             native.normalize_test(Xn, Zn, mom)
+    return Xn, Zn
+
+
+def predict_ace(obj, newX=None, newZ=None, marginal=False, return_average_treatments=False,
+                normalize=True):
+    """R/predict.ace.R:30-99 (predict.ace)."""
+    isbinary = obj["train_data"]["Zbinary"]
+    X = obj["train_data"]["X"]
+    px = X.shape[1]
+    pz = obj["train_data"]["Z"].shape[1]
+    mom = obj["moments"]
+    Xn, Zn = _test_points(obj, newX, newZ, normalize)
     K = obj["Kernel"]
     y = obj["train_data"]["y"]
     Btr = obj["Basis"].B
@@ -368,6 +380,75 @@ def predict_ace(obj, newX=None, newZ=None, marginal=False, return_average_treatm
     return K.predict_marginal(y, X, Btr, Xn, tb["B"], tb["dB"], mom[0, 0], mom[0, 1],
                               mom[1 + px:1 + px + pz, 1],
                               bool(np.all(isbinary)) and return_average_treatments)
+
+
+def predict_ace_batch(fits, newXs=None, newZs=None, marginal=False,
+                      return_average_treatments=False, normalize=True):
+    """predict_ace of M fits of small models (n <= 512 each, one kernel, p and
+    B) in one batched call: what [predict_ace(f, newX_j, newZ_j, ...) for f in
+    fits] returns, with one workgroup per fit on one GPU
+    (BatchModel.predict / predict_marginal).  newXs / newZs: None, or
+    sequences of length M whose entries are what predict_ace takes (None
+    included).  The fits may come from ace_train_batch or from ace_train; each
+    one's inverse of its last para_update (Q6) is installed next to its
+    training data, and the kernels are evaluated at its final parameters."""
+    from .model import BatchModel
+    fits = list(fits)
+    M = len(fits)
+    if M < 1:
+        raise AceError("fits must hold at least one fit")
+    if any(f is None for f in fits):
+        bad = [j for j, f in enumerate(fits) if f is None]
+        raise AceError(f"fits {bad} are None (models that ace_train_batch could not fit)")
+    if newZs is not None and not isinstance(newZs, (list, tuple)) and np.size(newZs) == 1:
+        newZs = [newZs] * M  # one treatment value for every test point of every fit
+    for name, v in (("newXs", newXs), ("newZs", newZs)):
+        if v is not None and (not isinstance(v, (list, tuple)) or len(v) != M):
+            raise AceError(f"{name} must be None or a sequence of length M = {M}")
+    K0 = fits[0]["Kernel"]
+    for j, f in enumerate(fits):
+        K = f["Kernel"]
+        if K.kernel != K0.kernel:
+            raise AceError(f"fit {j} uses kernel {K.kernel}, fit 0 {K0.kernel}: the fits of a "
+                           "batch must use one kernel")
+        if K.p != K0.p:
+            raise AceError(f"fit {j} has p = {K.p}, fit 0 has p = {K0.p}")
+        if K.B != K0.B:
+            raise AceError(f"fit {j} has basis dimension B = {K.B}, fit 0 has B = {K0.B}")
+        n = f["train_data"]["y"].size
+        if n > BATCH_NMAX:
+            raise AceError(f"fit {j}: n = {n} > {BATCH_NMAX}, the batched engine's limit (use "
+                           "predict_ace)")
+    px, B = K0.p, K0.B
+    pts = [_test_points(f, None if newXs is None else newXs[j],
+                        None if newZs is None else newZs[j], normalize)
+           for j, f in enumerate(fits)]
+    tbs = [f["Basis"].testbasis(Zn) for f, (_, Zn) in zip(fits, pts)]
+    theta = np.asfortranarray(np.column_stack([f["Kernel"].parameters for f in fits]))
+    nmax = max(f["train_data"]["y"].size for f in fits)
+    bm = BatchModel(K0.kernel, M, nmax, px, B, ctx=K0.ctx)
+    try:
+        for j, f in enumerate(fits):
+            bm.set_data(j, f["train_data"]["y"], f["train_data"]["X"], f["Basis"].B,
+                        f["moments"][0, 1])
+            bm.set_inverse(j, f["Kernel"].invKmatn)
+        Xns = [q[0] for q in pts]
+        if not marginal:
+            return bm.predict(theta, Xns, [t["B"] for t in tbs],
+                              [f["moments"][0, 0] for f in fits],
+                              [f["moments"][0, 1] for f in fits])
+        ate = [bool(np.all(f["train_data"]["Zbinary"])) and return_average_treatments
+               for f in fits]
+        if any(ate) != all(ate):
+            raise AceError("return_average_treatments needs a binary treatment in every fit of "
+                           "the batch, or in none")
+        pz = fits[0]["train_data"]["Z"].shape[1]
+        return bm.predict_marginal(
+            theta, Xns, [t["dB"] for t in tbs], [t["B"] for t in tbs],
+            [f["moments"][0, 1] for f in fits],
+            [np.ravel(f["moments"][1 + px:1 + px + pz, 1])[0] for f in fits], ate[0])
+    finally:
+        bm.close()
 
 
 def robust_treatment(obj, newX=None, n_steps=5):

@@ -517,8 +517,9 @@ int ace_model_create_sharded_host(ace_ctx *ctx, int kind, int64_t n, int p, int 
  * Errors: nmax > 512, p > 64 or B > 32 ACE_ERR_UNSUPPORTED; M < 1, j or n_j
  * out of range, or a call that needs data before every model has some
  * ACE_ERR_ARG; an allocation that does not fit ACE_ERR_OOM.
- * Out of scope: sharded batches (single GPU only) and the ace_dmat handle
- * path. */
+ * Out of scope: sharded batches (single GPU only), the ace_dmat handle
+ * path, and on batches grouped sums / robust_treatment, coefficient
+ * posteriors and response surfaces (prediction and ATE/ATT/ATU are below). */
 typedef struct ace_batch ace_batch;
 int ace_batch_create(ace_ctx *ctx, int kind, int64_t M, int64_t nmax, int p, int B,
                      ace_batch **out);
@@ -545,6 +546,43 @@ int ace_batch_train(ace_batch *b, int optimizer, double learn_rate, double momen
                     double *theta, double *stats, int *iters, int *converged, int *status);
 /* model j's resident inverse (n_j x n_j) of its last para_update */
 int ace_batch_get_inverse(ace_batch *b, int64_t j, double *inv);
+
+/* Posterior prediction of every model of a batch in one launch, one
+ * workgroup per model.  Kernels at the caller's theta
+ * (P x M), the inverse each model's resident one (Q6): that of its own last
+ * para_update, or the one ace_set_inverse_batch installed.  Per model the
+ * meaning of map, ci, var and avg is exactly ace_model_predict's /
+ * ace_model_predict_marginal's; a model's outputs are bitwise reproducible
+ * and depend neither on M nor on its position in the batch.  A model whose
+ * last para_update met a matrix that is not positive definite gets NaN in
+ * all its outputs; the others are untouched by it.
+ * Packed layout: off has M + 1 entries, off[0] = 0, model j has
+ * nx_j = off[j + 1] - off[j] >= 1 test points.  Model j's X2 block at
+ * X2 + off[j] p (column-major nx_j x p), its Z2 / dZ2 block at
+ * + off[j] (B - 1) (column-major nx_j x (B - 1); may be NULL when B == 1),
+ * Z_x, map and var at + off[j], ci at ci + 2 off[j] (column-major nx_j x 2).
+ * mean_y, std_y, std_Z: M entries each.  avg: 12 x M column-major, may be
+ * NULL (like Z_x) when calculate_ate == 0; with calculate_ate Z_x must be
+ * binary (0 or 1).
+ * Limits: n <= 512, p <= 64, B <= 32, single GPU.
+ * Errors: a null pointer that is read, a non-monotone off or an empty
+ * model, a model without data or with neither a para_update nor a
+ * set_inverse, j out of range, a Z_x that is not binary ACE_ERR_ARG; an
+ * allocation that does not fit ACE_ERR_OOM; a bounded sync that ran out
+ * ACE_ERR_TIMEOUT. */
+int ace_predict_batch(ace_batch *b, const double *theta, const int64_t *off,
+                      const double *X2, const double *Z2, const double *mean_y,
+                      const double *std_y, double *map, double *ci, double *var);
+int ace_predict_marginal_batch(ace_batch *b, const double *theta, const int64_t *off,
+                               const double *X2, const double *dZ2, const double *Z_x,
+                               const double *std_y, const double *std_Z, int calculate_ate,
+                               double *map, double *ci, double *var, double *avg);
+/* Installs a host inverse (n_j x n_j, symmetric: the lower triangle is read)
+ * as model j's resident one and clears the model's not-positive-definite
+ * mark; needs the model's set_data first.  After
+ * ace_set_inverse_batch(b, j, <what ace_batch_get_inverse(b, j) gave>)
+ * predictions are bitwise unchanged. */
+int ace_set_inverse_batch(ace_batch *b, int64_t j, const double *inv);
 
 #ifdef __cplusplus
 }
