@@ -292,8 +292,7 @@ int ace_grad(ace_ctx *ctx, int kind, int64_t n, int p, int B, const double *y, c
   sync(ctx);
   compose_grad(s, theta, gs.data(), sums[2], grad);
   const double logdet = host_logsum(eigenval, n);
-  stats[0] = std_y * std::sqrt(sums[0]) / std::sqrt((double)n);
-  stats[1] = -0.5 * (n * std::log(2.0 * M_PI) + logdet + sums[1]);
+  train_stats(std_y, (double)n, sums[0], logdet, sums[1], &stats[0], &stats[1]);
   return ACE_OK;
   ACE_CATCH
 }
@@ -323,8 +322,7 @@ int ace_stats(ace_ctx *ctx, int64_t n, const double *y, const double *Kmat, cons
   double sums[4];
   download(ctx, sums, dsums.d(), 4, "download");
   sync(ctx);
-  out[0] = std_y * std::sqrt(sums[0]) / std::sqrt((double)n);
-  out[1] = -0.5 * (n * std::log(2.0 * M_PI) + host_logsum(eigenval, n) + sums[1]);
+  train_stats(std_y, (double)n, sums[0], host_logsum(eigenval, n), sums[1], &out[0], &out[1]);
   return ACE_OK;
   ACE_CATCH
 }
@@ -695,21 +693,15 @@ void model_collect_timing(ace_model *m, int ts) {
   m->t_work[2] += pairs * (4 * B * p + 2 * p) + (m->s.kind == ACE_KERNEL_MATERN32 ? pairs * B * p : 0);
 }
 
-// Host syncs of the device-fused training loop: every ACE_TRAIN_SYNC
-// iterations (default 4).  Iterations enqueued after the one that converged
-// still run but change nothing in theta or the stats (k_train_step checks the
-// stop flag); their evaluations do overwrite the resident inverse, so the
-// stopping iteration's evaluation is re-run once at its saved theta.  A fit
-// spends at most ACE_TRAIN_SYNC extra evaluations.
-int train_sync_every() {
-  static const int v = std::max(1, env_int("ACE_TRAIN_SYNC", 4));
-  return v;
-}
-
 // ace_model_train of an unsharded model: theta, the optimizer moments and
 // the stats matrix live in HBM; each iteration is the evaluation pipeline
 // (tables from the device theta) + k_train_step, enqueued without a host
-// round trip.
+// round trip.  The host reads the stop words every train_sync_every()
+// iterations.  Iterations enqueued after the one that converged still run but
+// change nothing in theta or the stats (k_train_step checks the stop flag);
+// their evaluations do overwrite the resident inverse, so the stopping
+// iteration's evaluation is re-run once at its saved theta.  A fit spends at
+// most that many extra evaluations.
 int train_device(ace_model *m, int optimizer, double learn_rate, double momentum, double beta1,
                  double beta2, int norm_clip, double clip_at, int maxiter, double tol,
                  double *theta, double *stats, int *iters, int *converged) {
@@ -729,14 +721,7 @@ int train_device(ace_model *m, int optimizer, double learn_rate, double momentum
   alloc(ctx, dctl, 4 * sizeof(int), "alloc train control");
   ck(ctx, hipMemsetAsync(dctl.p, 0, 4 * sizeof(int), st), "memset control");
   TrainCfg c;
-  c.optimizer = optimizer;
-  c.lr = learn_rate;
-  c.momentum = momentum;
-  c.beta1 = beta1;
-  c.beta2 = beta2;
-  c.clip = norm_clip;
-  c.clip_at = clip_at;
-  c.tol = tol;
+  c.opt = opt_cfg(optimizer, learn_rate, momentum, beta1, beta2, norm_clip, clip_at, tol);
   c.P = P;
   c.B = s.B;
   c.p = s.p;
@@ -1015,8 +1000,7 @@ int ace_model_para_update(ace_model *m, int iter, double *theta, double *grad, d
   m->has_inverse = true;
   if (iter == 1) theta[1] = scal[3];  // mean_solution before the gradient (R/kernel_SE_R6.R:45)
   compose_grad(s, theta, gs.data(), sums[2], grad);
-  stats[0] = m->std_y * std::sqrt(sums[0]) / std::sqrt((double)m->n);
-  stats[1] = -0.5 * (m->n * std::log(2.0 * M_PI) + sums[3] + sums[1]);
+  train_stats(m->std_y, (double)m->n, sums[0], sums[3], sums[1], &stats[0], &stats[1]);
   if (mu_post) *mu_post = scal[3];
   if (flag) {  // not positive definite: the reference's outputs are non-finite
     const int P = 2 + s.B * (s.p + 1);
@@ -1052,8 +1036,7 @@ int ace_model_train_stats(ace_model *m, const double *theta, double *stats) {
     std::copy(hs, hs + 4, sums);
     flag = hs[4] != 0.0;
   }
-  stats[0] = m->std_y * std::sqrt(sums[0]) / std::sqrt((double)m->n);
-  stats[1] = -0.5 * (m->n * std::log(2.0 * M_PI) + sums[3] + sums[1]);
+  train_stats(m->std_y, (double)m->n, sums[0], sums[3], sums[1], &stats[0], &stats[1]);
   if (flag) stats[0] = stats[1] = kNaN;
   return ACE_OK;
   ACE_CATCH

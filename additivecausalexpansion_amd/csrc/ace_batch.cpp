@@ -9,13 +9,6 @@
 #include "ace_batch.h"
 #include "ace_common.h"
 
-// host read-backs of the stop words: every ACE_TRAIN_SYNC iterations
-// (default 4), the cadence of ace_model_train's device loop
-static int train_sync_every() {
-  static const int v = std::max(1, env_int("ACE_TRAIN_SYNC", 4));
-  return v;
-}
-
 struct ace_batch {
   ace_ctx *ctx = nullptr;
   Shape s;       // s.PM is the batch kernels' own bucket
@@ -336,14 +329,7 @@ int ace_batch_train(ace_batch *b, int optimizer, double learn_rate, double momen
   alloc(ctx, dctl, (size_t)(2 * M) * sizeof(int), "alloc train control");
   ck(ctx, hipMemsetAsync(dctl.p, 0, (size_t)(2 * M) * sizeof(int), st), "memset control");
   BatchStepCfg c;
-  c.optimizer = optimizer;
-  c.lr = learn_rate;
-  c.momentum = momentum;
-  c.beta1 = beta1;
-  c.beta2 = beta2;
-  c.clip = norm_clip;
-  c.clip_at = clip_at;
-  c.tol = tol;
+  c.opt = opt_cfg(optimizer, learn_rate, momentum, beta1, beta2, norm_clip, clip_at, tol);
   c.P = P;
   c.M = (int)M;
   const int K = train_sync_every();

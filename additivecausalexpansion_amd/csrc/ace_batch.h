@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ace_formulas.h"
+
 namespace ace {
 
 constexpr int BATCH_NMAX = 512;  // rows of the largest model one workgroup takes
@@ -47,13 +49,10 @@ struct BatchView {
 hipError_t launch_batch_eval(int kind, const BatchView &v, hipStream_t st);
 
 struct BatchStepCfg {
-  int optimizer;
-  double lr, momentum, beta1, beta2;
-  int clip;
-  double clip_at, tol;
+  OptCfg opt;
   int P, M;
 };
-// k_train_step's logic per model: st + j 3 P = [theta | m1 | m2], hist + j ldh
+// ace_model_train's per-iteration tail per model: st + j 3 P = [theta | m1 | m2], hist + j ldh
 // the model's stats matrix, ctl as above, out as k_batch_eval left it.
 hipError_t launch_batch_step(const BatchStepCfg &c, int it, const double *out, int64_t ldo,
                              double *st, double *hist, int64_t ldh, int *ctl, hipStream_t stream);

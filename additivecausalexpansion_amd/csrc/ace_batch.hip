@@ -5,8 +5,13 @@
 //                            in-place SPD inverse + log-determinant with the
 //                            right-hand sides [y, 1] carried along, alpha, the
 //                            gradient sums, and the composed gradient / stats;
-//   k_batch_step           : k_train_step's logic (ace_train.hip), one wave per
-//                            model.
+//   k_batch_step           : the training loop's per-iteration tail (clip,
+//                            optimizer, mu overwrite, stop tests), one wave
+//                            per model.
+//
+// The arithmetic is that of ace_formulas.h (kval, tab_weight, grad_entry,
+// train_stats, clip_on, opt_update), shared with the host and the single-model
+// kernels; this file keeps the LDS layouts and the order of every sum.
 //
 // Workgroup j touches model j's data and scratch only: no grid barrier, no
 // flag polling, no atomics -- a launch needs no co-residency and never waits
@@ -30,56 +35,7 @@ namespace ace {
 
 namespace {
 
-#define SQRT3 1.7320508075688772
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 constexpr int DP = BT + 1;  // pitch of the pivot block in LDS
-
-__device__ __forceinline__ double bsgn(double x) { return (double)((0.0 < x) - (x < 0.0)); }
-
-// kval of ace_pairs.hip (symmetric form): "lo" is the smaller index of the pair
-template <int KIND>
-__device__ __forceinline__ double bkval(int b, double r2, double lam, double zlo, double zhi,
-                                        double lzlo, double lzhi) {
-  if (KIND == 0) {
-    if (b == 0) return exp(lam - r2);
-    if (zlo == 0.0 || zhi == 0.0) return 0.0;
-    return (bsgn(zlo) * bsgn(zhi)) * exp(((lam - r2) + lzlo) + lzhi);
-  } else {
-    const double t = sqrt(r2);
-    const double e = (1.0 + SQRT3 * t) * exp(lam - SQRT3 * t);
-    if (b == 0) return e;
-    if (zlo == 0.0) return 0.0;
-    return (e * zlo) * zhi;
-  }
-}
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// the NW per-wave partials at sh[q stride], added in a fixed order
-template <int NW>
-__device__ __forceinline__ double wave_parts(const double *sh, int stride) {
-  double r = (sh[0] + sh[stride]) + (sh[2 * stride] + sh[3 * stride]);
-  if (NW == 8)
-    r += (sh[4 * stride] + sh[5 * stride]) + (sh[6 * stride] + sh[7 * stride]);
-  return r;
-}
-
-// sum over the workgroup in a fixed order; every thread gets it.  sh: NW doubles
-template <int NW>
-__device__ __forceinline__ double bsum(double v, double *sh) {
-  v = wsum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = wave_parts<NW>(sh, 1);
-  __syncthreads();
-  return r;
-}
 
 // LDS map (doubles).  Fixed head: scal[16], the pivot block D[2][BT][DP].
 // Behind it one region used twice: by the sweep as the panels P and W
@@ -133,7 +89,7 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
       double v = 0.0;
       if (e < 2 * nk) {
         const int gi = e >= nk, q = e - gi * nk, b = q / PM, i = q - b * PM;
-        if (i < p) v = exp(-th[gi ? 2 + B + b + B * i : 1 + b + B * (i + 1)]);  // Q1
+        if (i < p) v = tab_weight(th, B, b, i, gi);
       } else if (e < 2 * nk + B) {
         v = th[2 + (e - 2 * nk)];
       } else {
@@ -176,7 +132,7 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
               lzc = LZ[(int64_t)c * ZS + b - 1];
             }
           }
-          kf += bkval<KIND>(b, r2, sLam[b], zc, zr, lzc, lzr);
+          kf += kval<KIND, false>(b, r2, sLam[b], zc, zr, lzc, lzr);  // c: the smaller index
         }
         v = (r == c) ? kf + sLam[B] : kf;
       } else if (r < npad) {
@@ -334,9 +290,9 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
     sa += al;
   }
   for (int e = tid; e < B * (PM + 1) + 1; e += NTHR) sG[e] = 0.0;
-  e2 = bsum<NW>(e2, sSum);
-  ya = bsum<NW>(ya, sSum);
-  sa = bsum<NW>(sa, sSum);
+  e2 = block_sum<NW>(e2, sSum);
+  ya = block_sum<NW>(ya, sSum);
+  sa = block_sum<NW>(sa, sSum);
 
   // ---- gradient sums: T = A^-1 - alpha alpha^T over the lower pairs ---------
   for (int h = 0; NTHR * h < n; ++h) {  // (block-uniform)
@@ -381,7 +337,7 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
             zc = Z[(int64_t)c * ZS + b - 1];
             if (KIND == 0) lzc = LZ[(int64_t)c * ZS + b - 1];
           }
-          const double kb = bkval<KIND>(b, r2, lam, zc, zr, lzc, lzr);
+          const double kb = kval<KIND, false>(b, r2, lam, zc, zr, lzc, lzr);
           gl = fma(t, kb, gl);
           const double U = KIND == 0 ? t * kb : t * (kb / (1.0 + sqrt(3.0 * rt2)));
           if (GC == PM) {
@@ -407,13 +363,13 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
         // fixed-order reduction: lanes of a wave, then the waves
 #pragma unroll
         for (int i = 0; i < GC; ++i) {
-          const double v = wsum(g[i]);
+          const double v = wsum64(g[i]);
           if (lane == 0) sRed[wv * (PM + 1) + i0 + i] = v;
         }
         if (i0 == 0) {
-          const double v = wsum(gl);
+          const double v = wsum64(gl);
           if (lane == 0) sRed[wv * (PM + 1) + PM] = v;
-          const double w = wsum(tr);
+          const double w = wsum64(tr);
           if (lane == 0) sSum[wv] = w;
         }
       }
@@ -426,28 +382,17 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
   }
   __syncthreads();
 
-  // ---- compose_grad and the stats (k_train_step) ------------------------------
+  // ---- the gradient and the stats -------------------------------------------
   const double kNaN = __builtin_nan("");
   const bool flag = sScal[1] != 0.0;
   const int P = a.P;
   for (int q = tid; q < P; q += NTHR) {
-    double v;
-    if (q == 0) {
-      v = -0.5 * sG[B * (PM + 1)] * exp(th[0]);
-    } else if (q == 1) {
-      v = KIND == 0 ? sa : 0.0;
-    } else if (q < 2 + B) {
-      v = -0.5 * sG[(q - 2) * (PM + 1) + PM];
-    } else {
-      const int e = q - 2 - B, b = e % B, i = e / B;
-      const double sm = sG[b * (PM + 1) + i];
-      v = KIND == 0 ? -0.5 * (sm * exp(-th[q])) : -0.25 * 9 * sm * exp(-th[q]);
-    }
+    const double v = grad_entry(KIND, B, PM, th, sG, sa, q);  // KIND: an ace_kernel_kind
     out[q] = flag ? kNaN : v;
   }
   if (tid == 0) {
-    const double s0 = a.std_y[j] * sqrt(e2) / sqrt((double)n);
-    const double s1 = -0.5 * ((double)n * log(2.0 * M_PI) + sScal[0] + ya);
+    double s0, s1;
+    train_stats(a.std_y[j], (double)n, e2, sScal[0], ya, &s0, &s1);
     out[P] = flag ? kNaN : s0;
     out[P + 1] = flag ? kNaN : s1;
     out[P + 2] = flag ? kNaN : mu;
@@ -456,9 +401,9 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
 }
 
 // ---------------------------------------------------------------------------
-// One wave per model: norm clip (Q5), the optimizer (Q8), the mu overwrite,
-// the stats history, the convergence test and the non-finite stop, as
-// k_train_step.  A stopped model is left alone from then on.
+// One wave per model: norm clip (clip_on), the optimizer (opt_update), the mu
+// overwrite, the stats history, the convergence test and the non-finite stop,
+// as k_train_step.  A stopped model is left alone from then on.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_batch_step(BatchStepCfg c, int it,
                                                    const double *__restrict__ outp, int64_t ldo,
@@ -477,15 +422,15 @@ __global__ __launch_bounds__(64) void k_batch_step(BatchStepCfg c, int it,
     ss += g[q] * g[q];
     nf += isfinite(g[q]) ? 0.0 : 1.0;
   }
-  ss = wsum(ss);
-  nf = wsum(nf);
+  ss = wsum64(ss);
+  nf = wsum64(nf);
   const double prev = hist[2 * (it - 1) + 1];
   if (tid == 0) {
     hist[2 * it] = g[P];
     hist[2 * it + 1] = s1;
   }
   const double L2 = sqrt(ss);
-  const bool clip = c.clip && (L2 > c.clip_at) && isfinite(L2) && (L2 != 0);
+  const bool clip = clip_on(c.opt, L2);
   if (nf > 0.0) {  // the optimizer classes' stop(): theta stays as it was
     if (tid == 0) {
       if (it == 1) th[1] = mu;  // assigned before the optimizer runs
@@ -494,29 +439,16 @@ __global__ __launch_bounds__(64) void k_batch_step(BatchStepCfg c, int it,
     }
     return;
   }
-  const double b1 = c.beta1, b2 = c.beta2, eps = 1e-8;
-  const double c1 = 1 - pow(b1, (double)it), c2 = 1 - pow(b2, (double)it);
+  const double c1 = 1 - pow(c.opt.beta1, (double)it), c2 = 1 - pow(c.opt.beta2, (double)it);
   for (int q = tid; q < P; q += 64) {
     const double gj = clip ? g[q] / L2 : g[q];
     // theta[1] <- mu at iteration 1 comes before the step (R/kernel_SE_R6.R:45)
-    double t = (it == 1 && q == 1) ? mu : th[q];
-    if (c.optimizer == ACE_OPT_NESTEROV) {
-      m1[q] = c.momentum * m1[q] + c.lr * gj;
-      t = t + m1[q];
-    } else if (c.optimizer == ACE_OPT_NADAM) {
-      m1[q] = b1 * m1[q] + (1 - b1) * gj;
-      m2[q] = b2 * m2[q] + (1 - b2) * (gj * gj);
-      t = t + c.lr * ((b1 * m1[q] + (1 - b1) * gj) / c1) / (sqrt(m2[q] / c2) + eps);
-    } else {
-      m1[q] = (b1 * m1[q]) + (1 - b1) * gj;
-      m2[q] = b2 * m2[q] + (1 - b2) * (gj * gj);
-      t = t + c.lr * (m1[q] / c1) / (sqrt(m2[q] / c2) + eps);
-    }
+    const double t = opt_update(c.opt, c1, c2, gj, (it == 1 && q == 1) ? mu : th[q], m1, m2, q);
     th[q] = (q == 1) ? mu : t;  // private$mean_solution(y) with this iteration's inverse
   }
   if (tid == 0) {
     ctl[0] = it;
-    if (fabs(s1 - prev) < c.tol && it > 3) ctl[1] = 1;
+    if (fabs(s1 - prev) < c.opt.tol && it > 3) ctl[1] = 1;
   }
 }
 

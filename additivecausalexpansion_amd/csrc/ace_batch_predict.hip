@@ -20,6 +20,11 @@
 // and its mirror): an inverse installed from the host behaves like a resident
 // one.  The host composes map / ci / var and the 12 averages from a, kd, q and
 // gcov with the tails the single-model path uses (ace_common.h).
+//
+// The arithmetic is that of ace_formulas.h (kval in its cross and symmetric
+// forms, tab_weight for the kernel-indexed weights), and the wave and
+// workgroup sums are its wsum64 / wave_parts / block_sum; this file keeps the
+// LDS layout and the order of every sum.
 #include "../../include/ace_hip.h"
 #include "ace_batch.h"
 #include "ace_internal.h"
@@ -27,58 +32,6 @@
 namespace ace {
 
 namespace {
-
-#define SQRT3 1.7320508075688772
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double psgn(double x) { return (double)((0.0 < x) - (x < 0.0)); }
-
-// kval of ace_pairs.hip, restated.  CROSS: "lo" is the test point (the X1 / Z1
-// side of kernmat_*_cpp(X2, X, Z2, Z)); otherwise the smaller index of a
-// symmetric pair.
-template <int KIND, bool CROSS>
-__device__ __forceinline__ double pkval(int b, double r2, double lam, double zlo, double zhi,
-                                        double lzlo, double lzhi) {
-  if (KIND == 0) {
-    if (b == 0) return exp(lam - r2);
-    if (zlo == 0.0 || zhi == 0.0) return 0.0;  // Q7
-    return (psgn(zlo) * psgn(zhi)) * exp(((lam - r2) + lzlo) + lzhi);
-  } else {
-    const double t = sqrt(r2);
-    const double e = (1.0 + SQRT3 * t) * exp(lam - SQRT3 * t);
-    if (b == 0) return e;
-    if (zlo == 0.0) return 0.0;
-    if (CROSS && zhi == 0.0) return 0.0;
-    return (e * zlo) * zhi;
-  }
-}
-
-__device__ __forceinline__ double pwsum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// the NW per-wave partials at sh[q stride], added in a fixed order
-template <int NW>
-__device__ __forceinline__ double pwave_parts(const double *sh, int stride) {
-  double r = (sh[0] + sh[stride]) + (sh[2 * stride] + sh[3 * stride]);
-  if (NW == 8)
-    r += (sh[4 * stride] + sh[5 * stride]) + (sh[6 * stride] + sh[7 * stride]);
-  return r;
-}
-
-// sum over the workgroup in a fixed order; every thread gets it.  sh: NW doubles
-template <int NW>
-__device__ __forceinline__ double pbsum(double v, double *sh) {
-  v = pwsum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = pwave_parts<NW>(sh, 1);
-  __syncthreads();
-  return r;
-}
 
 // LDS map (doubles): scal[16] | wk[B PM] | lam[B] e^theta0 | alpha[nmax] |
 // u[2 nmax] (y - mu first, then the group sums of the cross rows) |
@@ -139,12 +92,12 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_predict(BatchPredVi
   const int b0 = a.marginal && B > 1 ? 1 : 0;
   const int b1 = a.marginal ? (B > 1 ? B : 1) : B;
 
-  // ---- theta tables (make_tab, Q1 kernel index) --------------------------------
+  // ---- theta tables (the kernel weights of make_tab; no gradient part) ----------
   for (int e = tid; e < nk + B + 1; e += NTHR) {
     double v = 0.0;
     if (e < nk) {
       const int b = e / PM, i = e - b * PM;
-      if (i < p) v = exp(-th[1 + b + B * (i + 1)]);
+      if (i < p) v = tab_weight(th, B, b, i, false);
     } else if (e < nk + B) {
       v = th[2 + (e - nk)];
     } else {
@@ -203,7 +156,9 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_predict(BatchPredVi
               lzc = LZ[(int64_t)c * ZS + b - 1];
             }
           }
-          kf += pkval<KIND, true>(b, r2, sLam[b], zt, zc, lzt, lzc);
+          // cross form: "lo" is the test point (the X1 / Z1 side of
+          // kernmat_*_cpp(X2, X, Z2, Z))
+          kf += kval<KIND, true>(b, r2, sLam[b], zt, zc, lzt, lzc);
         }
       }
       sK[pt * pitch + c] = kf;  // (the identity padding's columns: zero)
@@ -214,7 +169,7 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_predict(BatchPredVi
     for (int pt = wv; pt < nt; pt += NW) {
       double s = 0.0;
       for (int c = lane; c < n; c += 64) s = fma(sK[pt * pitch + c], sAl[c], s);
-      s = pwsum(s);
+      s = wsum64(s);
       if (lane == 0) {
         const int64_t r = i0 + pt;
         double kd = 0.0;
@@ -224,7 +179,7 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_predict(BatchPredVi
             z = Z2[r * ZS + b - 1];
             if (KIND == 0) lz = LZ2[r * ZS + b - 1];
           }
-          kd += pkval<KIND, false>(b, 0.0, sLam[b], z, z, lz, lz);
+          kd += kval<KIND, false>(b, 0.0, sLam[b], z, z, lz, lz);
         }
         oa[r] = s;
         okd[r] = kd;
@@ -277,13 +232,15 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_predict(BatchPredVi
     for (int u = 0; u < BPT; ++u)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
+        // over the 16 lanes of a row (written here, not as a shared template:
+        // this form keeps the kernel's machine code as it was)
         double v = qacc[u][q];
 #pragma unroll
         for (int m = 8; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
         if (lr == 0) sRed[wv * TP + u * BT + lk + 4 * q] = v;
       }
     __syncthreads();
-    if (tid < nt) oq[i0 + tid] = pwave_parts<NW>(sRed + tid, TP);
+    if (tid < nt) oq[i0 + tid] = wave_parts<NW>(sRed + tid, TP);
     __syncthreads();
   }
   if (!a.ate) return;
@@ -318,7 +275,7 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_predict(BatchPredVi
             lzc = LZ2[(int64_t)c * ZS + b - 1];
           }
         }
-        kf += pkval<KIND, false>(b, r2, sLam[b], zc, zr, lzc, lzr);
+        kf += kval<KIND, false>(b, r2, sLam[b], zc, zr, lzc, lzr);
       }
       const bool gc = zx[c] != 0.0;
       if (gr != gc) tu += kf;  // once: the host counts the pair's mirror
@@ -326,9 +283,9 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_predict(BatchPredVi
       else uu += (c == r) ? kf : 2.0 * kf;
     }
   }
-  tt = pbsum<NW>(tt, sRed);
-  tu = pbsum<NW>(tu, sRed);
-  uu = pbsum<NW>(uu, sRed);
+  tt = block_sum<NW>(tt, sRed);
+  tu = block_sum<NW>(tu, sRed);
+  uu = block_sum<NW>(uu, sRed);
 
   // ---- (c) u_g^T A^-1 u_h: one row per thread, columns in index order ---------
   double dtt = 0.0, dtu = 0.0, duu = 0.0;
@@ -343,9 +300,9 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_predict(BatchPredVi
     dtu = fma(sU[i], su, dtu);
     duu = fma(sU[nmax + i], su, duu);
   }
-  dtt = pbsum<NW>(dtt, sRed);
-  dtu = pbsum<NW>(dtu, sRed);
-  duu = pbsum<NW>(duu, sRed);
+  dtt = block_sum<NW>(dtt, sRed);
+  dtu = block_sum<NW>(dtu, sRed);
+  duu = block_sum<NW>(duu, sRed);
   if (tid == 0) {
     double *g = a.gcov + 3 * (int64_t)j;
     g[0] = tt - dtt;

@@ -219,9 +219,8 @@ inline std::vector<double> make_tab(const double *theta, const Shape &s, bool wi
   std::vector<double> t((size_t)(2 * B * PM + B), 0.0);
   for (int b = 0; b < B; ++b) {
     for (int i = 0; i < s.p; ++i) {
-      t[(size_t)(b * PM + i)] = std::exp(-theta[1 + b + B * (i + 1)]);  // Q1 kernel index
-      if (with_grad)
-        t[(size_t)(B * PM + b * PM + i)] = std::exp(-theta[2 + B + b + B * i]);  // gradient index
+      t[(size_t)(b * PM + i)] = tab_weight(theta, B, b, i, false);
+      if (with_grad) t[(size_t)(B * PM + b * PM + i)] = tab_weight(theta, B, b, i, true);
     }
     t[(size_t)(2 * B * PM + b)] = theta[2 + b];
   }
@@ -271,23 +270,11 @@ inline double host_logsum(const double *w, int64_t n) {
   return s;
 }
 
-// Final composition of the P-gradient from the device sums.
-//   gsum[b*(PM+1)+i] : sum T K_b d_i^2 (SE) / sum T K_b/(1+sqrt(3 r~2)) d_i^2 (Matern)
-//   gsum[b*(PM+1)+PM]: sum T K_b ; gsum[B*(PM+1)] : trace T
+// Final composition of the P-gradient from the device sums (grad_entry).
 inline void compose_grad(const Shape &s, const double *theta, const double *gsum, double sum_alpha,
                   double *grad) {
-  const int B = s.B, PM = s.PM, P = 2 + B * (s.p + 1);
-  for (int j = 0; j < P; ++j) grad[j] = 0.0;
-  grad[0] = -0.5 * gsum[B * (PM + 1)] * std::exp(theta[0]);  // sigma_gradient
-  for (int b = 0; b < B; ++b) grad[2 + b] = -0.5 * gsum[b * (PM + 1) + PM];
-  for (int i = 0; i < s.p; ++i)
-    for (int b = 0; b < B; ++b) {
-      const int j = 2 + B + b + B * i;
-      const double sum = gsum[b * (PM + 1) + i];
-      if (s.kind == ACE_KERNEL_SE) grad[j] = -0.5 * (sum * std::exp(-theta[j]));
-      else grad[j] = -0.25 * 9 * sum * std::exp(-theta[j]);
-    }
-  grad[1] = (s.kind == ACE_KERNEL_SE) ? sum_alpha : 0.0;
+  const int P = 2 + s.B * (s.p + 1);
+  for (int j = 0; j < P; ++j) grad[j] = grad_entry(s.kind, s.B, s.PM, theta, gsum, sum_alpha, j);
 }
 
 // Host tail of pred_cpp (src/pred_cpp.cpp:20-33): from a = tmp (y - mu),

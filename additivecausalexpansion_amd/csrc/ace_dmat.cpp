@@ -579,8 +579,7 @@ int ace_stats_dev(ace_ctx *ctx, int64_t n, const double *y, const ace_dmat *Kmat
   double sums[4];
   download(ctx, sums, dsums.d(), 4, "download");
   sync(ctx);
-  out[0] = std_y * std::sqrt(sums[0]) / std::sqrt((double)n);
-  out[1] = -0.5 * (n * std::log(2.0 * M_PI) + host_logsum(eigenval, n) + sums[1]);
+  train_stats(std_y, (double)n, sums[0], host_logsum(eigenval, n), sums[1], &out[0], &out[1]);
   if (inv->kind == ace_dmat::SWEPT && inv->nonpd) out[0] = out[1] = kNaN;
   return ACE_OK;
   ACE_CATCH
@@ -648,8 +647,7 @@ int ace_grad_dev(ace_ctx *ctx, int kind, int64_t n, int p, int B, const double *
   download(ctx, sums.data(), dsums.d(), 4, "download sums");
   sync(ctx);
   compose_grad(s, theta, gs.data(), sums[2], grad);
-  stats[0] = std_y * std::sqrt(sums[0]) / std::sqrt((double)n);
-  stats[1] = -0.5 * (n * std::log(2.0 * M_PI) + host_logsum(eigenval, n) + sums[1]);
+  train_stats(std_y, (double)n, sums[0], host_logsum(eigenval, n), sums[1], &stats[0], &stats[1]);
   if (swept && inv->nonpd) {
     const int P = 2 + B * (p + 1);
     for (int j = 0; j < P; ++j) grad[j] = kNaN;

@@ -1,11 +1,14 @@
 // ace_internal.h -- shared declarations between the HIP kernels
 // (ace_kernels.hip, ace_sweep.hip) and the host orchestration (ace_api.cpp).
 #pragma once
+#include <algorithm>
 #include <functional>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+
+#include "ace_formulas.h"
 
 namespace ace {
 
@@ -19,6 +22,12 @@ inline int env_int(const char *name, int dflt) {
 }
 // whether `name` is set at all (switches whose default depends on the size)
 inline bool env_set(const char *name) { return getenv(name) != nullptr; }
+// Host syncs of the device training loops (ace_model_train, ace_batch_train):
+// the stop words are read back every ACE_TRAIN_SYNC iterations (default 4).
+inline int train_sync_every() {
+  static const int v = std::max(1, env_int("ACE_TRAIN_SYNC", 4));
+  return v;
+}
 
 // Sweep (Gauss-Jordan SPD inversion) blocking; see DESIGN.md §3.
 #ifndef ACE_NB
@@ -53,9 +62,9 @@ struct Tile {
   int I, J;
 };
 
-// Per-theta tables, b-major: wk[b*PM+i] = exp(-theta[1+b+B*(i+1)]) (kernel
-// index, Q1), wg[b*PM+i] = exp(-theta[2+B+b+B*i]) (gradient index),
-// lam[b] = theta[2+b].  Total 2*B*PM + B doubles.
+// Per-theta tables, b-major: wk[b*PM+i] = tab_weight(theta, B, b, i, false)
+// (kernel index, Q1), wg[b*PM+i] = tab_weight(theta, B, b, i, true) (gradient
+// index), lam[b] = theta[2+b].  Total 2*B*PM + B doubles.
 struct TabView {
   const double *wk, *wg, *lam;
   // device exp(theta[0]) (the device-fused training loop's theta lives in
@@ -389,10 +398,7 @@ hipError_t launch_slice_norms(const double *X, int PM, int64_t np, int B, int NS
 hipError_t launch_make_tab(const double *theta, int B, int p, int PM, double *tab,
                            hipStream_t st);
 struct TrainCfg {
-  int optimizer;  // ace_optimizer
-  double lr, momentum, beta1, beta2;
-  int clip;
-  double clip_at, tol;
+  OptCfg opt;
   int P, B, p, PM, kind;
   int64_t n;
   double std_y;

@@ -26,38 +26,6 @@
 
 namespace ace {
 
-#define SQRT3 1.7320508075688772
-
-__device__ __forceinline__ double sgn(double x) {
-  return (double)((0.0 < x) - (x < 0.0));
-}
-
-// One slice value K_b for a pair, following the reference expressions:
-//  SE  (src/kernel_SE_cpp.cpp:96, 119 / 39, 53): slice 0 exp(lam - r2);
-//      b>=1: sign(z_lo) sign(z_hi) exp(((lam - r2) + log|z_lo|) + log|z_hi|),
-//      0 if either z is exactly 0 (Q7).
-//  Matern32 (src/kernel_Matern_cpp.cpp:217-227 / 79-86): t = sqrt(r2),
-//      e = (1 + sqrt3 t) exp(lam - sqrt3 t); b>=1: (e z_lo) z_hi, 0 if
-//      z_lo == 0 (and, in the cross kernel, if z_hi == 0).
-// "lo" is the first operand of the reference's product: the smaller index
-// of a symmetric pair (upper-triangle loop), the X1/Z1 side of a cross pair.
-template <int KIND, bool CROSS>
-__device__ __forceinline__ double kval(int b, double r2, double lam, double zlo,
-                                       double zhi, double lzlo, double lzhi) {
-  if (KIND == 0) {
-    if (b == 0) return exp(lam - r2);
-    if (zlo == 0.0 || zhi == 0.0) return 0.0;
-    return (sgn(zlo) * sgn(zhi)) * exp(((lam - r2) + lzlo) + lzhi);
-  } else {
-    const double t = sqrt(r2);
-    const double e = (1.0 + SQRT3 * t) * exp(lam - SQRT3 * t);
-    if (b == 0) return e;
-    if (zlo == 0.0) return 0.0;
-    if (CROSS && zhi == 0.0) return 0.0;
-    return (e * zlo) * zhi;
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Assembly.  MODE 1: symmetric full output (+cube), MODE 2: cross (+cube).
 // npad, sig, tiles and G are not read, and the column test below repeats the

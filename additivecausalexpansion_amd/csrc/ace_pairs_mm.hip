@@ -32,18 +32,15 @@
 
 namespace ace {
 
-// Register caps (__launch_bounds__ second argument = waves per SIMD):
-// gradient 2 (LDS 2 x 33 KB at p = 64 allows 2 workgroups per CU anyway),
-// assembly 3 up to PM = 32 and 2 above (3 would spill at PM = 64).
-typedef double d4 __attribute__((ext_vector_type(4)));
-
+// Register caps of the kernels below (__launch_bounds__ second argument =
+// waves per SIMD): gradient 2 (LDS 2 x 33 KB at p = 64 allows 2 workgroups per
+// CU anyway), assembly 3 up to PM = 32 and 2 above (3 would spill at PM = 64).
+//
 // Pairs per scheduling group in the elementwise loops: a sched_barrier after
 // every PAIR_GROUP pairs bounds live ranges.
 constexpr int PAIR_GROUP = 2;
 #define MM_PAIR_FENCE(cb, v) \
   if ((4 * (cb) + (v) + 1) % PAIR_GROUP == 0) __builtin_amdgcn_sched_barrier(0)
-
-#define SQRT3 1.7320508075688772
 
 // Lane-dependent select of two registers as two v_cndmask_b32 (no array
 // indexing the compiler could lower to a scratch gather).
@@ -194,7 +191,7 @@ __device__ __forceinline__ double sqrt_gs(double x) {
   return fma(s, fma(-h, s, 0.5), s);
 }
 
-// One slice value, the reference expressions (same as ace_pairs.hip kval):
+// One slice value, the reference expressions (same as kval, ace_formulas.h):
 //  SE  (src/kernel_SE_cpp.cpp:96, 119), Matern32 (src/kernel_Matern_cpp.cpp:217-227).
 // Without a slice test: the loops run slice 0 with z = 1 and log|z| = 0 (an
 // LDS row of ones / zeros), which gives the basis slice's value bit for bit

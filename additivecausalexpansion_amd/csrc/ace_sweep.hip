@@ -31,8 +31,6 @@
 
 namespace ace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 // The lookahead chain kernels (k_pivot, k_panel_split: one to sixteen
 // workgroups of latency-bound work) share CUs with the MFMA-heavy update tiles of the main
 // stream.  Raising their waves' issue priority lets them win the SIMD

@@ -31,8 +31,6 @@
 
 namespace ace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 constexpr int SR = 128, SC = 64, SBK = 16;
 constexpr int SLS = SR + 16;  // LDS pitch of the S stage
 constexpr int SLV = SC + 16;  // LDS pitch of the V stage

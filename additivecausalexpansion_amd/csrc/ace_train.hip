@@ -4,11 +4,13 @@
 //
 //   k_make_tab   : the theta tables of make_tab (ace_common.h) from the
 //                  device theta, plus exp(theta[0]) for the diagonal;
-//   k_train_step : para_update's compose_grad + stats (ace_api.cpp), the
-//                  norm clip (src/utilities_cpp.cpp:121-129, Q5), the
-//                  optimizer (src/optimizer_cpp.cpp:8-63, Q8), the mu
-//                  overwrite (R/kernel_SE_R6.R:45,58) and the convergence test
-//                  (R/main_ace.R:221-226), one workgroup.
+//   k_train_step : para_update's gradient and stats, the norm clip, the
+//                  optimizer, the mu overwrite (R/kernel_SE_R6.R:45,58) and
+//                  the convergence test (R/main_ace.R:221-226), one workgroup.
+//
+// The arithmetic is that of ace_formulas.h (tab_weight, grad_entry,
+// train_stats, clip_on, opt_update), shared with the host and the batched
+// engine; this file keeps the table layout and the order of the sums.
 #include "../../include/ace_hip.h"
 #include "ace_internal.h"
 
@@ -23,7 +25,7 @@ __global__ void k_make_tab(const double *__restrict__ th, int B, int p, int PM,
     const int q = e - gi * nk;
     const int b = q / PM, i = q - b * PM;
     double v = 0.0;
-    if (i < p) v = exp(-th[gi ? 2 + B + b + B * i : 1 + b + B * (i + 1)]);
+    if (i < p) v = tab_weight(th, B, b, i, gi);
     tab[e] = v;
   } else if (e < 2 * nk + B) {
     tab[e] = th[2 + (e - 2 * nk)];
@@ -42,13 +44,8 @@ hipError_t launch_make_tab(const double *theta, int B, int p, int PM, double *ta
 
 namespace {
 
-__device__ __forceinline__ double wsum64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// block sum of 1024 threads, every thread gets the result
+// block sum of 1024 threads, every thread gets the result; the 16 partials
+// are added in sequence (that order is part of the training loop's results)
 __device__ __forceinline__ double bsum(double v, double *sh) {
   v = wsum64(v);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -83,26 +80,14 @@ __global__ __launch_bounds__(1024) void k_train_step(TrainCfg c, int it,
   const double kNaN = __builtin_nan("");
   const double mu = scal[3];
   const bool bad = *flag != 0;  // not positive definite: non-finite outputs
-  const bool se = c.kind == ACE_KERNEL_SE;
-  // compose_grad (ace_common.h); theta[1] <- mu_solution at iter 1 happens
-  // before it in para_update but compose_grad does not read theta[1]
+  // theta[1] <- mu_solution at iter 1 happens before the gradient in
+  // para_update, but grad_entry does not read theta[1]
   for (int j = tid; j < P; j += 1024) {
-    double v;
-    if (j == 0) {
-      v = -0.5 * gsum[B * (PM + 1)] * exp(th[0]);
-    } else if (j == 1) {
-      v = se ? sums[2] : 0.0;
-    } else if (j < 2 + B) {
-      v = -0.5 * gsum[(j - 2) * (PM + 1) + PM];
-    } else {
-      const int q = j - 2 - B, b = q % B, i = q / B;
-      const double sm = gsum[b * (PM + 1) + i];
-      v = se ? -0.5 * (sm * exp(-th[j])) : -0.25 * 9 * sm * exp(-th[j]);
-    }
+    const double v = grad_entry(c.kind, B, PM, th, gsum, sums[2], j);
     g[j] = bad ? kNaN : v;
   }
-  double s0 = c.std_y * sqrt(sums[0]) / sqrt((double)c.n);
-  double s1 = -0.5 * ((double)c.n * log(2.0 * M_PI) + sums[3] + sums[1]);
+  double s0, s1;
+  train_stats(c.std_y, (double)c.n, sums[0], sums[3], sums[1], &s0, &s1);
   if (bad) s0 = s1 = kNaN;
   if (tid == 0) {
     hist[2 * it] = s0;
@@ -119,7 +104,7 @@ __global__ __launch_bounds__(1024) void k_train_step(TrainCfg c, int it,
   ss = bsum(ss, sh);
   nf = bsum(nf, sh);
   const double L2 = sqrt(ss);
-  const bool clip = c.clip && (L2 > c.clip_at) && isfinite(L2) && (L2 != 0);
+  const bool clip = clip_on(c.opt, L2);
   if (nf > 0.0) {  // the optimizer classes' stop(): theta stays as it was
     if (tid == 0) {
       ctl[0] = it;
@@ -127,29 +112,17 @@ __global__ __launch_bounds__(1024) void k_train_step(TrainCfg c, int it,
     }
     return;
   }
-  const double b1 = c.beta1, b2 = c.beta2, eps = 1e-8;
-  const double c1 = 1 - pow(b1, (double)it), c2 = 1 - pow(b2, (double)it);
+  const double c1 = 1 - pow(c.opt.beta1, (double)it), c2 = 1 - pow(c.opt.beta2, (double)it);
   for (int j = tid; j < P; j += 1024) {
     const double gj = clip ? g[j] / L2 : g[j];
-    if (c.optimizer == ACE_OPT_NESTEROV) {
-      m1[j] = c.momentum * m1[j] + c.lr * gj;
-      th[j] = th[j] + m1[j];
-    } else if (c.optimizer == ACE_OPT_NADAM) {
-      m1[j] = b1 * m1[j] + (1 - b1) * gj;
-      m2[j] = b2 * m2[j] + (1 - b2) * (gj * gj);
-      th[j] = th[j] + c.lr * ((b1 * m1[j] + (1 - b1) * gj) / c1) / (sqrt(m2[j] / c2) + eps);
-    } else {
-      m1[j] = (b1 * m1[j]) + (1 - b1) * gj;
-      m2[j] = b2 * m2[j] + (1 - b2) * (gj * gj);
-      th[j] = th[j] + c.lr * (m1[j] / c1) / (sqrt(m2[j] / c2) + eps);
-    }
+    th[j] = opt_update(c.opt, c1, c2, gj, th[j], m1, m2, j);
   }
   __syncthreads();
   if (tid == 0) {
     th[1] = mu;  // private$mean_solution(y) with this iteration's inverse
     const double change = fabs(s1 - hist[2 * (it - 1) + 1]);
     ctl[0] = it;
-    if (change < c.tol && it > 3) ctl[1] = 1;
+    if (change < c.opt.tol && it > 3) ctl[1] = 1;
   }
 }
 

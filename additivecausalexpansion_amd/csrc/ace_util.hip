@@ -5,17 +5,9 @@
 
 namespace ace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // Block-wide sum for 256 threads (deterministic order).
 __device__ __forceinline__ double block_sum256(double v, double *sh) {
-  v = wsum(v);
+  v = wsum64(v);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 0) sh[wv] = v;
   __syncthreads();
@@ -28,7 +20,7 @@ __device__ __forceinline__ double block_sum256(double v, double *sh) {
 // per-evaluation reductions (colsum of the tile partials, final sums with
 // n logs) run 4x shorter loops per thread than at 256.
 __device__ __forceinline__ double block_sum1024(double v, double *sh) {
-  v = wsum(v);
+  v = wsum64(v);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 0) sh[wv] = v;
   __syncthreads();

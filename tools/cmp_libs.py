@@ -6,7 +6,13 @@ switches.  usage: python tools/cmp_libs.py libA.so libB.so [n] [kernel] [what];
 CMP_ENV_B="K=V ..." sets environment switches for the second run only.  what =
 para_update (default), or cross: predict, coef_cross and predict_marginal_groups
 of one fitted model with p = 20, B = 10 at nx = 257 test points (the two-sided
-tile kernels; n = 700 is the shape the tests use)."""
+tile kernels; n = 700 is the shape the tests use), or formulas: every output
+of every entry point that evaluates a formula of csrc/ace_formulas.h (fused
+para_update / train_stats, the device training loop under each optimizer with
+the clip firing and off, host-buffer and handle grad / stats, the batched
+para_update / train / predict / predict_marginal with ATE), both kernels,
+compared bit for bit per output at fixed small shapes (n and kernel are not
+read)."""
 import os
 import subprocess
 import sys
@@ -49,7 +55,127 @@ g = m.predict_marginal_groups(th, X2, dZ2, 1.7, 0.8, 17, (np.arange(nx) % 17).as
 outs = [pr["map"], pr["var"], m.coef_cross(th, X2), g["gcov"], g["gsum"], g["map"], g["var"]]
 np.save({out!r}, np.concatenate([np.ravel(o) for o in outs]))
 """
-SNIPS = {"para_update": SNIP, "cross": SNIP_CROSS}
+# Shapes: the smallest at which every branch of the shared functions is taken
+# (exact zeros in Z on either side of a pair for the Q7 rules, n_j and nx_j on
+# either side of a 16-row block / a 32-point pass, the PM = 4 and PM = 64
+# buckets, B = 1 and B > 1, each optimizer, the clip firing and off).
+SNIP_FORMULAS = """
+import sys, numpy as np
+sys.path.insert(0, {root!r})
+import additivecausalexpansion_amd as A
+from additivecausalexpansion_amd import native as N
+from additivecausalexpansion_amd.model import BatchModel
+from additivecausalexpansion_amd.synthetic import make_problem
+out = {{}}
+# Every device object lives inside run(): a handle left at script level is
+# released at interpreter exit after the context it belongs to (the script's
+# globals form a cycle with its functions, and the collector finalises the
+# older context first), and ace_dmat_free then writes into the freed context.
+def run():
+    def put(name, *arrs):
+        for i, a in enumerate(arrs):
+            out[name + "/" + str(i)] = np.ravel(np.asarray(a, dtype=np.float64))
+    def problem(n, p, B, seed):
+        y, X, Z, th, sy = make_problem(n, p, B, seed=seed)
+        Z = np.array(Z, order="F")
+        if B > 1:
+            Z[3::7, 0] = 0.0   # exact zeros: the Q7 rules
+            Z[5::11, :] = 0.0
+        return y, X, Z, th + 0.05 * np.sin(np.arange(th.size)), sy
+    OPTS = [(o, c) for o in ("NAG", "Adam", "Nadam") for c in (True, False)]
+    for kernel in ("SE", "Matern32"):
+        # fused model: para_update, train_stats, the inverse
+        y, X, Z, th, sy = problem(97, 2, 5, 1)
+        m = A.DeviceModel(kernel, 97, 2, 5)
+        m.set_data(y, X, Z, sy)
+        t = th.copy()
+        for it in (1, 2):
+            g, st, mu = m.para_update(it, t)
+            put(kernel + "/fused/it" + str(it), g, st, [mu], t)
+            t = t + 0.01 * g / max(1.0, float(np.abs(g).max()))
+        put(kernel + "/fused/inverse", m.inverse())
+        put(kernel + "/fused/train_stats", m.train_stats(t))
+        m.close()
+        # the device training loop
+        y, X, Z, th, sy = problem(60, 3, 4, 2)
+        for opt, clip in OPTS:
+            m = A.DeviceModel(kernel, 60, 3, 4)
+            m.set_data(y, X, Z, sy)
+            t = th.copy()
+            stats, iters, conv = m.train(t, optimizer=opt, learning_rate=0.003, momentum=0.9,
+                                         norm_clip=clip, clip_at=0.5, maxiter=6)
+            put(kernel + "/train/" + opt + "/clip" + str(int(clip)), t, stats, [iters, conv], m.inverse())
+            m.close()
+        # host buffers and handles: grad, stats
+        y, X, Z, th, sy = problem(97, 2, 5, 3)
+        sym = N.kernmat_SE_symmetric_cpp if kernel == "SE" else N.kernmat_Matern32_symmetric_cpp
+        grad = N.grad_SE_cpp if kernel == "SE" else N.grad_Matern_cpp
+        for dev in (False, True):
+            K = sym(X, Z, th, device=dev)
+            inv = N.invkernel_cpp(K["full"], th[0])
+            mu = N.mu_solution_cpp(y, inv["inv"])
+            t = th.copy()
+            t[1] = mu
+            st = np.zeros(2)
+            g = grad(y, X, Z, K["full"], K["elements"], inv["inv"], inv["eigenval"], t, st, 5, sy)
+            st2 = N.stats_cpp(y, K["full"], inv["inv"], inv["eigenval"], mu, sy)
+            put(kernel + "/abi/dev" + str(int(dev)), g, st, st2, [mu], inv["eigenval"])
+        # the batched engine
+        ns, nxs = (15, 16, 33), (1, 32, 33)
+        for p, B in ((3, 1), (3, 4), (33, 1), (33, 4)):
+            tag = kernel + "/batch/p" + str(p) + "B" + str(B)
+            probs = [problem(n, p, B, 10 + j) for j, n in enumerate(ns)]
+            th0 = np.asfortranarray(np.column_stack([q[3] for q in probs]))
+            def model():
+                bm = BatchModel(kernel, 3, 33, p, B)
+                for j, q in enumerate(probs):
+                    bm.set_data(j, q[0], q[1], q[2], q[4])
+                return bm
+            bm = model()
+            T = th0.copy(order="F")
+            for it in (1, 2):
+                g, st, mu = bm.para_update(it, T)
+                put(tag + "/it" + str(it), g, st, mu, T)
+                T = np.asfortranarray(T + 0.01 * g / max(1.0, float(np.abs(g).max())))
+            put(tag + "/inverse", *[bm.inverse(j) for j in range(3)])
+            tests = [problem(40, p, B, 20 + j) for j in range(3)]
+            X2s = [np.asfortranarray(q[1][:nx]) for q, nx in zip(tests, nxs)]
+            Z2s = [np.asfortranarray(q[2][:nx]) for q, nx in zip(tests, nxs)]
+            for q in Z2s:
+                if B > 1:
+                    q[1::5, -1] = 0.0
+            pr = bm.predict(T, X2s, Z2s, [0.3, -0.2, 0.1], [1.7, 0.9, 1.1])
+            put(tag + "/predict", *[r[k] for r in pr for k in ("map", "ci", "var")])
+            dZ2s = [np.asfortranarray(q * 0.7 + 0.1) for q in Z2s]
+            for q in dZ2s:
+                if B > 1:
+                    q[1::5, -1] = 0.0
+            zxs = [(np.arange(nx) % 3 == 0).astype(np.float64) for nx in nxs]
+            for ate in (False, True):
+                pm = bm.predict_marginal(T, X2s, dZ2s, zxs, [1.7, 0.9, 1.1], [0.8, 1.2, 1.0],
+                                         calculate_ate=ate)
+                put(tag + "/marginal/ate" + str(int(ate)), *[r[k] for r in pm for k in ("map", "ci", "var")])
+                if ate:
+                    put(tag + "/marginal/avg", *[r[g][k] for r in pm for g in ("ate", "att", "atu")
+                                                 for k in ("map", "ci", "var")])
+            bm.close()
+            for opt, clip in OPTS:
+                bm = model()
+                T = th0.copy(order="F")
+                stats, iters, conv, status = bm.train(T, optimizer=opt, learning_rate=0.003, momentum=0.9,
+                                                      norm_clip=clip, clip_at=0.5, maxiter=6)
+                put(tag + "/train/" + opt + "/clip" + str(int(clip)), T, stats, iters, conv, status,
+                    *[bm.inverse(j) for j in range(3)])
+                bm.close()
+run()
+np.savez({out!r}, **out)
+"""
+SNIPS = {"para_update": SNIP, "cross": SNIP_CROSS, "formulas": SNIP_FORMULAS}
+
+
+def bits_equal(a, b):
+    """Equal bit for bit (a NaN equals only the same NaN)."""
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
 def main():
@@ -60,13 +186,26 @@ def main():
     res = []
     with tempfile.TemporaryDirectory() as d:
         for i, lib in enumerate((a, b)):
-            out = os.path.join(d, f"o{i}.npy")
+            out = os.path.join(d, f"o{i}." + ("npz" if what == "formulas" else "npy"))
             env = dict(os.environ, ACE_LIB_PATH=os.path.abspath(lib))
             if i == 1 and os.environ.get("CMP_ENV_B"):  # "K=V ..." for the second run only
                 env.update(kv.split("=", 1) for kv in os.environ["CMP_ENV_B"].split())
             subprocess.run([sys.executable, "-c", SNIPS[what].format(root=ROOT, n=n, kernel=kernel, out=out)],
-                           env=env, check=True, timeout=120)
-            res.append(np.load(out))
+                           env=env, check=True, timeout=300)
+            res.append(dict(np.load(out)) if what == "formulas" else np.load(out))
+    if what == "formulas":
+        keys = sorted(set(res[0]) | set(res[1]))
+        diff = [k for k in keys if k not in res[0] or k not in res[1]
+                or not bits_equal(res[0][k], res[1][k])]
+        for k in keys:
+            v = res[1].get(k)
+            print(f"{k}: {'DIFFERS' if k in diff else 'bit-identical'} "
+                  f"({0 if v is None else v.size} values, "
+                  f"{0 if v is None else int(np.sum(~np.isfinite(v)))} non-finite)")
+        nval = sum(v.size for v in res[1].values())
+        print(f"formulas: {len(keys) - len(diff)} of {len(keys)} outputs bit-identical "
+              f"({nval} values); differing: {diff if diff else 'none'}")
+        sys.exit(0 if not diff else 1)
     same = np.array_equal(res[0], res[1])
     rel = float(np.max(np.abs(res[0] - res[1]) / np.maximum(np.abs(res[0]), 1e-300)))
     print(f"{what} n={n} {kernel}: bit-identical={same} max rel diff={rel:.3e} finite={bool(np.all(np.isfinite(res[1])))}")

@@ -37,4 +37,5 @@ def table(src, filt=""):
 if __name__ == "__main__":
     for x in table(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else ""):
         print(f"{x['name']:55s} vgpr {x.get('VGPRs', 0):4d} scratch {x.get('ScratchSize', 0):4d} "
-              f"spill {x.get('VGPRs Spill', 0):3d} occ {x.get('Occupancy', 0)}")
+              f"spill {x.get('VGPRs Spill', 0):3d} lds {x.get('LDS Size', 0):6d} "
+              f"occ {x.get('Occupancy', 0)}")
