@@ -516,12 +516,13 @@ void assemble_and_sweep(ace_ctx *ctx, SweepWork &w, const Shape &s, const PairSi
                         const SweepTiming *tmg, hipEvent_t *ev_asm) {
   hipStream_t st = ctx->stream;
   const int steps = (int)(w.npad / NB);
+  const SweepEvents E{steps, w.Z};
   SweepSync sy = w.sync(ctx);
   // ACE_ASM_PERSIST=R: the second part as a persistent work queue that
   // leaves R CUs of every shader engine to the first group's head path
   // (DESIGN §5); the queue is reset before anything can join it
   const int R = asm_persist_reserve();
-  const bool persist = R > 0 && sy.side && sy.nev >= 5 * steps + 6;
+  const bool persist = R > 0;
   // (the flag and the persistent assembly's queue are zeroed by the same launch)
   ck(ctx, launch_aug_init(w.A.d(), w.naug, w.npad, n, y, st, 1, 0, w.flag.i(), 1,
                           persist ? w.aq.i() : nullptr, persist ? 2 + 64 : 0),
@@ -530,19 +531,17 @@ void assemble_and_sweep(ace_ctx *ctx, SweepWork &w, const Shape &s, const PairSi
   ck(ctx, launch_assembly_mm(s.kind, s.PM, ps, w.npad, s.B, s.ZS, tv, sig, w.A.d(), w.naug,
                              nullptr, st, nullptr, 0, 1, 1),
      "assembly (first panel)");
-  if (sy.side && sy.nev >= 2 * steps + 1) {  // run_sweep's "inputs ready" event
-    ck(ctx, hipEventRecord(sy.ev[2 * steps], st), "event");
-    sy.ready_recorded = true;
-  }
+  ck(ctx, hipEventRecord(sy.ev[E.ready()], st), "event");  // the sweep's inputs
+  sy.ready_recorded = true;
   AsmFill fill;
-  if (persist && sy.ready_recorded) {
+  if (persist) {
     ck(ctx, launch_assembly_persist(s.kind, s.PM, ps, w.npad, s.B, s.ZS, tv, sig, w.A.d(), w.naug,
                                     st, w.aq.i(), R),
        "assembly (persistent)");
     const int tail = asm_tail_mode();
     if (tail == 0) {  // group 0's tail path after the whole assembly
-      sy.tail_after = sy.ev[5 * steps + 5];
-      ck(ctx, hipEventRecord(sy.tail_after, st), "event");
+      ck(ctx, hipEventRecord(sy.ev[E.tail_after()], st), "event");
+      sy.tail_after_recorded = true;
     }
     sy.tail_split = tail == 2;  // ... after group 0's head path
     const int per = asm_fill_on() ? assembly_persist_per_cu(s.kind, s.PM, s.B) : 0;

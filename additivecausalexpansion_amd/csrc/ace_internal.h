@@ -2,13 +2,12 @@
 // (ace_kernels.hip, ace_sweep.hip) and the host orchestration (ace_api.cpp).
 #pragma once
 #include <algorithm>
-#include <functional>
-#include <vector>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "ace_formulas.h"
+#include "ace_sweep_plan.h"
 
 namespace ace {
 
@@ -29,14 +28,6 @@ inline int train_sync_every() {
   return v;
 }
 
-// Sweep (Gauss-Jordan SPD inversion) blocking; see DESIGN.md §3.
-#ifndef ACE_NB
-#define ACE_NB 256
-#endif
-constexpr int NB = ACE_NB;  // outer pivot block = panel width
-constexpr int SUB = 64;    // inner pivot block, eliminated inside LDS
-constexpr int UT = 128;    // update tile (MFMA f64 16x16x4, 4 waves x 64x64)
-constexpr int AUG = 128;   // augmented right-hand-side rows (y, 1) appended to A
 constexpr int AT = 64;     // assembly / gradient pair tile
 constexpr int PMAX = 64;   // largest supported covariate count p
 constexpr int BMAX = 32;   // largest supported component count B
@@ -54,13 +45,6 @@ int pm_bucket(int p);  // smallest compiled bucket >= p, or -1
 __host__ __device__ __forceinline__ int64_t lcol(int64_t c, int G) {
   return G == 1 ? c : (c / NB / G) * NB + c % NB;
 }
-__host__ __device__ __forceinline__ bool owns_col(int64_t c, int G, int r) {
-  return G == 1 || (c / NB) % G == r;
-}
-// A pair / update tile (row tile I, column tile J) of a per-rank tile list.
-struct Tile {
-  int I, J;
-};
 
 // Per-theta tables, b-major: wk[b*PM+i] = tab_weight(theta, B, b, i, false)
 // (kernel index, Q1), wg[b*PM+i] = tab_weight(theta, B, b, i, true) (gradient
@@ -213,19 +197,6 @@ struct SweepBufs {
   int *bq = nullptr;
   int breserve = 0;
 };
-// SweepBufs::bq for a sweep of `steps` steps in groups of Z: per group a bulk
-// work queue of BQ_INTS ints (k_update_multi_r, zeroed per sweep), from fctr
-// on two counters per step (k_panel_split4's grid barrier and exits), from
-// qctr on one per step (k_update_q4's D_0 pieces).  The counters are zero
-// between launches: each launch's last workgroup resets them.
-constexpr int BQ_INTS = 2 + 64;
-struct BqLayout {
-  int64_t fctr, qctr, ints;
-};
-inline BqLayout bq_layout(int steps, int Z) {
-  const int64_t q = (int64_t)((steps + Z - 1) / Z) * BQ_INTS;
-  return BqLayout{q, q + 2 * steps, q + 3 * steps};
-}
 // CUs per shader engine a small-n bulk launch leaves to the panel chains:
 // ACE_BULK_RESERVE (0 .. 2) overrides; default 1 up to n = ACE_BULK_RESERVE_N,
 // none above (there the bulk launches are the critical path)
@@ -236,45 +207,27 @@ bool q_first(int64_t naug);
 // Several sweep steps per bulk update launch (run_sweep_heads, default);
 // ACE_PAIR=0 selects the one-step reference schedule.
 bool pair_steps();
-// Head / tail lists of the group schedule's lookahead (run_sweep_heads):
-// 2Z lists per group at off[G 2Z + m] (see ace_sweep.hip).
-std::vector<Tile> group_head_tiles(int64_t naug, int steps, int Z, std::vector<int64_t> &off);
 // Steps per bulk launch: ACE_GROUP = 2 .. 4 (default 4); sweep_group_n: for a
 // model of naug rows (3 at small n unless ACE_GROUP is set)
 int sweep_group();
 int sweep_group_n(int64_t naug);
-double update_gemm_tiles_group(int64_t naug, int64_t ka0, int npan, int kx0, int kx1);
-// The lower 128-tiles with I or J in block k+1, for k = 0 .. steps-2,
-// concatenated (each step's list dealt to the XCDs like the bulk order);
-// off[k] .. off[k+1] is step k's range.
-std::vector<Tile> cross_update_tiles(int64_t naug, int steps, std::vector<int64_t> &off);
-// k_update tile order: the tiles of `tl` grouped into S x S super-blocks of
-// 128-tiles that are dealt whole to the 8 XCDs; list index b runs on XCD
-// b % 8 (dispatch is round-robin).  Entries with I < 0 are padding.
-std::vector<Tile> xcd_update_order(const std::vector<Tile> &tl, int S,
-                                   const std::function<double(const Tile &)> &cost = nullptr);
-// per group of Z steps, the bulk order with each XCD's cheap tiles last:
-// ngroups lists of *len entries (sharded: rank r's own tiles of G)
-std::vector<Tile> pair_bulk_orders(int64_t naug, int steps, int64_t *len, int G = 1, int r = 0,
-                                   int Z = 2);
-// own lower tiles of size T over [0, ntile*T) in row-major order (ace_shard.cpp)
-std::vector<Tile> own_tiles(int64_t ntile, int T, int G, int r);
-// super-block size S of that order (0: row-major grid); ACE_UPD_ORDER=S
-// overrides (diagnostic A/B switch)
+// super-block size S of the update tile orders (xcd_update_order; 0: row-major
+// grid); ACE_UPD_ORDER=S overrides (diagnostic A/B switch)
 int update_order_block();
 // Lookahead streams and events of one sweep.  side: the panel chains (one-step
 // schedule) / the head path; side2: the tail path; either may alias the main
-// stream (ACE_STREAMS).  ev: 6 steps + 10 events (SweepWork::ensure).
+// stream (ACE_STREAMS).  ev: the events SweepEvents{steps, Z} names (SweepWork::ensure).
 struct SweepSync {
   hipStream_t side;
   hipStream_t side2 = nullptr;
   hipEvent_t *ev;
   int nev;
-  bool ready_recorded = false;  // caller already recorded ev[2 * steps] ("inputs ready")
-  // recorded on the main stream after the whole assembly: the first group's
-  // tail path waits for it when the assembly's second part leaves CUs to the
-  // head path (ACE_ASM_PERSIST); null: it waits for ev[2 * steps]
-  hipEvent_t tail_after = nullptr;
+  bool ready_recorded = false;  // caller already recorded SweepEvents::ready()
+  // caller recorded SweepEvents::tail_after() on the main stream after the
+  // whole assembly: the first group's tail path waits for it when the
+  // assembly's second part leaves CUs to the head path (ACE_ASM_PERSIST);
+  // false: it waits for ready()
+  bool tail_after_recorded = false;
   // called on side2 after group 0's tail path, before its completion event
   // (ACE_ASM_FILL: the persistent assembly's filler launch)
   hipError_t (*fill)(void *, hipStream_t) = nullptr;
@@ -293,11 +246,6 @@ struct SweepTiming {
 // (A^-1 R)^T and the corner -R^T A^-1 R.
 hipError_t run_sweep(const SweepBufs &b, hipStream_t st, const SweepSync *sync,
                      const SweepTiming *timing);
-double update_gemm_tiles(int64_t naug, int64_t k0, int kx, bool look);
-// every GEMM flop of one sweep, whatever the schedule: each step's update of
-// every lower tile outside its block (bulk + lookahead crosses) and its panel
-// GEMM W_i = Pn_i W_kk
-double sweep_flops(int64_t naug, int64_t npad);
 
 // ---- sharded sweep (one rank's view; ace_shard.cpp drives the steps) --------
 // Step k on rank r:  pack -> [exchange: broadcast `low` from rank k%G,

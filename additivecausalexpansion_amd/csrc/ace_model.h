@@ -61,10 +61,10 @@ struct SweepWork {
         alloc(ctx, Ps[j], (size_t)(naug * NB) * sizeof(double), "alloc panel");
         alloc(ctx, Ws[j], (size_t)(naug * NB) * sizeof(double), "alloc panel");
       }
-      const std::vector<Tile> o = pair_bulk_orders(naug, steps, &glen, 1, 0, Z);
+      const std::vector<Tile> o = pair_bulk_orders(naug, steps, update_order_block(), &glen, 1, 0, Z);
       alloc(ctx, gorder, o.size() * sizeof(Tile), "alloc bulk orders");
       upload_bytes(ctx, gorder.p, o.data(), o.size() * sizeof(Tile), "upload bulk orders");
-      const std::vector<Tile> h = group_head_tiles(naug, steps, Z, hoff);
+      const std::vector<Tile> h = group_head_tiles(naug, steps, Z, update_order_block(), hoff);
       alloc(ctx, htiles, std::max<size_t>(h.size(), 1) * sizeof(Tile), "alloc head tiles");
       if (!h.empty())
         upload_bytes(ctx, htiles.p, h.data(), h.size() * sizeof(Tile), "upload head tiles");
@@ -85,11 +85,11 @@ struct SweepWork {
       bq_npad = npad;
       bq_Z = Z;
     }
-    const std::vector<Tile> t = cross_update_tiles(naug, steps, xoff);
+    const std::vector<Tile> t = cross_update_tiles(naug, steps, update_order_block(), xoff);
     alloc(ctx, xtiles, std::max<size_t>(t.size(), 1) * sizeof(Tile), "alloc cross tiles");
     if (!t.empty())
       upload_bytes(ctx, xtiles.p, t.data(), t.size() * sizeof(Tile), "upload cross tiles");
-    const size_t need = (size_t)(6 * steps + 10);
+    const size_t need = (size_t)SweepEvents{steps, Z}.count();
     while (ev.size() < need) {
       hipEvent_t e;
       ck(ctx, hipEventCreateWithFlags(&e, ACE_SYNC_EVENT_FLAGS), "event");

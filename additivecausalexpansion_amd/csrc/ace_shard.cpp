@@ -261,53 +261,13 @@ ShardSweep sweep_view(const ShardModel &m, RankState &R, int which) {
   return b;
 }
 
-// GEMM flops of one k_update launch on a tile list (tiles outside block k
-// and outside the cross of kx; a tile of the AUG row block computes 16 rows)
-double update_flops(const std::vector<Tile> &tl, int64_t naug, int64_t k0, int kx) {
-  const int KT = NB / UT, kt0 = (int)(k0 / UT), kt1 = kt0 + KT;
-  const int taug = (int)(naug / UT) - 1;
-  double cnt = 0.0;
-  for (const Tile &t : tl) {
-    if (t.I < 0) continue;  // padding of the XCD order
-    if (kx >= 0 && ((t.I >= kx * KT && t.I < (kx + 1) * KT) || (t.J >= kx * KT && t.J < (kx + 1) * KT)))
-      continue;
-    const bool Ik = t.I >= kt0 && t.I < kt1, Jk = t.J >= kt0 && t.J < kt1;
-    if (!(Ik || Jk)) cnt += (t.I == taug) ? 16.0 / UT : 1.0;
-  }
-  return cnt * 2.0 * UT * UT * NB;
-}
-
-// GEMM flops of one k_update_multi launch (npan steps from block ka) on a tile
-// list, skipping the cross of blocks [kx0, kx1): a tile in group block jm
-// starts from W_jm and takes the later panels, any other tile every panel
-// (the kernel's rule; update_gemm_tiles_group over the whole triangle)
-double update_flops_group(const std::vector<Tile> &tl, int64_t naug, int64_t ka0, int npan, int kx0,
-                          int kx1) {
-  constexpr int KT = NB / UT;
-  const int ta0 = (int)(ka0 / UT);
-  const int taug = (int)(naug / UT) - 1;
-  double cnt = 0.0;
-  for (const Tile &t : tl) {
-    if (t.I < 0) continue;
-    if (kx0 >= 0 && ((t.I >= kx0 * KT && t.I < kx1 * KT) || (t.J >= kx0 * KT && t.J < kx1 * KT)))
-      continue;
-    const int di = t.I - ta0, dj = t.J - ta0;
-    const int bi = (di >= 0 && di < npan * KT) ? di / KT : -1;
-    const int bj = (dj >= 0 && dj < npan * KT) ? dj / KT : -1;
-    const int jm = std::max(bi, bj);
-    if (jm == npan - 1) continue;
-    cnt += ((t.I == taug) ? 16.0 / UT : 1.0) * (jm >= 0 ? npan - 1 - jm : npan);
-  }
-  return cnt * 2.0 * UT * UT * NB;
-}
-
 // The head schedule's tile lists on rank R: group_head_tiles' lists (the
-// single-GPU head / tail split, ace_sweep.hip) restricted to the rank's own
+// single-GPU head / tail split, ace_sweep_plan.cpp) restricted to the rank's own
 // tiles (column block owned), offsets hoff[G 2Z + m].
 void build_head_lists(ace_ctx *ctx, RankState &R, int64_t naug, int steps, int G, int Z) {
   constexpr int KT = NB / UT;
   std::vector<int64_t> off;
-  const std::vector<Tile> all = group_head_tiles(naug, steps, Z, off);
+  const std::vector<Tile> all = group_head_tiles(naug, steps, Z, update_order_block(), off);
   std::vector<Tile> mine;
   R.hoff.assign(off.size(), 0);
   for (size_t m = 0; m + 1 < off.size(); ++m) {
@@ -511,8 +471,9 @@ void run_sweep_sharded_steps(ShardModel &m, int which, bool timed) {
       ck(ctx, shard_update_main(v[j], k, buf, more ? k + 1 : -1, st), "shard update");
       if (tm && j == 0) {
         ck(ctx, hipEventRecord(m.ev_upd[(size_t)m.upd_used + 1], st), "event");
-        m.upd_flops[(size_t)m.upd_used / 2] =
-            update_flops(m.ranks[0]->hupd, m.naug, (int64_t)k * NB, more ? k + 1 : -1);
+        m.upd_flops[(size_t)m.upd_used / 2] =  // (one step, the cross of block k + 1 skipped)
+            tile_list_work(m.ranks[0]->hupd, m.naug / UT, k * (NB / UT), 1, more ? k + 1 : -1, k + 2) *
+            TILE_FLOPS;
         m.upd_used += 2;
       }
     }
@@ -677,7 +638,7 @@ void run_sweep_sharded_heads(ShardModel &m, int which, bool timed) {
       if (tm && j == 0) {
         ck(ctx, hipEventRecord(m.ev_upd[(size_t)m.upd_used + 1], st), "event");
         m.upd_flops[(size_t)m.upd_used / 2] =
-            update_flops_group(R.hupd, m.naug, (int64_t)kg * NB, zsize(g), kx0, kx1);
+            tile_list_work(R.hupd, m.naug / UT, kg * (NB / UT), zsize(g), kx0, kx1) * TILE_FLOPS;
         m.upd_used += 2;
       }
     }

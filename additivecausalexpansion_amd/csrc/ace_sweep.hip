@@ -24,9 +24,6 @@
 // y.alpha with no extra pass over the inverse.
 #include "ace_internal.h"
 
-#include <functional>
-#include <map>
-
 #include "ace_wgtime.h"
 
 namespace ace {
@@ -84,10 +81,6 @@ struct PivotLds {
   __attribute__((aligned(16))) double rowb[2][SUB];
   double pv[SUB];
 };
-
-#ifndef ACE_BULK_RESERVE_N
-#define ACE_BULK_RESERVE_N 8192
-#endif
 
 // broadcast lane T of every 16-lane row to the row (64-bit DPP)
 template <int T>
@@ -1317,17 +1310,14 @@ __global__ __launch_bounds__(UTHREADS, 2) void k_update_multi_r(double *__restri
 // up to n = ACE_BULK_RESERVE_N unless overridden
 bool q_first(int64_t naug) {
   static const int v = env_set("ACE_QFIRST") ? env_int("ACE_QFIRST", 0) != 0 : -1;
-  if (v >= 0) return v != 0;
-  return naug <= ACE_BULK_RESERVE_N + AUG;
+  return v >= 0 ? v != 0 : default_q_first(naug);
 }
 
 int bulk_reserve(int64_t naug) {
   static const int v =
       env_set("ACE_BULK_RESERVE") ? std::max(0, std::min(2, env_int("ACE_BULK_RESERVE", 0))) : -1;
-  if (v >= 0) return v;
-  return naug <= ACE_BULK_RESERVE_N + AUG ? 1 : 0;
+  return v >= 0 ? v : default_bulk_reserve(naug);
 }
-
 
 // Lookahead update: only the tiles with I or J in block kx (the next panel).
 // About 2 n/128 tiles -- one workgroup per CU at 128 x 128 -- so it uses
@@ -1896,106 +1886,12 @@ static hipError_t panel_sweep(const SweepBufs &b, int buf, int64_t k0, hipStream
   return hipGetLastError();
 }
 
-// GEMM tiles of one k_update launch, in full-tile units: a tile of the AUG
-// row block computes 16 of its 128 rows.
-double update_gemm_tiles(int64_t naug, int64_t k0, int kx, bool look) {
-  const int64_t nT = naug / UT, KT = NB / UT, kt0 = k0 / UT, kt1 = kt0 + KT;
-  double cnt = 0.0;
-  for (int64_t I = 0; I < nT; ++I)
-    for (int64_t J = 0; J <= I; ++J) {
-      const bool inx = kx >= 0 && ((I >= kx * KT && I < (kx + 1) * KT) ||
-                                   (J >= kx * KT && J < (kx + 1) * KT));
-      if (inx != look) continue;
-      const bool Ik = I >= kt0 && I < kt1, Jk = J >= kt0 && J < kt1;
-      if (!(Ik || Jk)) cnt += (I == nT - 1) ? 16.0 / UT : 1.0;
-    }
-  return cnt;
-}
-
-double sweep_flops(int64_t naug, int64_t npad) {
-  thread_local int64_t cn = -1, cp = -1;
-  thread_local double cf = 0.0;
-  if (naug == cn && npad == cp) return cf;
-  double f = 0.0;
-  for (int64_t k0 = 0; k0 < npad; k0 += NB)
-    f += update_gemm_tiles(naug, k0, -1, false) * 2.0 * UT * UT * NB +
-         2.0 * (double)(naug - NB) * NB * NB;
-  cn = naug;
-  cp = npad;
-  cf = f;
-  return f;
-}
-
 int update_order_block() {
   // 2 with two steps per launch (K = 512 panels per tile): 78.7-78.9 ms
   // per C2 evaluation against 79.1-79.2 at 4, 79.6-79.7 at 3, 81.1-81.2
   // at 8, 79.1-79.5 at 1 and at 0 (row-major); profiles/r02_chain_ab.txt
   static const int v = std::max(0, env_int("ACE_UPD_ORDER", 2));
   return v;
-}
-
-// The one-step schedule's lookahead cross on k_update's 128-tiles: -0.2 ms
-// per C2 evaluation against the 64-tile k_update_x (same box, 2 rounds: 81.03
-// / 81.26 vs 81.25 / 81.49 ms)
-std::vector<Tile> cross_update_tiles(int64_t naug, int steps, std::vector<int64_t> &off) {
-  const int64_t nT = naug / UT;
-  constexpr int KT = NB / UT;
-  std::vector<Tile> all;
-  off.assign(1, 0);
-  for (int k = 0; k + 1 < steps; ++k) {
-    const int64_t x0 = (int64_t)(k + 1) * KT, x1 = x0 + KT;
-    std::vector<Tile> t;
-    for (int64_t I = 0; I < nT; ++I)
-      for (int64_t J = 0; J <= I; ++J)
-        if ((I >= x0 && I < x1) || (J >= x0 && J < x1)) t.push_back(Tile{(int)I, (int)J});
-    const int S = update_order_block();
-    const std::vector<Tile> o = S > 0 ? xcd_update_order(t, S) : t;
-    all.insert(all.end(), o.begin(), o.end());
-    off.push_back((int64_t)all.size());
-  }
-  return all;
-}
-
-std::vector<Tile> pair_bulk_orders(int64_t naug, int steps, int64_t *len, int G, int r, int Z) {
-  const int64_t nT = naug / UT;
-  constexpr int KT = NB / UT;
-  const int ng = (steps + Z - 1) / Z;
-  const std::vector<Tile> base = own_tiles(nT, UT, G, r);
-  const int S = std::max(1, update_order_block());
-  std::vector<Tile> all;
-  std::vector<std::vector<Tile>> lists;
-  *len = 0;
-  for (int g = 0; g < ng; ++g) {
-    const int z = std::min(Z, steps - Z * g);
-    const int64_t ta0 = (int64_t)Z * g * KT;
-    const bool more = g + 1 < ng;
-    const int64_t x0 = more ? (int64_t)Z * (g + 1) * KT : -1;
-    const int64_t x1 = more ? (int64_t)std::min(Z * (g + 1) + Z, steps) * KT : -1;
-    // segments the tile runs: every panel, or those after its latest group
-    // block (a copy for the last one)
-    auto cost = [&](const Tile &t) -> double {
-      const int64_t I = t.I, J = t.J;
-      if (more && ((I >= x0 && I < x1) || (J >= x0 && J < x1))) return 0.0;  // skipped
-      const int64_t di = I - ta0, dj = J - ta0;
-      const int bi = (di >= 0 && di < z * KT) ? (int)(di / KT) : -1;
-      const int bj = (dj >= 0 && dj < z * KT) ? (int)(dj / KT) : -1;
-      const int jm = std::max(bi, bj);
-      if (jm == z - 1) return 0.05;  // copy
-      const double rows = (I == nT - 1) ? 16.0 / UT : 1.0;
-      return rows * (jm >= 0 ? z - 1 - jm : z);
-    };
-    // each XCD's cheap tiles last: -0.15 ms per C2 evaluation once the side
-    // chain is off the critical path (profiles/r02_chain_ab.txt)
-    lists.push_back(xcd_update_order(base, S, cost));
-    *len = std::max<int64_t>(*len, (int64_t)lists.back().size());
-  }
-  // one length for every group (padding: whole rows of 8, so the XCD dealing
-  // of each list stands)
-  for (auto &o : lists) {
-    o.resize((size_t)*len, Tile{-1, -1});
-    all.insert(all.end(), o.begin(), o.end());
-  }
-  return all;
 }
 
 int sweep_group() {
@@ -2012,8 +1908,7 @@ int sweep_group() {
 // profiles/r05_v11_ab_c1_group.txt), 4 above
 int sweep_group_n(int64_t naug) {
   static const bool set = env_set("ACE_GROUP");
-  if (set) return sweep_group();
-  return naug <= ACE_BULK_RESERVE_N + AUG ? 3 : 4;
+  return set ? sweep_group() : default_group(naug);
 }
 
 bool pair_steps() {
@@ -2022,245 +1917,129 @@ bool pair_steps() {
   return v;
 }
 
-// Head / tail split of the group schedule's lookahead (run_sweep_heads).
-// Group G (blocks [kb, kb + z)), lists at off[G 2Z + m] (m = 0, 1 unused for G = 0):
-//   m = 0          Q: the lower tiles with I and J in the group's blocks
-//   m = 1          the rest of the group's cross (I or J in the group, not in Q)
-//   m = 2 + i      Q_{i+1}: the tiles of Q with J in block kb + i + 1 or later
-//                  (panel kb + i is applied to them as soon as it is final), i < z - 1
-//   m = z + j      T_j: the tiles with I or J in block kb + j minus the head
-//                  H_j = {J in block kb + j, I in blocks [kb + j, kb + z)}, 1 <= j < z
-// Every list is XCD-dealt like the cross lists.
-std::vector<Tile> group_head_tiles(int64_t naug, int steps, int Z, std::vector<int64_t> &off) {
-  const int64_t nT = naug / UT;
-  constexpr int KT = NB / UT;
-  const int ng = (steps + Z - 1) / Z;
-  const int S = update_order_block();
-  std::vector<Tile> all;
-  off.assign((size_t)ng * 2 * Z + 1, 0);
-  auto blk = [&](int64_t t) { return (int)(t / KT); };
-  for (int G = 0; G < ng; ++G) {
-    const int kb = Z * G, z = std::min(Z, steps - kb);
-    std::vector<std::vector<Tile>> L((size_t)2 * Z);
-    {  // (group 0 uses only m >= 2)
-      for (int64_t I = 0; I < nT; ++I)
-        for (int64_t J = 0; J <= I; ++J) {
-          const int bi = blk(I) - kb, bj = blk(J) - kb;  // relative blocks
-          const bool ii = bi >= 0 && bi < z, ij = bj >= 0 && bj < z;
-          const Tile t{(int)I, (int)J};
-          if (ii && ij) {
-            L[0].push_back(t);
-            for (int i = 0; i + 1 < z; ++i)
-              if (bj >= i + 1) L[(size_t)(2 + i)].push_back(t);
-          } else if (ii || ij) {
-            L[1].push_back(t);
-          }
-          for (int j = 1; j < z; ++j) {
-            if (bi != j && bj != j) continue;
-            const bool head = bj == j && bi >= j && bi < z;
-            if (!head) L[(size_t)(z + j)].push_back(t);
-          }
-        }
-    }
-    for (int m = 0; m < 2 * Z; ++m) {
-      const std::vector<Tile> o = S > 0 ? xcd_update_order(L[(size_t)m], S) : L[(size_t)m];
-      all.insert(all.end(), o.begin(), o.end());
-      off[(size_t)G * 2 * Z + m + 1] = (int64_t)all.size();
-    }
+// Panels kb .. kb + npan - 1 of one launch: panel k's operands in slot k % nslot
+static PanelSet panel_set(double *const *R, double *const *C, int kb, int npan, int nslot) {
+  PanelSet ps;
+  for (int j = 0; j < 4; ++j) {
+    ps.R[j] = j < npan ? R[(kb + j) % nslot] : nullptr;
+    ps.C[j] = j < npan ? C[(kb + j) % nslot] : nullptr;
   }
-  return all;
+  return ps;
 }
 
-// GEMM tiles of one launch of npan steps from block ka0 / NB (k_update_multi's
-// rule) over every lower tile outside blocks [kx0, kx1), in units of one full
-// tile x NB (a tile of the AUG row block computes 16 of 128 rows).
-double update_gemm_tiles_group(int64_t naug, int64_t ka0, int npan, int kx0, int kx1) {
-  const int64_t nT = naug / UT;
-  constexpr int KT = NB / UT;
-  const int64_t ta0 = ka0 / UT;
-  double cnt = 0.0;
-  for (int64_t I = 0; I < nT; ++I)
-    for (int64_t J = 0; J <= I; ++J) {
-      if (kx0 >= 0 && ((I >= kx0 * KT && I < kx1 * KT) || (J >= kx0 * KT && J < kx1 * KT)))
-        continue;
-      const int64_t di = I - ta0, dj = J - ta0;
-      const int bi = (di >= 0 && di < npan * KT) ? (int)(di / KT) : -1;
-      const int bj = (dj >= 0 && dj < npan * KT) ? (int)(dj / KT) : -1;
-      const int jm = std::max(bi, bj);
-      if (jm == npan - 1) continue;
-      cnt += ((I == nT - 1) ? 16.0 / UT : 1.0) * (jm >= 0 ? npan - 1 - jm : npan);
-    }
-  return cnt;
-}
+// A schedule's events, by name (SweepEvents): recorded on and awaited by a
+// stream.  The first failure sticks in err, and nothing is enqueued after it.
+struct SweepIssue {
+  const SweepSync *sy;
+  hipError_t err = hipSuccess;
+  bool ok() const { return err == hipSuccess; }
+  void rec(int event, hipStream_t s) { if (ok()) err = hipEventRecord(sy->ev[event], s); }
+  void wait(hipStream_t s, int event) { if (ok()) err = hipStreamWaitEvent(s, sy->ev[event], 0); }
+};
 
-std::vector<Tile> own_tiles(int64_t ntile, int T, int G, int r) {
-  std::vector<Tile> t;
-  for (int64_t I = 0; I < ntile; ++I)
-    for (int64_t J = 0; J <= I; ++J)
-      if (owns_col(J * T, G, r)) t.push_back(Tile{(int)I, (int)J});
-  return t;
-}
-
-std::vector<Tile> xcd_update_order(const std::vector<Tile> &tl, int S,
-                                   const std::function<double(const Tile &)> &cost) {
-  // super-blocks (I / S, J / S) in row-major order; each goes whole to the
-  // XCD with the fewest tiles so far, so an XCD's in-flight tiles share few
-  // row / column panel blocks in its L2 (about -1 % per update launch at C2
-  // against every-eighth-tile dealing, profiles/r01_pairs_ab.txt)
-  constexpr int X = 8;
-  std::vector<std::vector<Tile>> q(X);
-  std::map<std::pair<int, int>, std::vector<Tile>> sb;
-  for (const Tile &t : tl) sb[{t.I / S, t.J / S}].push_back(t);
-  for (auto &kv : sb) {
-    int x = 0;
-    for (int i = 1; i < X; ++i)
-      if (q[i].size() < q[x].size()) x = i;
-    q[x].insert(q[x].end(), kv.second.begin(), kv.second.end());
-  }
-  if (cost)  // each XCD's dearest tiles first: its launch tail is the cheap ones
-    for (auto &v : q)
-      std::stable_sort(v.begin(), v.end(),
-                       [&](const Tile &a, const Tile &b) { return cost(a) > cost(b); });
-  size_t len = 0;
-  for (auto &v : q) len = std::max(len, v.size());
-  std::vector<Tile> out(len * X, Tile{-1, -1});
-  for (int x = 0; x < X; ++x)
-    for (size_t i = 0; i < q[x].size(); ++i) out[i * X + x] = q[x][i];
-  return out;
-}
-
-// The default schedule: Z = b.Z sweep steps per bulk launch (group g = steps
-// Z g .. Z g + z_g - 1, the last one may be shorter; panels in slots k % 2Z),
-// the lookahead split by what the next chain needs (lists from
-// group_head_tiles; group g+1 = blocks [kb, kb + z)):
-//   side (head path, the critical one): group g's panels on Q (gathers panel
-//     kb's head rows) -> for each panel k = kb + j: pivot + sub-steps ->
-//     panel GEMM of the rows in blocks (k, kb + z) -> panel k on Q_{j+1}
-//     (gathers panel k + 1's head rows) -> ...  -> ready(g+1)
-//   side2 (tail path): group g's panels on the rest of the cross -> for each
-//     panel k: [after k's sub-steps] the panel GEMM of the other rows ->
-//     [after k's head GEMM] T_{j+1}: panels kb .. k on block k + 1's cross
-//     minus its head -> ... -> ready2(g+1)
-//   main:  wait(ready g, ready2 g) -> the bulk launch of group g.
-// The head path is a chain of small launches (Q: z(z KT + 1) KT / 2 tiles),
-// where whole block-column crosses before each chain lost (C2 76.6 -> 75.9
-// ms, profiles/r03_v5_heads_ab.txt).  Every element sees the one-step
-// schedule's MFMA chains (run_sweep_steps) in the same order, fp64 kept in
-// registers between a launch's panels: bit-identical to it (tests/test_gpu.py).
-static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
-                                  const SweepTiming *tm) {
-  const int64_t naug = b.ld;
-  const unsigned nT = (unsigned)(naug / UT);
-  constexpr int KT = NB / UT;
-  const int steps = (int)(b.npad / NB);
+// The group schedule's launches (run_sweep_heads: their order, streams, waits).
+// The small-n regime (n <= ACE_BULK_RESERVE_N by default; ACE_BULK_RESERVE
+// selects it at any n): the chains, not the bulk launches, are the critical
+// path.  The bulk launches run as a persistent queue that leaves CUs to
+// the chains (k_update_multi_r), and with it
+//   * the latency-critical head launches work on 32 x 32 pieces
+//     (k_update_q4 / k_panel_gemm_q4): every Q launch, the head panel GEMMs
+//     and each group's last tail panel GEMM -- C1 3.59 -> 3.41 ms against
+//     64 x 64 (profiles/r06_qsplit_ab.txt);
+//   * each panel's four split sub-steps run as one k_panel_split4 launch;
+//   * each group's last tail panel GEMM runs on the head stream (tlast in
+//     run_sweep_heads).
+// bq_layout: after the queues, k_panel_split4's counters (fctr + 2 k) and
+// one D_0 counter of k_update_q4 per panel (qctr + k), zero between launches.
+struct HeadLaunches : SweepIssue {
+  const SweepBufs &b;
   const int Z = b.Z;
-  const int ng = (steps + Z - 1) / Z;
-  hipStream_t side = sy->side, side2 = sy->side2;
-  auto zsize = [&](int g) { return std::min(Z, steps - Z * g); };
-  auto slot = [&](int k) { return k % (2 * Z); };
-  auto E2 = [&](int g) { return sy->ev[2 * steps + 2 + 2 * g]; };     // ready2(g)
-  auto Egh = [&](int k) { return sy->ev[3 * steps + 3 + 2 * k]; };    // panel k's head GEMM done
-  auto Esp = [&](int k) { return sy->ev[3 * steps + 4 + 2 * k]; };    // panel k's sub-steps done
-  // bulk launch g done: the next-but-one group's Q waits for it on the side
-  // stream directly (with the tail path's E2), not through the main stream's
-  // combined event -- one cross-stream hop instead of two before each Q, the
-  // GPU's idle gap at every C1 group boundary 28 -> 10 us, bitwise equal
-  // (profiles/r05_v14_qdirect.txt)
-  // (events 5 steps + 3 .. + 7 belong to assemble_and_sweep)
-  const bool qdirect = sy->nev >= 6 * steps + 9;
-  auto Eb = [&](int g) { return sy->ev[5 * steps + 9 + g]; };  // g = -1: the main stream's
-                                                                // work before the sweep
-  auto gout = [&](int k) {
+  const int nT = (int)(b.ld / UT);
+  const bool small = b.bq && b.breserve > 0;
+  const BqLayout bql = bq_layout((int)(b.npad / NB), Z);
+  int slot(int k) const { return k % (2 * Z); }
+  // a launch that also gathers panel k into its slot
+  GatherOut gout(int k) const {
     return GatherOut{b.P[slot(k)], b.W[slot(k)], b.S[0], (int64_t)k * NB, b.ld};
+  }
+  struct List {
+    const Tile *p;
+    int64_t n;
   };
-  auto list = [&](int G, int m, const Tile *&p, int64_t &n) {
-    const int64_t i = (int64_t)G * 2 * Z + m;
-    p = b.htiles + b.hoff[i];
-    n = b.hoff[i + 1] - b.hoff[i];
-  };
+  // list m of group G (group_head_tiles' numbering)
+  List list(int G, int m) const {
+    const int64_t *const o = b.hoff + ((int64_t)G * 2 * Z + m);
+    return List{b.htiles + o[0], o[1] - o[0]};
+  }
   // npan steps from block kb on a tile list, skipping blocks [kx0, kx1).  Two
   // panels run k_update_multi too (77.1 against 78.1 ms per C2 evaluation with
   // a two-panel kernel of its own, profiles/r03_v4_group_ab.txt)
-  auto upd = [&](int npan, int kb, int kx0, int kx1, const Tile *tl, int64_t nt, GatherOut go,
-                 hipStream_t s_) {
-    if (nt <= 0) return;
+  void upd(int npan, int kb, int kx0, int kx1, List tl, GatherOut go, hipStream_t s_) {
+    if (!ok() || tl.n <= 0) return;
     const int64_t ka0 = (int64_t)kb * NB;
-    if (npan == 1) {
-      hipLaunchKernelGGL(k_update, dim3((unsigned)nt), dim3(UTHREADS), 0, s_, b.A, b.ld,
-                         b.W[slot(kb)], b.P[slot(kb)], b.W[slot(kb)], b.ld, ka0, -1, tl, 1, go);
-    } else {
-      PanelSet ps;
-      for (int j = 0; j < 4; ++j) {
-        ps.R[j] = j < npan ? b.W[slot(kb + j)] : nullptr;
-        ps.C[j] = j < npan ? b.P[slot(kb + j)] : nullptr;
-      }
-      hipLaunchKernelGGL(k_update_multi<false>, dim3((unsigned)nt), dim3(UTHREADS), 0, s_, b.A,
-                         b.ld, ps, npan, b.ld, ka0, kx0, kx1, tl, go, 1);
-    }
-  };
-  // The small-n regime (n <= ACE_BULK_RESERVE_N by default; ACE_BULK_RESERVE
-  // selects it at any n): the chains, not the bulk launches, are the critical
-  // path.  The bulk launches run as a persistent queue that leaves CUs to
-  // the chains (k_update_multi_r), and with it
-  //   * the latency-critical head launches work on 32 x 32 pieces
-  //     (k_update_q4 / k_panel_gemm_q4): every Q launch, the head panel GEMMs
-  //     and each group's last tail panel GEMM -- C1 3.59 -> 3.41 ms against
-  //     64 x 64 (profiles/r06_qsplit_ab.txt);
-  //   * each panel's four split sub-steps run as one k_panel_split4 launch;
-  //   * each group's last tail panel GEMM runs on the head stream (tlast below).
-  // bq_layout: after the queues, k_panel_split4's counters (fctr + 2 k) and
-  // one D_0 counter of k_update_q4 per panel (qctr + k), zero between launches.
-  const bool small = b.bq && b.breserve > 0;
-  const BqLayout bql = bq_layout(steps, Z);
-  int *const fctr = small ? b.bq + bql.fctr : nullptr;
-  int *const qctr = small ? b.bq + bql.qctr : nullptr;
+    if (npan == 1)
+      hipLaunchKernelGGL(k_update, dim3((unsigned)tl.n), dim3(UTHREADS), 0, s_, b.A, b.ld,
+                         b.W[slot(kb)], b.P[slot(kb)], b.W[slot(kb)], b.ld, ka0, -1, tl.p, 1, go);
+    else
+      hipLaunchKernelGGL(k_update_multi<false>, dim3((unsigned)tl.n), dim3(UTHREADS), 0, s_, b.A,
+                         b.ld, panel_set(b.W, b.P, kb, npan, 2 * Z), npan, b.ld, ka0, kx0, kx1,
+                         tl.p, go, 1);
+  }
+  // group g's bulk launch: its zg steps from block kg on its order, skipping
+  // the next group's cross [kx0, kx1)
+  void bulk(int g, int kg, int zg, int kx0, int kx1, hipStream_t s_) {
+    if (!ok()) return;
+    const List ord{b.gorder + (int64_t)g * b.glen, b.glen};
+    if (small && zg > 2)
+      // one workgroup per launch slot: two per CU (k_update_multi_r's occupancy)
+      hipLaunchKernelGGL(k_update_multi_r<false>, dim3(2 * device_cu_count()), dim3(UTHREADS), 0, s_, b.A, b.ld,
+                         panel_set(b.W, b.P, kg, zg, 2 * Z), zg, b.ld, (int64_t)kg * NB, kx0, kx1, ord.p, ord.n,
+                         b.bq + (int64_t)g * BQ_INTS, b.breserve, no_gather());
+    else
+      upd(zg, kg, kx0, kx1, ord, no_gather(), s_);
+  }
   // head-path launches on Q lists, on 64 x 64 quarters (k_update_q) or, small
-  // n, 32 x 32 pieces.  A launch that gathers a panel (every panel k >= 1)
+  // n, 32 x 32 pieces.  Each gathers a panel (go: every panel k >= 1) and
   // also sweeps its D_0 (k_update_q's fused pivot): that panel's chain then
   // starts at sub-step 0's panel update.
-  auto qupd = [&](int npan, int kb, const Tile *tl, int64_t nt, GatherOut go, hipStream_t s_) {
-    if (nt <= 0) return;
-    PanelSet ps;
-    for (int j = 0; j < 4; ++j) {
-      ps.R[j] = j < npan ? b.W[slot(kb + j)] : nullptr;
-      ps.C[j] = j < npan ? b.P[slot(kb + j)] : nullptr;
-    }
-    const bool fp = go.k0 >= 0;
+  void qupd(int npan, int kb, List tl, GatherOut go, hipStream_t s_) {
+    if (!ok() || tl.n <= 0) return;
+    const PanelSet ps = panel_set(b.W, b.P, kb, npan, 2 * Z);
     if (small)
-      hipLaunchKernelGGL(k_update_q4, dim3((unsigned)(16 * nt)), dim3(256), 0, s_, b.A, b.ld, ps,
-                         npan, b.ld, tl, go, fp ? b.SW : nullptr, fp ? b.piv : nullptr,
-                         fp ? b.flag : nullptr, qctr + (go.k0 >= 0 ? go.k0 / NB : 0));
+      hipLaunchKernelGGL(k_update_q4, dim3((unsigned)(16 * tl.n)), dim3(256), 0, s_, b.A, b.ld, ps,
+                         npan, b.ld, tl.p, go, b.SW, b.piv, b.flag, b.bq + bql.qctr + go.k0 / NB);
     else
-      hipLaunchKernelGGL(k_update_q, dim3((unsigned)(4 * nt)), dim3(256), 0, s_, b.A, b.ld, ps, npan,
-                         b.ld, tl, go, fp ? b.SW : nullptr, fp ? b.piv : nullptr,
-                         fp ? b.flag : nullptr);
-  };
+      hipLaunchKernelGGL(k_update_q, dim3((unsigned)(4 * tl.n)), dim3(256), 0, s_, b.A, b.ld, ps, npan,
+                         b.ld, tl.p, go, b.SW, b.piv, b.flag);
+  }
   // panel k's GEMM W_i = Pn_i W_kk over row tiles [r0, r1) (head) or all the
   // others (tail); the kernel itself skips the pivot block's rows
-  auto pgemm = [&](int k, int r0, int r1, bool head, hipStream_t s_, bool last = false) {
-    const int n = head ? r1 - r0 : (int)nT - (r1 - r0);
-    if (n <= 0) return;
+  void pgemm(int k, int r0, int r1, bool head, hipStream_t s_, bool last = false) {
+    const int n = head ? r1 - r0 : nT - (r1 - r0);
+    if (!ok() || n <= 0) return;
+    double *const W = b.W[slot(k)], *const P = b.P[slot(k)];
+    const int64_t k0 = (int64_t)k * NB;
+    auto q4 = [&](int rows, int from) {  // `rows` row tiles from `from`, on 32 x 32 pieces
+      if (rows > 0)
+        hipLaunchKernelGGL(k_panel_gemm_q4, dim3((unsigned)(2 * rows * (UT / XT)), 2 * (NB / XT)),
+                           dim3(256), 0, s_, W, P, b.ld, k0, from);
+    };
     if (!head && last && small) {
       // the group's last tail GEMM is on the path to the next group's Q: on
       // 32 x 32 pieces, the rows before and after the head
-      if (r0 > 0)
-        hipLaunchKernelGGL(k_panel_gemm_q4, dim3((unsigned)(2 * r0 * (UT / XT)), 2 * (NB / XT)),
-                           dim3(256), 0, s_, b.W[slot(k)], b.P[slot(k)], b.ld, (int64_t)k * NB, 0);
-      if ((int)nT > r1)
-        hipLaunchKernelGGL(k_panel_gemm_q4, dim3((unsigned)(2 * ((int)nT - r1) * (UT / XT)), 2 * (NB / XT)),
-                           dim3(256), 0, s_, b.W[slot(k)], b.P[slot(k)], b.ld, (int64_t)k * NB, r1);
-      return;
-    }
-    if (head && small)
-      hipLaunchKernelGGL(k_panel_gemm_q4, dim3((unsigned)(2 * n * (UT / XT)), 2 * (NB / XT)), dim3(256),
-                         0, s_, b.W[slot(k)], b.P[slot(k)], b.ld, (int64_t)k * NB, r0);
-    else if (head)
+      q4(r0, 0);
+      q4(nT - r1, r1);
+    } else if (head && small) {
+      q4(n, r0);
+    } else if (head) {
       hipLaunchKernelGGL(k_panel_gemm_q, dim3((unsigned)(n * (UT / XT)), NB / XT), dim3(256), 0, s_,
-                         b.W[slot(k)], b.P[slot(k)], b.ld, (int64_t)k * NB, r0);
-    else
-      hipLaunchKernelGGL(k_panel_gemm_t, dim3((unsigned)n, NB / UT), dim3(UTHREADS), 0, s_,
-                         b.W[slot(k)], b.P[slot(k)], b.ld, (int64_t)k * NB, 1, 0, 0, r0, r1);
-  };
+                         W, P, b.ld, k0, r0);
+    } else {
+      hipLaunchKernelGGL(k_panel_gemm_t, dim3((unsigned)n, NB / UT), dim3(UTHREADS), 0, s_, W, P,
+                         b.ld, k0, 1, 0, 0, r0, r1);
+    }
+  }
+  // [pivot +] sub-steps of panel k (gathered).
   // Small n: each fused chain launch with 13 KB of extra LDS, so that no
   // bulk / cross / tail workgroup (73.7 KB) fits beside a chain workgroup
   // (77.3 KB): the chain runs alone on its 16 CUs instead of sharing each
@@ -2269,191 +2048,172 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
   // before them only the contention moved, r06_c1_chain_isolation_ab.txt).
   // Placement only: the results do not depend on it.  ACE_CHAIN_XLDS=B
   // overrides the bytes (0: off).
-  static const unsigned xlds = (unsigned)std::max(0, env_int("ACE_CHAIN_XLDS", 13312));
-  auto chain = [&](int k, hipStream_t s_) {  // [pivot +] sub-steps of panel k (gathered)
+  void chain(int k, hipStream_t s_) {
+    static const unsigned xlds = (unsigned)std::max(0, env_int("ACE_CHAIN_XLDS", 13312));
+    if (!ok()) return;
     panel_chain(b.P[slot(k)], b.W[slot(k)], b.ld, (int64_t)k * NB, b.SW, b.S, b.piv, b.flag, 1, 0,
-                s_, k > 0, true, small ? fctr + 2 * k : nullptr, small ? xlds : 0u);
-  };
-  hipError_t e;
-  if (small && (e = hipMemsetAsync(b.bq, 0, (size_t)bql.fctr * sizeof(int), st)) != hipSuccess)
-    return e;  // the bulk queues (k_update_multi_r), before any bulk launch
-  if (!sy->ready_recorded) {
-    e = hipEventRecord(sy->ev[2 * steps], st);  // inputs ready
-    if (e != hipSuccess) return e;
+                s_, k > 0, true, small ? b.bq + bql.fctr + 2 * k : nullptr, small ? xlds : 0u);
   }
-  if ((e = hipStreamWaitEvent(side, sy->ev[2 * steps], 0)) != hipSuccess) return e;
-  // group G's lookahead: group G-1's panels on Q (side) and on the rest of
-  // the group's cross (side2), then each panel's chain, head / tail GEMMs
-  // and the next head / tail updates.  Group 0 has no previous panels: its
-  // first panel is gathered by k_gather.  (A non-fused split kernel -- k_pivot
-  // for every sub-step, 112 registers, 73 KB of LDS -- did not get group 0's
-  // chains beside the assembly's second part: neutral,
-  // profiles/r03_v5_heads_ab.txt.)
+};
+
+// The default schedule: Z = b.Z sweep steps per bulk launch (group g = steps
+// Z g .. Z g + z_g - 1, the last one may be shorter; panels in slots k % 2Z),
+// the lookahead split by what the next chain needs (lists from
+// group_head_tiles; group g+1 = blocks [kb, kb + z)):
+//   side (head path, the critical one): group g's panels on Q (gathers panel
+//     kb's head rows) -> for each panel k = kb + j: pivot + sub-steps ->
+//     panel GEMM of the rows in blocks (k, kb + z) -> panel k on Q_{j+1}
+//     (gathers panel k + 1's head rows) -> ...  -> head_done(g+1)
+//   side2 (tail path): group g's panels on the rest of the cross -> for each
+//     panel k: [after k's sub-steps] the panel GEMM of the other rows ->
+//     [after k's head GEMM] T_{j+1}: panels kb .. k on block k + 1's cross
+//     minus its head -> ... -> [after head_done(g+1)] tail_done(g+1)
+//   main:  wait(tail_done g) -> the bulk launch of group g.
+// The head path is a chain of small launches (Q: z(z KT + 1) KT / 2 tiles),
+// where whole block-column crosses before each chain lost (C2 76.6 -> 75.9
+// ms, profiles/r03_v5_heads_ab.txt).  Every element sees the one-step
+// schedule's MFMA chains (run_sweep_steps) in the same order, fp64 kept in
+// registers between a launch's panels: bit-identical to it (tests/test_gpu.py).
+static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
+                                  const SweepTiming *tm) {
+  const int64_t naug = b.ld;
+  constexpr int KT = NB / UT;
+  const int steps = (int)(b.npad / NB), Z = b.Z, ng = (steps + Z - 1) / Z;
+  const SweepEvents E{steps, Z};
+  hipStream_t side = sy->side, side2 = sy->side2;
+  HeadLaunches L{{sy}, b};
+  int used = 0;
+  auto zsize = [&](int g) { return std::min(Z, steps - Z * g); };
   // Small n (default up to n = ACE_BULK_RESERVE_N; ACE_QFIRST overrides): at a group
   // boundary the next group's Q launch (its head square, K = Z NB) runs
   // alone -- the rest of the cross (side2) and the bulk launch (main) wait
   // for it.  There the chain is the critical path and the bulk is short; Q
   // beside both took 163 us instead of ~40 (C1 trace, profiles/r05_v4_*).
   const bool qfirst = q_first(naug);
-  auto Eq = [&](int G) { return sy->ev[2 * steps + 1 + 2 * G]; };  // group G's Q done
   // Small n: group G's last tail panel GEMM on the head stream after the
-  // tail path's last T update (Et(G), an event slot the direct-wait schedule
-  // leaves free); the next group's Q then follows it in stream order and
-  // waits for the tail path through Et(G) instead of E2(G)
-  auto tlast = [&](int G) {
-    return small && qdirect && zsize(G) >= 2 && !(G == 0 && sy->tail_split);
-  };
-  auto Et = [&](int G) { return sy->ev[2 * G + 1]; };
-  hipEvent_t const Ef = sy->ev[2 * steps - 1];  // group 0's tail path + filler (odd: free too)
+  // tail path's last T update (last_tail(G)); the next group's Q then follows
+  // it in stream order and waits for the tail path through last_tail(G)
+  // instead of tail_done(G)
+  auto tlast = [&](int G) { return L.small && zsize(G) >= 2 && !(G == 0 && sy->tail_split); };
   // group G's first head launch (k_gather / Q); the rest by produce(G)
-  auto produce_q = [&](int G) -> hipError_t {
-    const int kb = Z * G;
-    if (G == 0) {
+  auto produce_q = [&](int G) {
+    if (G > 0)
+      L.qupd(zsize(G - 1), Z * (G - 1), L.list(G, 0), L.gout(Z * G), side);  // Q
+    else if (L.ok())  // (group 0 has no previous panels to gather panel 0 with)
       hipLaunchKernelGGL(k_gather, dim3((unsigned)(naug / 64), NB / 64), dim3(256), 0, side, b.A,
-                         b.ld, (int64_t)0, b.P[slot(0)], b.W[slot(0)], b.ld, b.S[0]);
-    } else {
-      const Tile *tl;
-      int64_t nt;
-      list(G, 0, tl, nt);
-      qupd(zsize(G - 1), Z * (G - 1), tl, nt, gout(kb), side);  // Q
-    }
-    return qfirst ? hipEventRecord(Eq(G), side) : hipSuccess;
+                         b.ld, (int64_t)0, b.P[0], b.W[0], b.ld, b.S[0]);
+    if (qfirst) L.rec(E.q_done(G), side);
   };
-  auto produce = [&](int G) -> hipError_t {
+  // group G's lookahead: group G-1's panels on Q (side, produce_q) and on the
+  // rest of the group's cross (side2), then each panel's chain, head / tail
+  // GEMMs and the next head / tail updates.  (A non-fused split kernel --
+  // k_pivot for every sub-step, 112 registers, 73 KB of LDS -- did not get
+  // group 0's chains beside the assembly's second part: neutral,
+  // profiles/r03_v5_heads_ab.txt.)
+  auto produce = [&](int G) {
     const int kb = Z * G, zb = zsize(G);
-    const Tile *tl;
-    int64_t nt;
     if (G > 0) {
-      if (qfirst) {
-        const hipError_t q = hipStreamWaitEvent(side2, Eq(G), 0);
-        if (q != hipSuccess) return q;
-      }
-      list(G, 1, tl, nt);
-      upd(zsize(G - 1), Z * (G - 1), -1, -1, tl, nt, gout(kb), side2);  // the rest of the cross
+      if (qfirst) L.wait(side2, E.q_done(G));
+      // the rest of the cross
+      L.upd(zsize(G - 1), Z * (G - 1), -1, -1, L.list(G, 1), L.gout(kb), side2);
     }
-    hipError_t r;
     const int hend = (kb + zb) * KT;  // head rows end (row tiles)
     // the head path (side) needs nothing of the tail path (side2): group 0's
     // tail may wait for the whole head path (sy->tail_split) -- on the CUs
     // the assembly leaves free the two would otherwise share them step by step
     const bool split = G == 0 && sy->tail_split;
     const bool tl_ = tlast(G);
-    auto head = [&](int j) -> hipError_t {
+    auto head = [&](int j) {
       const int k = kb + j;
-      chain(k, side);
-      hipError_t q;
-      // (the tail path waits for Esp(k) unless its last GEMM moved here, for
-      // Egh(k) only before a T launch: no marker packet nobody waits for)
-      const bool lastj = j + 1 == zb;
-      if (!(tl_ && lastj) && (q = hipEventRecord(Esp(k), side)) != hipSuccess) return q;
-      pgemm(k, (k + 1) * KT, hend, true, side);
-      if ((!lastj || !tl_) && (q = hipEventRecord(Egh(k), side)) != hipSuccess) return q;
-      if (tl_ && j + 1 == zb) {  // the last tail GEMM here, after the tail path's T_{zb-1}
-        if ((q = hipStreamWaitEvent(side, Et(G), 0)) != hipSuccess) return q;
-        pgemm(k, (k + 1) * KT, hend, false, side, true);
+      // the group's last tail GEMM here, after the tail path's T_{zb-1}
+      const bool tail_here = tl_ && j + 1 == zb;
+      L.chain(k, side);
+      // (the tail path waits for substeps_done(k) unless its last GEMM moved
+      // here, for head_gemm_done(k) only before a T launch: no marker packet
+      // nobody waits for)
+      if (!tail_here) L.rec(E.substeps_done(k), side);
+      L.pgemm(k, (k + 1) * KT, hend, true, side);
+      if (!tail_here) L.rec(E.head_gemm_done(k), side);
+      if (tail_here) {
+        L.wait(side, E.last_tail(G));
+        L.pgemm(k, (k + 1) * KT, hend, false, side, true);
       }
-      if (j + 1 < zb) {
-        list(G, 2 + j, tl, nt);
-        qupd(1, k, tl, nt, gout(k + 1), side);  // panel k on Q_{j+1}
-      }
-      return hipSuccess;
+      if (j + 1 < zb) L.qupd(1, k, L.list(G, 2 + j), L.gout(k + 1), side);  // panel k on Q_{j+1}
     };
-    auto tail = [&](int j) -> hipError_t {
+    auto tail = [&](int j) {
       const int k = kb + j;
-      hipError_t q;
-      if (tl_ && j + 1 == zb) return hipSuccess;  // on the head stream (above)
-      if ((q = hipStreamWaitEvent(side2, Esp(k), 0)) != hipSuccess) return q;
-      pgemm(k, (k + 1) * KT, hend, false, side2, j + 1 == zb);
+      if (tl_ && j + 1 == zb) return;  // on the head stream (above)
+      L.wait(side2, E.substeps_done(k));
+      L.pgemm(k, (k + 1) * KT, hend, false, side2, j + 1 == zb);
       if (j + 1 < zb) {
-        if ((q = hipStreamWaitEvent(side2, Egh(k), 0)) != hipSuccess) return q;
-        list(G, zb + j + 1, tl, nt);
-        upd(j + 1, kb, -1, -1, tl, nt, gout(k + 1), side2);  // T_{j+1}
-        if (tl_ && j + 2 == zb && (q = hipEventRecord(Et(G), side2)) != hipSuccess) return q;
+        L.wait(side2, E.head_gemm_done(k));
+        L.upd(j + 1, kb, -1, -1, L.list(G, zb + j + 1), L.gout(k + 1), side2);  // T_{j+1}
+        if (tl_ && j + 2 == zb) L.rec(E.last_tail(G), side2);
       }
-      return hipSuccess;
     };
     for (int j = 0; j < zb; ++j) {
-      if ((r = head(j)) != hipSuccess) return r;
-      if (!split && (r = tail(j)) != hipSuccess) return r;
+      head(j);
+      if (!split) tail(j);
     }
-    if ((r = hipEventRecord(sy->ev[2 * G], side)) != hipSuccess) return r;
+    L.rec(E.head_done(G), side);
     if (split) {
-      if ((r = hipStreamWaitEvent(side2, sy->ev[2 * G], 0)) != hipSuccess) return r;
-      for (int j = 0; j < zb; ++j)
-        if ((r = tail(j)) != hipSuccess) return r;
+      L.wait(side2, E.head_done(G));
+      for (int j = 0; j < zb; ++j) tail(j);
     }
-    if (G == 0 && sy->fill && (r = sy->fill(sy->fill_arg, side2)) != hipSuccess) return r;
-    // (group 0: the next Q also needs the assembly's filler launch: Ef)
-    if (G == 0 && sy->fill && tl_ && (r = hipEventRecord(Ef, side2)) != hipSuccess) return r;
-    // (qdirect: E2(G) also stands for the head path, so that the main stream
+    if (G == 0 && sy->fill && L.ok()) L.err = sy->fill(sy->fill_arg, side2);
+    // (group 0: the next Q also needs the assembly's filler launch)
+    if (G == 0 && sy->fill && tl_) L.rec(E.filler(), side2);
+    // (tail_done(G) also stands for the head path, so that the main stream
     // waits for one event before each bulk launch)
-    if (qdirect && !split && (r = hipStreamWaitEvent(side2, sy->ev[2 * G], 0)) != hipSuccess)
-      return r;
-    return hipEventRecord(E2(G), side2);
+    if (!split) L.wait(side2, E.head_done(G));
+    L.rec(E.tail_done(G), side2);
   };
-  if ((e = hipStreamWaitEvent(side2, sy->tail_after ? sy->tail_after : sy->ev[2 * steps], 0)) !=
-      hipSuccess)
-    return e;
-  if ((e = produce_q(0)) != hipSuccess || (e = produce(0)) != hipSuccess) return e;
-  if (qdirect && (e = hipEventRecord(Eb(-1), st)) != hipSuccess) return e;
-  int used = 0;
+  if (L.small && (L.err = hipMemsetAsync(b.bq, 0, (size_t)L.bql.fctr * sizeof(int), st)) != hipSuccess)
+    return L.err;  // the bulk queues (k_update_multi_r), before any bulk launch
+  if (!sy->ready_recorded) L.rec(E.ready(), st);
+  L.wait(side, E.ready());
+  L.wait(side2, sy->tail_after_recorded ? E.tail_after() : E.ready());
+  produce_q(0);
+  produce(0);
+  // bulk launch g done: the next-but-one group's Q waits for it on the side
+  // stream directly (with the tail path's tail_done), not through an event of
+  // the main stream after both -- one cross-stream hop instead of two before
+  // each Q, the GPU's idle gap at every C1 group boundary 28 -> 10 us, bitwise
+  // equal (profiles/r05_v14_qdirect.txt)
+  L.rec(E.bulk_done(-1), st);
   for (int g = 0; g < ng; ++g) {
-    const int kg = Z * g;
     const bool more = g + 1 < ng;
-    const int kb = Z * (g + 1), zb = more ? zsize(g + 1) : 0;
-    if (!qdirect && (e = hipStreamWaitEvent(st, sy->ev[2 * g], 0)) != hipSuccess) return e;
-    if ((e = hipStreamWaitEvent(st, E2(g), 0)) != hipSuccess) return e;
+    const int kx0 = more ? Z * (g + 1) : -1, kx1 = more ? Z * (g + 1) + zsize(g + 1) : -1;
+    L.wait(st, E.tail_done(g));
     if (more) {
       // Q(g+1) needs the tail path of g and bulk g-1 (A's square, the panel
       // slots it gathers into); at g = 0 the main stream's assembly instead.
       // The side2 path of g+1 needs the same (its own tail path in order, the
-      // head path through E2).  Without qdirect both wait for ev[2g+1], the
-      // main stream's record after all three.
-      if (qdirect) {
-        if ((e = hipStreamWaitEvent(side, !tlast(g) ? E2(g) : (g == 0 && sy->fill) ? Ef : Et(g), 0)) !=
-            hipSuccess)
-          return e;
-        if ((e = hipStreamWaitEvent(side, Eb(g - 1), 0)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(side2, Eb(g - 1), 0)) != hipSuccess) return e;
-      } else {
-        if ((e = hipEventRecord(sy->ev[2 * g + 1], st)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(side, sy->ev[2 * g + 1], 0)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(side2, sy->ev[2 * g + 1], 0)) != hipSuccess) return e;
-      }
-      if ((e = produce_q(g + 1)) != hipSuccess) return e;
-      if (qfirst && (e = hipStreamWaitEvent(st, Eq(g + 1), 0)) != hipSuccess) return e;
+      // head path through tail_done).
+      L.wait(side, !tlast(g) ? E.tail_done(g) : (g == 0 && sy->fill) ? E.filler() : E.last_tail(g));
+      L.wait(side, E.bulk_done(g - 1));
+      L.wait(side2, E.bulk_done(g - 1));
+      produce_q(g + 1);
+      if (qfirst) L.wait(st, E.q_done(g + 1));
     }
     // (the bulk launch is enqueued before the rest of group g+1's lookahead:
     // at small n the host's enqueue of ~40 launches, not the device, used to
     // hold it back by ~0.5 ms; the device order is the same either way)
-    const bool timed = tm && tm->ev && used + 2 <= tm->nev;
-    if (timed) (void)hipEventRecord(tm->ev[used], st);
-    const int64_t grid = b.gorder ? b.glen : (b.order ? b.norder : (int64_t)nT * (nT + 1) / 2);
-    const Tile *ord = b.gorder ? b.gorder + (int64_t)g * b.glen : b.order;
-    const int kx0 = more ? kb : -1, kx1 = more ? kb + zb : -1;
-    if (small && ord && zsize(g) > 2) {
-      PanelSet ps;
-      for (int j = 0; j < 4; ++j) {
-        ps.R[j] = j < zsize(g) ? b.W[slot(kg + j)] : nullptr;
-        ps.C[j] = j < zsize(g) ? b.P[slot(kg + j)] : nullptr;
-      }
-      // one workgroup per launch slot: two per CU (k_update_multi_r's occupancy)
-      hipLaunchKernelGGL(k_update_multi_r<false>, dim3(2 * device_cu_count()), dim3(UTHREADS), 0, st, b.A, b.ld,
-                         ps, zsize(g), b.ld, (int64_t)kg * NB, kx0, kx1, ord, grid,
-                         b.bq + (int64_t)g * BQ_INTS, b.breserve, no_gather());
-    } else {
-      upd(zsize(g), kg, kx0, kx1, ord, grid, no_gather(), st);
-    }
-    if (timed) {
-      (void)hipEventRecord(tm->ev[used + 1], st);
+    // (SweepTiming: the launch's event pair, while pairs are left)
+    hipEvent_t *const tp = tm && tm->ev && used + 2 <= tm->nev ? tm->ev + used : nullptr;
+    if (tp) (void)hipEventRecord(tp[0], st);
+    L.bulk(g, Z * g, zsize(g), kx0, kx1, st);
+    if (tp) {
+      (void)hipEventRecord(tp[1], st);
       if (tm->flops)
         tm->flops[used / 2] =
-            update_gemm_tiles_group(naug, (int64_t)kg * NB, zsize(g), kx0, kx1) * 2.0 * UT * UT * NB;
+            update_gemm_tiles_group(naug, (int64_t)Z * g * NB, zsize(g), kx0, kx1) * TILE_FLOPS;
       used += 2;
     }
-    if (qdirect && g + 2 < ng && (e = hipEventRecord(Eb(g), st)) != hipSuccess) return e;  // Q(g+2)
-    if (more && (e = produce(g + 1)) != hipSuccess) return e;
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (g + 2 < ng) L.rec(E.bulk_done(g), st);  // Q(g+2)
+    if (more) produce(g + 1);
+    if (!L.ok()) return L.err;
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   }
   if (tm && tm->used) *tm->used = used;
   return hipSuccess;
@@ -2465,48 +2225,51 @@ static hipError_t run_sweep_heads(const SweepBufs &b, hipStream_t st, const Swee
 // launch, profiles/r02_chain_ab.txt).
 //   side:  wait(bulk k-1 done) -> the cross of block k+1 with panel k (the
 //          lower tiles with I or J in block k+1, b.xtiles) -> panel k+1:
-//          gather, chain, panel GEMM -> ready(k+1)
-//   main:  wait(ready k) -> step k on every tile outside that cross.
+//          gather, chain, panel GEMM -> step_panel_done(k+1)
+//   main:  wait(step_panel_done k) -> step k on every tile outside that cross.
 // ACE_STREAMS=1 runs both on one stream, in this order.
 static hipError_t run_sweep_steps(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
                                   const SweepTiming *tm) {
   const int64_t naug = b.ld;
   const unsigned nT = (unsigned)(naug / UT);
   const int steps = (int)(b.npad / NB);
+  const SweepEvents E{steps, b.Z};
   hipStream_t side = sy->side;
+  SweepIssue L{sy};
   int used = 0;
-  hipError_t e;
-  if (!sy->ready_recorded && (e = hipEventRecord(sy->ev[2 * steps], st)) != hipSuccess)
-    return e;  // inputs ready
-  if ((e = hipStreamWaitEvent(side, sy->ev[2 * steps], 0)) != hipSuccess) return e;
-  if ((e = panel_sweep(b, 0, 0, side)) != hipSuccess) return e;
-  if ((e = hipEventRecord(sy->ev[0], side)) != hipSuccess) return e;
+  if (!sy->ready_recorded) L.rec(E.ready(), st);
+  L.wait(side, E.ready());
+  if (L.ok()) L.err = panel_sweep(b, 0, 0, side);
+  L.rec(E.step_panel_done(0), side);
   for (int k = 0; k < steps; ++k) {
     const int buf = k & 1;
     const int64_t k0 = (int64_t)k * NB;
     const bool more = k + 1 < steps;
-    if ((e = hipStreamWaitEvent(st, sy->ev[2 * k], 0)) != hipSuccess) return e;  // panel k done
+    L.wait(st, E.step_panel_done(k));
     if (more) {
-      if ((e = hipEventRecord(sy->ev[2 * k + 1], st)) != hipSuccess) return e;  // bulk k-1 done
-      if ((e = hipStreamWaitEvent(side, sy->ev[2 * k + 1], 0)) != hipSuccess) return e;
-      const int64_t x0 = b.xoff[k], nx = b.xoff[k + 1] - x0;
-      hipLaunchKernelGGL(k_update, dim3((unsigned)nx), dim3(UTHREADS), 0, side, b.A, b.ld, b.W[buf],
-                         b.P[buf], b.W[buf], b.ld, k0, -1, b.xtiles + x0, 1, no_gather());
-      if ((e = panel_sweep(b, buf ^ 1, k0 + NB, side)) != hipSuccess) return e;
-      if ((e = hipEventRecord(sy->ev[2 * (k + 1)], side)) != hipSuccess) return e;
+      L.rec(E.step_bulk_before(k), st);  // bulk k-1 done
+      L.wait(side, E.step_bulk_before(k));
+      if (L.ok()) {
+        const int64_t x0 = b.xoff[k], nx = b.xoff[k + 1] - x0;
+        hipLaunchKernelGGL(k_update, dim3((unsigned)nx), dim3(UTHREADS), 0, side, b.A, b.ld,
+                           b.W[buf], b.P[buf], b.W[buf], b.ld, k0, -1, b.xtiles + x0, 1, no_gather());
+        L.err = panel_sweep(b, buf ^ 1, k0 + NB, side);
+      }
+      L.rec(E.step_panel_done(k + 1), side);
     }
-    const bool timed = tm && tm->ev && used + 2 <= tm->nev;
-    if (timed) (void)hipEventRecord(tm->ev[used], st);
+    if (!L.ok()) return L.err;
+    hipEvent_t *const tp = tm && tm->ev && used + 2 <= tm->nev ? tm->ev + used : nullptr;
+    if (tp) (void)hipEventRecord(tp[0], st);
     hipLaunchKernelGGL(k_update, dim3(b.order ? (unsigned)b.norder : nT * (nT + 1) / 2),
                        dim3(UTHREADS), 0, st, b.A, b.ld, b.W[buf], b.P[buf], b.W[buf], b.ld, k0,
                        more ? k + 1 : -1, b.order, 1, no_gather());
-    if (timed) {
-      (void)hipEventRecord(tm->ev[used + 1], st);
-      if (tm->flops) tm->flops[used / 2] =
-          update_gemm_tiles(naug, k0, more ? k + 1 : -1, false) * 2.0 * UT * UT * NB;
+    if (tp) {
+      (void)hipEventRecord(tp[1], st);
+      if (tm->flops)
+        tm->flops[used / 2] = update_gemm_tiles(naug, k0, more ? k + 1 : -1, false) * TILE_FLOPS;
       used += 2;
     }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((L.err = hipGetLastError()) != hipSuccess) return L.err;
   }
   if (tm && tm->used) *tm->used = used;
   return hipSuccess;
@@ -2516,14 +2279,9 @@ hipError_t run_sweep(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
                      const SweepTiming *tm) {
   const int steps = (int)(b.npad / NB);
   // both schedules run on the caller's side streams (which may alias the
-  // main one) and events (SweepSync)
-  if (!sy || !sy->side || !sy->side2 || !b.xtiles || sy->nev < 5 * steps + 3)
-    return hipErrorInvalidValue;
-  if (pair_steps() && steps >= 2) {
-    if (!b.htiles || !b.gorder || !b.P[2 * b.Z - 1]) return hipErrorInvalidValue;
-    return run_sweep_heads(b, st, sy, tm);
-  }
-  return run_sweep_steps(b, st, sy, tm);
+  // main one) and events (SweepSync; buffers, lists and events: SweepWork)
+  if (sy->nev < SweepEvents{steps, b.Z}.count()) return hipErrorInvalidValue;
+  return pair_steps() && steps >= 2 ? run_sweep_heads(b, st, sy, tm) : run_sweep_steps(b, st, sy, tm);
 }
 
 // ---- sharded step pieces (driven by ace_shard.cpp) --------------------------
@@ -2582,13 +2340,9 @@ hipError_t shard_update_group(const ShardSweep &b, int kb, int npan, int nslot, 
                        b.W[s0], b.W[s0], b.ld, (int64_t)kb * NB, -1, tiles, b.G, go);
     return hipGetLastError();
   }
-  PanelSet ps;
-  for (int j = 0; j < 4; ++j) {
-    ps.R[j] = j < npan ? b.P[(kb + j) % nslot] : nullptr;
-    ps.C[j] = j < npan ? b.W[(kb + j) % nslot] : nullptr;
-  }
-  hipLaunchKernelGGL(k_update_multi<true>, dim3((unsigned)nt), dim3(UTHREADS), 0, st, b.A, b.ld, ps,
-                     npan, b.ld, (int64_t)kb * NB, kx0, kx1, tiles, go, b.G);
+  hipLaunchKernelGGL(k_update_multi<true>, dim3((unsigned)nt), dim3(UTHREADS), 0, st, b.A, b.ld,
+                     panel_set(b.P, b.W, kb, npan, nslot), npan, b.ld, (int64_t)kb * NB, kx0, kx1,
+                     tiles, go, b.G);
   return hipGetLastError();
 }
 

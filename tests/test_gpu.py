@@ -464,14 +464,16 @@ def test_update_tile_order_is_bitwise_neutral(A, tmp_path):
 LARGE_N_REGIME = {"ACE_GROUP": "4", "ACE_BULK_RESERVE": "0", "ACE_QFIRST": "0"}
 
 
-@pytest.mark.parametrize("n", [1100, 1500, 2600])
+@pytest.mark.parametrize("n", [300, 900, 1100, 1500, 2600])
 def test_sweep_schedules_are_bitwise_neutral(A, tmp_path, n):
     """The default schedule (run_sweep_heads: Z sweep steps per bulk launch,
     head / tail lookahead) runs every element's MFMA chain over the same k
     order as the one-step reference schedule (ACE_PAIR=0, `single`): the
     inverse is bit-identical.  n = 1100: 5 steps, 1500: 6, 2600: 11, so the
     groups are 2+2+1 / 3+2 / 4+1, 2+2+2 / 3+3 / 4+2 and 2 x 5 + 1 / 3+3+3+2 /
-    4+4+3 at Z = 2 / 3 / 4 (ACE_GROUP).  `default` is the small-n regime:
+    4+4+3 at Z = 2 / 3 / 4 (ACE_GROUP); n = 300: 2 steps, one group at every
+    Z; n = 900: 4 steps, 2+2 / 3+1 / 4, so the default Z = 3 ends on a group of
+    a single step in the small-n regime.  `default` is the small-n regime:
     Z = 3, the bulk launches as a persistent queue that leaves 1 CU per
     engine to the chains, and with it the head launches on 32 x 32 pieces,
     each panel's four sub-steps in one k_panel_split4 launch and the last
