@@ -7,12 +7,13 @@ from .native import (  # noqa: F401
     DMat, Adam_cpp, Nadam_cpp, Nesterov_cpp, coef_contract, grad_Matern_cpp, grad_SE_cpp,
     invkernel_cpp, kernmat_Matern32_cpp, kernmat_Matern32_symmetric_cpp, kernmat_SE_cpp,
     kernmat_SE_symmetric_cpp, mu_solution_cpp, ncs_basis, ncs_basis_deriv, norm_clip_cpp,
-    normalize_test, normalize_train, pred_cpp, pred_marginal_cpp, robust_levels, stats_cpp,
-    zero_pattern_order)
+    normalize_test, normalize_train, potrf_lower, pred_cpp, pred_marginal_cpp, robust_levels,
+    stats_cpp, zero_pattern_order)
 from .model import (  # noqa: F401
     BatchModel, DeviceModel, KernelClass_Matern32_R6, KernelClass_SE_R6, comm_unique_id, optAdam,
     optNadam, optNesterov, set_optimizer)
 from .r6 import R6KernelMatern32, R6KernelSE  # noqa: F401
 from .train import (  # noqa: F401
-    AceFit, ace_train, ace_train_batch, coef_posterior, linear_spline, ns_spline, predict_ace,
-    predict_ace_batch, response_surface, robust_treatment, set_basis, set_initial_parameters, square_spline)
+    AceFit, ace_train, ace_train_batch, coef_posterior, linear_spline, ns_spline,
+    posterior_draws, predict_ace, predict_ace_batch, response_surface, robust_treatment, set_basis,
+    set_initial_parameters, square_spline)

@@ -111,6 +111,11 @@ SIGNATURES = {
     "ace_model_predict_surface": (ctypes.c_int, [_vp, _D, _I64, _D, _I64, _D, ctypes.c_int,
                                                  ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                                  _D, _D, _D]),
+    "ace_model_predict_joint": (ctypes.c_int, [_vp, _D, _I64, _D, _D, ctypes.c_int,
+                                               ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                               ctypes.c_int, ctypes.c_double, _I64, _D, _D, _D, _D,
+                                               _D, _I64P]),
+    "ace_potrf_lower": (ctypes.c_int, [_I64, _D, _I64, ctypes.c_double, _D, _I64, _I64P]),
     "ace_model_profile": (ctypes.c_int, [_vp, ctypes.c_int]),
     "ace_model_kernel_time": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                              ctypes.POINTER(_I64),

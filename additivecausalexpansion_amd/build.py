@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["csrc/ace_pairs.hip", "csrc/ace_pairs_mm.hip", "csrc/ace_sweep.hip", "csrc/ace_util.hip",
-           "csrc/ace_symm.hip", "csrc/ace_api.cpp", "csrc/ace_host.cpp", "csrc/ace_shard.cpp",
+           "csrc/ace_symm.hip", "csrc/ace_joint.hip", "csrc/ace_api.cpp", "csrc/ace_host.cpp", "csrc/ace_shard.cpp",
            "csrc/ace_predict.cpp", "csrc/ace_dmat.cpp", "csrc/ace_train.hip",
            "csrc/ace_batch.hip", "csrc/ace_batch_predict.hip", "csrc/ace_batch.cpp",
            "csrc/ace_sweep_plan.cpp"]

@@ -442,4 +442,21 @@ hipError_t launch_diag_scaled(const double *A, int64_t ld, int64_t n, double sca
 // w = y - mu
 hipError_t launch_center(const double *y, int64_t n, double mu, double *w, hipStream_t st);
 
+// ---- joint posterior at the test points (ace_joint.hip) ----------------------
+// C (nx x nx, ldc) = scale (Kxx - Kx T + noise I) for Kx (nx x n, ldk) and
+// T (n x nx, ldt): lower 64-tiles on the fp64 MFMA, mirrored, so C is exactly
+// symmetric; Kxx is read at r >= c and on the diagonal tiles
+hipError_t launch_post_cov(const double *Kx, int64_t ldk, const double *T, int64_t ldt, int64_t n,
+                           const double *Kxx, int64_t ldx, int64_t nx, double noise, double scale,
+                           double *C, int64_t ldc, hipStream_t st);
+// L (n x n, ldl) = the lower Cholesky factor of tril(C) + jitter I, zeros
+// above the diagonal; blocked right-looking, NB = 64, no host sync.  *flag
+// (device int, reset here): 0, or the 1-based index of the first pivot that
+// is <= 0 or not finite -- L is then unfinished.
+hipError_t launch_potrf_lower(const double *C, int64_t ldc, int64_t n, double jitter, double *L,
+                              int64_t ldl, int *flag, hipStream_t st);
+// D (nx x S, ld nx) = m 1^T + L xi for xi (nx x S, ld nx)
+hipError_t launch_draws(const double *L, int64_t ldl, int64_t nx, const double *xi, int64_t S,
+                        const double *m, double *D, hipStream_t st);
+
 }  // namespace ace

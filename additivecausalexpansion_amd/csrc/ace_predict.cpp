@@ -560,6 +560,137 @@ void coef_cov_from_gram(const double *theta, int64_t nx, int B, double *cov) {
     }
 }
 
+// ace_model_predict_joint: the joint posterior at nx <= JOINT_NX test points
+// of a single-GPU model.  K_xX, T' = A^-1 K_xX^T (the full symmetric product:
+// the triangular form only serves the diagonal) and K_xx as predict_impl
+// builds them, in the retained scratch; then C = scale (K_xx - K_xX T' +
+// noise I) (k_post_cov), its factor L (launch_potrf_lower, no host sync
+// between the steps) and D = m 1^T + L xi.  C, L and the draws are scratch of
+// this call alone (PredScratch holds what the other calls share).  The
+// factor's flag is read once, with the results; outputs are written only at
+// the end.
+constexpr int64_t JOINT_NX = 8192, JOINT_S = 4096;
+
+struct JointReq {
+  bool marginal = false, noise = false;
+  double mean_y = 0.0, std_y = 1.0, std_Z = 1.0, jitter = 0.0;
+  int64_t S = 0;
+  const double *xi = nullptr;
+  double *map = nullptr, *cov = nullptr, *L = nullptr, *draws = nullptr;
+  int64_t *info = nullptr;
+};
+
+void joint_once(ace_model *m, const double *theta, int64_t nx, const double *X2, const double *Zt,
+                const JointReq &rq) {
+  ace_ctx *ctx = m->ctx;
+  hipStream_t st = ctx->stream;
+  const Shape &s = m->s;
+  const int64_t n = m->n;
+  const int B = s.B;
+  const bool marginal = rq.marginal;
+  const int b0 = marginal && B > 1 ? 1 : 0;  // src/pred_cpp.cpp:55-67
+  const int b1 = marginal ? (B > 1 ? B : 1) : B;
+  const double mu = theta[1];
+  const bool factor = rq.L || rq.S > 0;
+  std::vector<double> tab = make_tab(theta, s, false);  // kernels at the caller's theta (Q6)
+  DBuf dtab, dw, dad, dtmp, dC, dL, dxi, dD, dmap, dflag;
+  upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
+  const TabView tv = tab_view(dtab, s);
+  SideBufs test;
+  upload_side(ctx, test, s, X2, Zt, nx, nx);
+  const PairSide train = m->side.view(n);
+  alloc(ctx, dw, (size_t)n * sizeof(double), "alloc w");
+  ck(ctx, launch_center(m->y.d(), n, mu, dw.d(), st), "center y");
+  std::shared_ptr<PredScratch> ps = std::static_pointer_cast<PredScratch>(ctx->pred_state);
+  if (!ps) {
+    ps = std::make_shared<PredScratch>();
+    ctx->pred_state = ps;
+  }
+  alloc(ctx, ps->K, (size_t)(nx * n) * sizeof(double), "alloc K_xX");
+  alloc(ctx, ps->T, (size_t)(nx * n) * sizeof(double), "alloc T");
+  alloc(ctx, ps->Kxx, (size_t)(nx * nx) * sizeof(double), "alloc K_xx");
+  alloc(ctx, dC, (size_t)(nx * nx) * sizeof(double), "alloc C");
+  alloc(ctx, dad, (size_t)(2 * nx) * sizeof(double), "alloc sums");
+  // kernmat_*_cpp(X2, X, Z2, Z): test side first
+  ck(ctx, launch_assembly(2, s.kind, s.PM, test.view(nx), train, B, s.ZS, tv, ps->K.d(), nx,
+                          nullptr, st, b0, b1),
+     "cross assembly");
+  symm_resident(m, ps->K.d(), nx, true, nx, ps->T.d(), dtmp);
+  ck(ctx, launch_pred_cols(ps->T.d(), n, ps->K.d(), nx, n, nx, dw.d(), dad.d(), dad.d() + nx, st),
+     "pred sums");
+  ck(ctx, launch_assembly(1, s.kind, s.PM, test.view(nx), test.view(nx), B, s.ZS, tv,
+                          ps->Kxx.d(), nx, nullptr, st, b0, b1),
+     "symmetric assembly");
+  const double sc = marginal ? rq.std_y / rq.std_Z : rq.std_y;
+  const double noise = (!marginal && rq.noise) ? std::exp(theta[0]) : 0.0;
+  ck(ctx, launch_post_cov(ps->K.d(), nx, ps->T.d(), n, n, ps->Kxx.d(), nx, nx, noise, sc * sc,
+                          dC.d(), nx, st),
+     "posterior covariance");
+  if (factor) {
+    alloc(ctx, dL, (size_t)(nx * nx) * sizeof(double), "alloc L");
+    alloc(ctx, dflag, sizeof(int), "alloc flag");
+    ck(ctx, launch_potrf_lower(dC.d(), nx, nx, rq.jitter, dL.d(), nx, dflag.i(), st), "factor");
+  }
+  // the map needs the sums on the host (finish_pred / finish_marginal state it)
+  std::vector<double> ad((size_t)(2 * nx)), zero((size_t)nx, 0.0), hmap((size_t)nx),
+      hci((size_t)(2 * nx)), hvar((size_t)nx);
+  download(ctx, ad.data(), dad.d(), ad.size(), "download sums");
+  sync(ctx);
+  if (!marginal)
+    finish_pred(nx, ad.data(), zero.data(), zero.data(), theta[0], mu, rq.mean_y, rq.std_y,
+                hmap.data(), hci.data(), hvar.data());
+  else
+    finish_marginal(nx, ad.data(), zero.data(), zero.data(), rq.std_y, rq.std_Z, nullptr, nullptr,
+                    hmap.data(), hci.data(), hvar.data(), nullptr);
+  if (rq.S > 0) {
+    upload(ctx, dmap, hmap.data(), hmap.size(), "upload map");
+    upload(ctx, dxi, rq.xi, (size_t)(nx * rq.S), "upload xi");
+    alloc(ctx, dD, (size_t)(nx * rq.S) * sizeof(double), "alloc draws");
+    ck(ctx, launch_draws(dL.d(), nx, nx, dxi.d(), rq.S, dmap.d(), dD.d(), st), "draws");
+  }
+  int flag = 0;
+  if (factor) {
+    sync(ctx);
+    ck(ctx, hipMemcpyAsync(&flag, dflag.p, sizeof(int), hipMemcpyDeviceToHost, st), "download flag");
+    sync(ctx);
+  }
+  if (rq.cov) download(ctx, rq.cov, dC.d(), (size_t)(nx * nx), "download cov");
+  if (flag == 0) {
+    if (rq.L) download(ctx, rq.L, dL.d(), (size_t)(nx * nx), "download L");
+    if (rq.S > 0) download(ctx, rq.draws, dD.d(), (size_t)(nx * rq.S), "download draws");
+  }
+  sync(ctx);
+  if (flag != 0) {  // a numerical outcome: map and cov stay valid
+    if (rq.L) std::fill(rq.L, rq.L + nx * nx, kNaN);
+    if (rq.S > 0) std::fill(rq.draws, rq.draws + nx * rq.S, kNaN);
+  }
+  std::copy(hmap.begin(), hmap.end(), rq.map);
+  *rq.info = flag;
+}
+
+void joint_impl(ace_model *m, const double *theta, int64_t nx, const double *X2, const double *Zt,
+                const JointReq &rq) {
+  ace_ctx *ctx = m->ctx;
+  try {
+    joint_once(m, theta, nx, X2, Zt, rq);
+  } catch (const Fail &f) {
+    if (f.code != ACE_ERR_OOM) throw;
+    (void)hipGetLastError();
+    sync(ctx);  // the failed call's launches may still read the scratch
+    release_pred_state(ctx);
+    ctx->sweep_pool.clear();
+    joint_once(m, theta, nx, X2, Zt, rq);
+  }
+  if (auto ps = std::static_pointer_cast<PredScratch>(ctx->pred_state))
+    if (ps->K.bytes + ps->T.bytes + ps->Kxx.bytes > PRED_KEEP_BYTES) release_pred_state(ctx);
+}
+
+void unsupported(ace_ctx *ctx, bool ok, const char *msg) {
+  if (ok) return;
+  ctx->err = msg;
+  throw Fail{ACE_ERR_UNSUPPORTED};
+}
+
 // gsum / gcount of ace_model_predict_marginal_groups from the final map
 void group_sums_host(int64_t nx, int G, const int32_t *label, const double *map, double *gsum,
                      int64_t *gcount) {
@@ -786,6 +917,77 @@ int ace_model_predict_surface(ace_model *m, const double *theta, int64_t nx, con
   if (rc != ACE_OK) throw Fail{rc};
   return ACE_OK;
   ACE_CATCH
+}
+
+int ace_model_predict_joint(ace_model *m, const double *theta, int64_t nx, const double *X2,
+                            const double *Zt, int marginal, double mean_y, double std_y,
+                            double std_Z, int noise, double jitter, int64_t S, const double *xi,
+                            double *map, double *cov, double *L, double *draws, int64_t *info) {
+  if (!m) return ACE_ERR_ARG;
+  ace_ctx *ctx = m->ctx;
+  ACE_TRY
+  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+  arg(ctx, nx >= 1 && theta && map && info && (m->s.p == 0 || X2) && (m->s.B == 1 || Zt),
+      "bad shape / null argument");
+  arg(ctx, S >= 0 && (S == 0 || (xi && draws)), "S > 0 needs xi and draws");
+  arg(ctx, jitter >= 0.0 && std::isfinite(jitter), "jitter must be finite and >= 0");
+  unsupported(ctx, !m->shard, "predict_joint: sharded models are not supported (single GPU only)");
+  unsupported(ctx, nx <= JOINT_NX, "predict_joint: nx <= 8192 (one chunk; C is 512 MB there)");
+  unsupported(ctx, S <= JOINT_S, "predict_joint: S <= 4096 draws per call");
+  require_inverse(m);
+  JointReq rq;
+  rq.marginal = marginal != 0;
+  rq.noise = noise != 0;
+  rq.mean_y = marginal ? 0.0 : mean_y;
+  rq.std_y = std_y;
+  rq.std_Z = std_Z;
+  rq.jitter = jitter;
+  rq.S = S;
+  rq.xi = xi;
+  rq.map = map;
+  rq.cov = cov;
+  rq.L = L;
+  rq.draws = draws;
+  rq.info = info;
+  joint_impl(m, theta, nx, X2, Zt, rq);
+  return ACE_OK;
+  ACE_CATCH
+}
+
+int ace_potrf_lower(int64_t n, const double *A, int64_t lda, double jitter, double *L, int64_t ldl,
+                    int64_t *info) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  ace_ctx *ctx = nullptr;
+  const int rc = ace_create(dev, &ctx);
+  if (rc != ACE_OK) return rc;
+  int code = ACE_OK;
+  try {
+    arg(ctx, n >= 1 && A && L && info && lda >= n && ldl >= n, "bad shape / null argument");
+    arg(ctx, jitter >= 0.0 && std::isfinite(jitter), "jitter must be finite and >= 0");
+    unsupported(ctx, n <= 4 * JOINT_NX, "potrf_lower: n <= 32768");
+    hipStream_t st = ctx->stream;
+    std::vector<double> h((size_t)(n * n));
+    for (int64_t c = 0; c < n; ++c) std::copy(A + c * lda, A + c * lda + n, h.begin() + c * n);
+    DBuf dA, dL, dflag;
+    upload(ctx, dA, h.data(), h.size(), "upload A");
+    alloc(ctx, dL, (size_t)(n * n) * sizeof(double), "alloc L");
+    alloc(ctx, dflag, sizeof(int), "alloc flag");
+    ck(ctx, launch_potrf_lower(dA.d(), n, n, jitter, dL.d(), n, dflag.i(), st), "factor");
+    int flag = 0;
+    sync(ctx);
+    ck(ctx, hipMemcpyAsync(&flag, dflag.p, sizeof(int), hipMemcpyDeviceToHost, st), "download flag");
+    download(ctx, h.data(), dL.d(), h.size(), "download L");
+    sync(ctx);
+    for (int64_t c = 0; c < n; ++c)
+      for (int64_t r = 0; r < n; ++r) L[r + c * ldl] = flag ? kNaN : h[(size_t)(r + c * n)];
+    *info = flag;
+  } catch (const Fail &f) {
+    code = f.code;
+    g_create_err = ctx->err;  // no context outlives the call: ace_last_error(NULL)
+  }
+  ace_destroy(ctx);
+  return code;
 }
 
 }  // extern "C"

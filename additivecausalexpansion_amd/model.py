@@ -246,6 +246,43 @@ class DeviceModel:
             ci.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ptr(var)), self.ctx.handle)
         return {"map": mp, "ci": ci, "var": var}
 
+    def predict_joint(self, theta, X2, Z2, mean_y, std_y, *, marginal=False, std_Z=1.0,
+                      noise=True, jitter=0.0, xi=None, return_cov=False, return_factor=False):
+        """ace_model_predict_joint: the joint posterior at the rows of X2 --
+        {"map", "info"} and, if asked, "cov" (nx x nx, exactly symmetric), "L"
+        (lower Cholesky factor of cov + jitter I) and, with xi (nx x S standard
+        normals, the caller's), "draws" = map 1^T + L xi.  Z2: the test basis,
+        or with marginal its derivative (then std_y / std_Z scales, and
+        mean_y and noise are not used).  info > 0: pivot info of the factor
+        was not positive -- L and draws are NaN, map and cov valid; under Q6
+        (kernels at a theta other than the resident inverse's) cov need not be
+        positive semidefinite.  nx <= 8192, S <= 4096, single-GPU models."""
+        th, X2f, Zf, nx = self._test_side(theta, X2, Z2)
+        S = 0
+        xif = draws = None
+        if xi is not None:
+            xif = np.asfortranarray(np.asarray(xi, dtype=np.float64).reshape(nx, -1))
+            S = xif.shape[1]
+            draws = np.empty((nx, S), order="F") if S else None
+            if not S:
+                xif = None
+        mp = np.empty(nx)
+        cov = np.empty((nx, nx), order="F") if return_cov else None
+        L = np.empty((nx, nx), order="F") if return_factor else None
+        info = ctypes.c_int64(0)
+        check(lib().ace_model_predict_joint(
+            self.handle, ptr(th), nx, ptr(X2f), ptr(Zf), 1 if marginal else 0, float(mean_y),
+            float(std_y), float(np.ravel([std_Z])[0]), 1 if noise else 0, float(jitter), S,
+            ptr(xif), ptr(mp), ptr(cov), ptr(L), ptr(draws), ctypes.byref(info)), self.ctx.handle)
+        out = {"map": mp, "info": int(info.value)}
+        if return_cov:
+            out["cov"] = cov
+        if return_factor:
+            out["L"] = L
+        if xi is not None:
+            out["draws"] = draws if S else np.empty((nx, 0), order="F")
+        return out
+
     def comm_calls(self):
         """ace_model_comm_calls: collectives this rank issued since creation,
         {"broadcast", "allgather", "allreduce", "groups"} (zeros when simulated)."""
@@ -625,6 +662,15 @@ class _KernelClass:
                            "(para_update on the same data)")
         return self._model.predict_surface(self.parameters, X2, Zb, marginal, mean_y, std_y,
                                            std_Z)
+
+    def predict_joint(self, y, X, Z, X2, Z2, mean_y, std_y, **kw):
+        """The joint posterior at the test points on the fit's device model
+        (DeviceModel.predict_joint and its keywords; Z2 the test basis, or its
+        derivative with marginal=True)."""
+        if not self._resident(y, X, Z):
+            raise AceError("predict_joint needs the fit's device-resident inverse "
+                           "(para_update on the same data)")
+        return self._model.predict_joint(self.parameters, X2, Z2, mean_y, std_y, **kw)
 
     def mean_solution(self, y):
         """R/kernel_SE_R6.R:99-102 (private in the SE class)."""

@@ -461,3 +461,22 @@ def coef_contract(mean, cov, W, offset=0.0, scale=1.0, shift=0.0, noise=0.0):
                                   ptr(mp), ci.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                   ptr(var)))
     return {"map": mp, "ci": ci, "var": var}
+
+
+def potrf_lower(A, jitter=0.0, lda=None):
+    """ace_potrf_lower: (L, info) with L the lower Cholesky factor of A +
+    jitter I (the lower triangle of A is read; zeros above L's diagonal),
+    info = 0, or the 1-based index of the first pivot that is <= 0 or not
+    finite (L is then all NaN).  A: n x n, or with lda an (lda, n)
+    column-major array whose first n rows are the matrix."""
+    Af = fmat(A)
+    if Af.ndim != 2:
+        raise AceError("A must be a matrix")
+    n = Af.shape[1]
+    ld = Af.shape[0] if lda is None else int(lda)
+    if Af.shape[0] != ld or ld < n or n < 1:
+        raise AceError("A must be lda x n with lda >= n >= 1")
+    L = np.empty((n, n), order="F")
+    info = ctypes.c_int64(0)
+    check(lib().ace_potrf_lower(n, ptr(Af), ld, float(jitter), ptr(L), n, ctypes.byref(info)))
+    return L, int(info.value)

@@ -382,6 +382,63 @@ def predict_ace(obj, newX=None, newZ=None, marginal=False, return_average_treatm
                               bool(np.all(isbinary)) and return_average_treatments)
 
 
+def posterior_draws(fit, newX=None, newZ=None, marginal=False, n_draws=1000, seed=0, xi=None,
+                    jitter=None, return_average_treatments=False, return_cov=False):
+    """Joint posterior draws at the test points of predict_ace(fit, newX, newZ,
+    marginal): {"map": (nx), "draws": (nx, S)} with draws = map 1^T + L xi, L
+    the Cholesky factor of the posterior covariance of the predictions (the
+    noise term included) or, with marginal, of the marginal effects -- what
+    simultaneous bands, P(effect > 0 on a subgroup), quantiles and ranks of
+    the CATE are computed from.  xi (nx x S standard normals) defaults to
+    numpy's default_rng(seed).standard_normal((nx, n_draws)); the device draws
+    nothing itself.  jitter (absolute, added to the diagonal before factoring)
+    defaults to 0 for the prediction and to 1e-10 mean(diag cov) for the
+    marginal, whose covariance has no noise term to keep it definite.
+    return_average_treatments with a binary treatment adds "ate", "att",
+    "atu" (S each): every draw's mean over all, the treated and the untreated
+    test points (NaN for an empty group).  return_cov adds "cov"."""
+    X = fit["train_data"]["X"]
+    px = X.shape[1]
+    pz = fit["train_data"]["Z"].shape[1]
+    mom = fit["moments"]
+    Xn, Zn = _test_points(fit, newX, newZ, True)
+    K = fit["Kernel"]
+    y = fit["train_data"]["y"]
+    Btr = fit["Basis"].B
+    tb = fit["Basis"].testbasis(Zn)
+    nx = Xn.shape[0]
+    if xi is None:
+        xi = np.random.default_rng(seed).standard_normal((nx, int(n_draws)))
+    xi = np.asfortranarray(np.asarray(xi, dtype=np.float64).reshape(nx, -1))
+    std_Z = mom[1 + px:1 + px + pz, 1]
+    if jitter is None:
+        jitter = 0.0
+        if marginal:
+            v = K.predict_marginal(y, X, Btr, Xn, tb["B"], tb["dB"], mom[0, 0], mom[0, 1], std_Z,
+                                   False)["var"]
+            jitter = 1e-10 * float(np.mean(v))
+    r = K.predict_joint(y, X, Btr, Xn, tb["dB"] if marginal else tb["B"], mom[0, 0], mom[0, 1],
+                        marginal=marginal, std_Z=std_Z, noise=True, jitter=jitter, xi=xi,
+                        return_cov=return_cov)
+    if r["info"] > 0:
+        raise AceError(
+            f"posterior_draws: the posterior covariance is not positive definite at pivot "
+            f"{r['info']} of {nx} (jitter={jitter:g}). Pass a larger jitter=; note that the "
+            "fit's inverse is the last para_update's while the kernels use the final "
+            "parameters (Q6), so the matrix need not be positive semidefinite at all")
+    out = {"map": r["map"], "draws": r["draws"]}
+    if return_cov:
+        out["cov"] = r["cov"]
+    if return_average_treatments and bool(np.all(fit["train_data"]["Zbinary"])):
+        D = r["draws"]
+        zx = np.ravel(tb["B"]).astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["ate"] = D.sum(axis=0) / nx
+            out["att"] = (zx @ D) / np.sum(zx)
+            out["atu"] = ((zx == 0).astype(np.float64) @ D) / np.sum(zx == 0)
+    return out
+
+
 def predict_ace_batch(fits, newXs=None, newZs=None, marginal=False,
                       return_average_treatments=False, normalize=True):
     """predict_ace of M fits of small models (n <= 512 each, one kernel, p and

@@ -394,6 +394,43 @@ int ace_model_predict_surface(ace_model *m, const double *theta, int64_t nx,
                               const double *X2, int64_t nz, const double *Zb,
                               int marginal, double mean_y, double std_y,
                               double std_Z, double *map, double *ci, double *var);
+/* The joint posterior at the test points: the matrix the reference forms in
+ * full (src/pred_cpp.cpp:22, :72) and reduces to its diagonal,
+ *   C = scale^2 (K_xx - K_xX A^-1 K_xX^T [+ exp(theta[0]) I]),
+ * its lower Cholesky factor and joint draws D = map 1^T + L xi.
+ * marginal == 0: the kernels of ace_model_predict (Zt the test basis),
+ * scale = std_y, the noise term when noise != 0, map as ace_model_predict.
+ * marginal != 0: slices 1..B-1 (slice 0 when B == 1) with Zt the derivative
+ * basis, scale = std_y / std_Z, never a noise term (noise and mean_y are
+ * ignored), map as ace_model_predict_marginal.
+ *   map (nx); cov (nx x nx, may be NULL): exactly symmetric; L (nx x nx, may
+ *   be NULL): L L^T = cov + jitter I, exact zeros above the diagonal; xi
+ *   (nx x S, column-major) the caller's standard normals -- there is no
+ *   device generator -- and draws (nx x S); both may be NULL when S == 0.
+ * jitter >= 0 is absolute, in the units of cov.  Blocked right-looking
+ * Cholesky (NB = 64), rows solved by substitution.  All outputs are bitwise
+ * reproducible.
+ * *info = 0: the factor exists (or neither L nor draws was asked for, and none
+ * was computed).  *info = k > 0: pivot k (1-based) was the first that is <= 0
+ * or not finite; as in LAPACK this is a numerical outcome and the call still
+ * returns ACE_OK: map and cov are valid, L and draws are filled with NaN.
+ * The resident inverse is the last para_update's (Q6): with kernels at a
+ * different theta C need not be positive semidefinite, and then no jitter of
+ * the size of rounding helps -- factor at the theta of the inverse.
+ * Limits: nx <= 8192, S <= 4096, single-GPU models; a sharded model or a
+ * larger size returns ACE_ERR_UNSUPPORTED.  ACE_ERR_ARG before the first
+ * para_update, for nx < 1 or a negative or non-finite jitter. */
+int ace_model_predict_joint(ace_model *m, const double *theta, int64_t nx, const double *X2,
+                            const double *Zt, int marginal, double mean_y, double std_y,
+                            double std_Z, int noise, double jitter, int64_t S, const double *xi,
+                            double *map, double *cov, double *L, double *draws, int64_t *info);
+/* The factor alone, on host buffers: L (n x n, ldl) = the lower Cholesky
+ * factor of A + jitter I for a symmetric A (n x n, lda) of which the lower
+ * triangle is read; *info as above (L all NaN when *info > 0).  Runs on the
+ * current HIP device with a context of its own; after a failure
+ * ace_last_error(NULL) has the message.  n <= 32768. */
+int ace_potrf_lower(int64_t n, const double *A, int64_t lda, double jitter, double *L, int64_t ldl,
+                    int64_t *info);
 /* Per-kernel device timing for the roofline report: when enabled, HIP
  * events bracket every launch of the dense update kernel (`which` = 0),
  * the assembly kernel (1) and the gradient kernel (2) on the model's
