@@ -525,7 +525,8 @@ int ace_mu_solution_dev(ace_ctx *ctx, int64_t n, const double *y, const ace_dmat
 // the swept AUG rows (A^-1 y - mu A^-1 1) when this y was swept along, else a
 // product with the inverse; the residual is e^sigma alpha when inv was swept
 // from this same virtual Kfull (provenance), else the explicit Kfull alpha.
-static void alpha_and_sums(ace_ctx *ctx, int64_t n, const double *y, double mu,
+// Returns whether alpha came from the AUG rows.
+static bool alpha_and_sums(ace_ctx *ctx, int64_t n, const double *y, double mu,
                            const ace_dmat *Kfull, const ace_dmat *inv, DBuf &dalpha,
                            DBuf &dsums) {
   note_y(ctx, y, n);
@@ -535,7 +536,8 @@ static void alpha_and_sums(ace_ctx *ctx, int64_t n, const double *y, double mu,
   alloc(ctx, dalpha, (size_t)n * sizeof(double), "alloc alpha");
   alloc(ctx, dsums, 8 * sizeof(double), "alloc sums");
   const bool swept = inv->kind == ace_dmat::SWEPT;
-  if (swept && !inv->nonpd && inv->yaug && same_vals(*inv->yaug, y, (size_t)n)) {
+  const bool from_aug = swept && !inv->nonpd && inv->yaug && same_vals(*inv->yaug, y, (size_t)n);
+  if (from_aug) {
     const SweepWork &w = *inv->sweep;
     alloc(ctx, dscal, 8 * sizeof(double), "alloc scal");
     ck(ctx, launch_alpha_from_aug(w.A.d(), w.naug, w.npad, n, mu, 0, dalpha.d(), dscal.d(),
@@ -563,6 +565,7 @@ static void alpha_and_sums(ace_ctx *ctx, int64_t n, const double *y, double mu,
        "final sums");
   }
   sync(ctx);  // ds, dmu and dscal are freed on return
+  return from_aug;
 }
 
 int ace_stats_dev(ace_ctx *ctx, int64_t n, const double *y, const ace_dmat *Kmat,
@@ -600,14 +603,25 @@ int ace_grad_dev(ace_ctx *ctx, int kind, int64_t n, int p, int B, const double *
   arg(ctx, !Kel || (Kel->rows == n && Kel->cols == n && Kel->slices == B), "K must be n x n x B");
   const std::shared_ptr<SideBufs> sb = cached_side(ctx, s, n, X, Z);
   std::vector<double> tab = make_tab(theta, s);
-  DBuf dtab, dalpha, dsums, dg0, dwork0, dgs0;
+  DBuf dtab, dalpha, dsums, dg0, dwork0, dgs0, dmug;
   upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
-  alpha_and_sums(ctx, n, y, theta[1], Kfull, inv, dalpha, dsums);
+  const bool aug_alpha = alpha_and_sums(ctx, n, y, theta[1], Kfull, inv, dalpha, dsums);
   // the gradient recomputes K_b from X, Z, theta (a virtual cube is exactly
   // that); a dense cube handle is read like ace_grad's host cube
   const double *cube = (Kel && Kel->kind == ace_dmat::DENSE) ? Kel->buf.d() : nullptr;
   const bool swept = inv->kind == ace_dmat::SWEPT;
   const double *Ainv = swept ? inv->sweep->A.d() : values(as(inv));
+  // the gradient of mu, sum(inv ybar): summed over a product with the swept
+  // inverse it carries cond x eps of sum|alpha|; y . (A^-1 1) - mu 1^T A^-1 1
+  // from the inverse's AUG row 1 (as mu_solution_dev) has the rounding of
+  // the AUG-row alpha, whichever response was swept along
+  const bool mu_from_aug = swept && !inv->nonpd && !aug_alpha;
+  if (mu_from_aug) {
+    const SweepWork &w = *inv->sweep;
+    alloc(ctx, dmug, 2 * sizeof(double), "alloc mu gradient");
+    ck(ctx, launch_aug_dot(w.A.d(), w.naug, w.npad, n, dstate(ctx).ydev.d(), dmug.d(), ctx->stream),
+       "aug dot");
+  }
   const int64_t ld = swept ? inv->sweep->naug : n;
   // the fused model's XCD-dealt tile order and partial-sum scratch, kept
   // with the sweep buffers
@@ -645,7 +659,10 @@ int ace_grad_dev(ace_ctx *ctx, int kind, int64_t n, int p, int B, const double *
   std::vector<double> gs((size_t)ldg), sums(4);
   download(ctx, gs.data(), dgs->d(), gs.size(), "download gsum");
   download(ctx, sums.data(), dsums.d(), 4, "download sums");
+  double yv1[2] = {0.0, 0.0};
+  if (mu_from_aug) download(ctx, yv1, dmug.d(), 2, "download mu gradient");
   sync(ctx);
+  if (mu_from_aug) sums[2] = yv1[0] - theta[1] * yv1[1];
   compose_grad(s, theta, gs.data(), sums[2], grad);
   train_stats(std_y, (double)n, sums[0], host_logsum(eigenval, n), sums[1], &stats[0], &stats[1]);
   if (swept && inv->nonpd) {

@@ -28,7 +28,10 @@ class DMat:
     not (include/ace_hip.h "device-matrix handles")."""
 
     def __init__(self, handle, ctx):
-        self.handle, self.ctx = handle, ctx
+        # the Context is kept alive until the handle is freed: ace_dmat_free
+        # returns sweep buffers to the context's pool
+        self._owner = ctx or default_context()
+        self.handle, self.ctx = handle, self._owner.handle
         r, c, sl = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         check(lib().ace_dmat_dims(handle, ctypes.byref(r), ctypes.byref(c), ctypes.byref(sl)))
         self.shape = (r.value, c.value) if sl.value == 1 else (r.value, c.value, sl.value)
@@ -41,11 +44,19 @@ class DMat:
         h = ctypes.c_void_p()
         check(lib().ace_dmat_upload(_ctx(ctx), dims[0], dims[1], dims[2], ptr(af),
                                     ctypes.byref(h)), _ctx(ctx))
-        return cls(h, _ctx(ctx))
+        return cls(h, ctx)
 
     def read(self):
         out = np.empty(self.shape, order="F")
         check(lib().ace_dmat_read(self.handle, 0, out.size, ptr(out)), self.ctx)
+        return out
+
+    def read_region(self, offset, count):
+        """`count` values from column-major index `offset` on (the R shim's
+        ALTREP Elt / Get_region reads); count = 0 is allowed."""
+        out = np.empty(max(int(count), 0))
+        buf = out if out.size else np.empty(1)  # a valid pointer for count <= 0
+        check(lib().ace_dmat_read(self.handle, int(offset), int(count), ptr(buf)), self.ctx)
         return out
 
     def __array__(self, dtype=None, copy=None):
@@ -62,7 +73,8 @@ class DMat:
 
     def __del__(self):
         try:
-            if getattr(self, "handle", None):
+            # a context closed first took its handles' memory with it
+            if getattr(self, "handle", None) and self._owner.handle:
                 lib().ace_dmat_free(self.handle)
                 self.handle = None
         except Exception:
@@ -118,7 +130,7 @@ def _kernmat_cross(kind, X1, X2, Z1, Z2, parameters, ctx=None, elements=True, de
         check(lib().ace_kernmat_cross_dev(_ctx(ctx), kind, n1, n2, p, B, ptr(X1), ptr(X2), ptr(Z1),
                                           ptr(Z2), ptr(th), ctypes.byref(hf), ctypes.byref(he)),
               _ctx(ctx))
-        return {"full": DMat(hf, _ctx(ctx)), "elements": DMat(he, _ctx(ctx))}
+        return {"full": DMat(hf, ctx), "elements": DMat(he, ctx)}
     full = np.empty((n1, n2), order="F")
     el = np.empty((n1, n2, B), order="F") if elements else None
     check(lib().ace_kernmat_cross(_ctx(ctx), kind, n1, n2, p, B, ptr(X1), ptr(X2), ptr(Z1),
@@ -137,7 +149,7 @@ def _kernmat_sym(kind, X, Z, parameters, ctx=None, elements=True, device=False):
         hf, he = ctypes.c_void_p(), ctypes.c_void_p()
         check(lib().ace_kernmat_sym_dev(_ctx(ctx), kind, n, p, B, ptr(X), ptr(Z), ptr(th),
                                         ctypes.byref(hf), ctypes.byref(he)), _ctx(ctx))
-        return {"full": DMat(hf, _ctx(ctx)), "elements": DMat(he, _ctx(ctx))}
+        return {"full": DMat(hf, ctx), "elements": DMat(he, ctx)}
     full = np.empty((n, n), order="F")
     el = np.empty((n, n, B), order="F") if elements else None
     check(lib().ace_kernmat_sym(_ctx(ctx), kind, n, p, B, ptr(X), ptr(Z), ptr(th), ptr(full),
@@ -175,7 +187,7 @@ def invkernel_cpp(pdmat, sigma, ctx=None):
         h = ctypes.c_void_p()
         check(lib().ace_invkernel_dev(_ctx(ctx), pdmat.handle, sig, ptr(ev), ctypes.byref(h)),
               _ctx(ctx))
-        return {"eigenval": ev, "inv": DMat(h, _ctx(ctx))}
+        return {"eigenval": ev, "inv": DMat(h, ctx)}
     K = fmat(pdmat)
     n = K.shape[0]
     if K.shape != (n, n):
