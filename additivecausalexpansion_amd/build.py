@@ -17,7 +17,8 @@ SOURCES = ["csrc/ace_pairs.hip", "csrc/ace_pairs_mm.hip", "csrc/ace_sweep.hip", 
            "csrc/ace_batch.hip", "csrc/ace_batch_predict.hip", "csrc/ace_batch.cpp",
            "csrc/ace_sweep_plan.cpp"]
 HEADERS = ["csrc/ace_internal.h", "csrc/ace_common.h", "csrc/ace_model.h", "csrc/ace_batch.h",
-           "csrc/ace_formulas.h", "csrc/ace_wgtime.h", "csrc/ace_sweep_plan.h", "../include/ace_hip.h"]
+           "csrc/ace_formulas.h", "csrc/ace_wgtime.h", "csrc/ace_sweep_plan.h", "csrc/ace_retry.h",
+           "../include/ace_hip.h"]
 OUT = os.path.join(HERE, "libace_hip.so")
 OBJDIR = os.path.join(HERE, "build")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -428,12 +428,7 @@ int ace_pred_marginal(ace_ctx *ctx, int64_t nX, int64_t nx, int B, const double 
   std::vector<double> zx;
   if (calculate_ate) {
     zx.assign(Z_x, Z_x + nx);
-    std::vector<double> W3((size_t)(3 * nx));
-    for (int64_t r = 0; r < nx; ++r) {
-      W3[(size_t)r] = 1.0;
-      W3[(size_t)(nx + r)] = zx[(size_t)r];
-      W3[(size_t)(2 * nx + r)] = (zx[(size_t)r] == 0) ? 1.0 : 0.0;
-    }
+    const std::vector<double> W3 = ate_weights(Z_x, nx);
     upload(ctx, dW3, W3.data(), W3.size(), "upload weights");
     alloc(ctx, dq3, (size_t)(3 * nx + 3) * sizeof(double), "alloc");
     alloc(ctx, dtw, (size_t)(3 * nX) * sizeof(double), "alloc");

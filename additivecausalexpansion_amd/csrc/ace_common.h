@@ -248,6 +248,15 @@ struct SideBufs {
   }
 };
 
+// rows c0 .. c0 + nc of a side as an operand of their own
+inline PairSide chunk_view(const SideBufs &sb, const Shape &s, int64_t c0, int64_t nc) {
+  PairSide ps = sb.view(nc);
+  ps.X += c0 * s.PM;
+  ps.Z += c0 * s.ZS;
+  ps.LZ += c0 * s.ZS;
+  return ps;
+}
+
 inline void upload_side(ace_ctx *ctx, SideBufs &sb, const Shape &s, const double *X, const double *Z,
                  int64_t n, int64_t nalloc) {
   std::vector<double> xr = pack_rows(X, n, s.p, s.PM);
@@ -292,6 +301,17 @@ inline void finish_pred(int64_t nx, const double *a, const double *kd, const dou
     ci[r + nx] = yx + 1.96 * sd;
     var[r] = std::pow(sd, 2);
   }
+}
+
+// The ATE / ATT / ATU weights [1 | Z_x | Z_x == 0] (nx x 3, src/pred_cpp.cpp:89-106)
+inline std::vector<double> ate_weights(const double *Z_x, int64_t nx) {
+  std::vector<double> W3((size_t)(3 * nx));
+  for (int64_t r = 0; r < nx; ++r) {
+    W3[(size_t)r] = 1.0;
+    W3[(size_t)(nx + r)] = Z_x[r];
+    W3[(size_t)(2 * nx + r)] = (Z_x[r] == 0) ? 1.0 : 0.0;
+  }
+  return W3;
 }
 
 // ATE / ATT / ATU of pred_marginal_cpp (src/pred_cpp.cpp:89-126) from the sums

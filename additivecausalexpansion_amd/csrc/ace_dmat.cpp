@@ -137,10 +137,7 @@ const double *marginal_rows(ace_dmat *h, int64_t r0, int64_t nr, int64_t *ld, DB
     const KernSrc &k = *h->src;
     const Shape &s = k.shape;
     const int b0 = B > 1 ? 1 : 0, b1 = B > 1 ? B : 1;
-    PairSide a = k.s1->view(nr);
-    a.X += r0 * s.PM;
-    a.Z += r0 * s.ZS;
-    a.LZ += r0 * s.ZS;
+    const PairSide a = chunk_view(*k.s1, s, r0, nr);
     const PairSide b = symmetric ? k.s1->view(n2) : k.s2->view(n2);
     // the symmetric form's r < c ordering (mode 1) is only kept when the
     // block is the whole square matrix; row blocks use the cross form,
@@ -272,6 +269,23 @@ std::shared_ptr<SweepWork> pooled_sweep(ace_ctx *ctx, int64_t n) {
 
 void check_square(ace_ctx *ctx, const ace_dmat *h, int64_t n, const char *what) {
   arg(ctx, h && h->rows == n && h->cols == n && h->kind != ace_dmat::CUBE, what);
+}
+
+// What pred_dev and pred_marginal_dev hand the pipeline alike: w = y_X - mu
+// on the device (dw) and the product with the inverse handle.
+PredOps handle_ops(ace_ctx *ctx, int64_t nX, const double *y_X, double mu, const ace_dmat *inv,
+                   DBuf &dw) {
+  std::vector<double> w((size_t)nX);
+  for (int64_t c = 0; c < nX; ++c) w[(size_t)c] = y_X[c] - mu;
+  upload(ctx, dw, w.data(), w.size(), "upload w");
+  PredOps op;
+  op.ctx = ctx;
+  op.n = nX;
+  op.w = dw.d();
+  op.symm = [inv](const double *V, int64_t ldv, int64_t k, double *out, DBuf &) {
+    inv_times(as(inv), V, ldv, true, k, out);
+  };
+  return op;
 }
 
 }  // namespace
@@ -685,17 +699,8 @@ int ace_pred_dev(ace_ctx *ctx, int64_t nX, int64_t nx, const double *y_X, double
   arg(ctx, K_xX && K_xX->rows == nx && K_xX->cols == nX && K_xX->kind != ace_dmat::CUBE,
       "K_xX must be an nx x nX matrix handle");
   check_square(ctx, K_xx, nx, "K_xx must be an nx x nx matrix handle");
-  std::vector<double> w((size_t)nX);
-  for (int64_t c = 0; c < nX; ++c) w[(size_t)c] = y_X[c] - mu;
   DBuf dw;
-  upload(ctx, dw, w.data(), w.size(), "upload w");
-  PredOps op;
-  op.ctx = ctx;
-  op.n = nX;
-  op.w = dw.d();
-  op.symm = [&](const double *V, int64_t ldv, int64_t k, double *out, DBuf &) {
-    inv_times(as(invK_XX), V, ldv, true, k, out);
-  };
+  PredOps op = handle_ops(ctx, nX, y_X, mu, invK_XX, dw);
   op.cross = [&](int64_t c0, int64_t, int64_t *ld, DBuf &) -> const double * {
     *ld = nx;
     return values(as(K_xX)) + c0;
@@ -714,7 +719,11 @@ int ace_pred_dev(ace_ctx *ctx, int64_t nX, int64_t nx, const double *y_X, double
                              sizeof(double), (size_t)nx, hipMemcpyDeviceToDevice, ctx->stream),
        "diag");
   };
-  pred_pipeline(op, nx, false, nullptr, 0, sigma, mu, mean_y, std_y, 1.0, map, ci, var, nullptr);
+  PredReq rq(nx, std_y, map, ci, var);
+  rq.sigma = sigma;
+  rq.mu = mu;
+  rq.mean_y = mean_y;
+  pred_pipeline(op, rq);
   return ACE_OK;
   ACE_CATCH
 }
@@ -734,18 +743,9 @@ int ace_pred_marginal_dev(ace_ctx *ctx, int64_t nX, int64_t nx, const double *y_
   arg(ctx, K_xX && K_xX->rows == nx && K_xX->cols == nX, "K_xX must be nx x nX x B");
   arg(ctx, K_xx && K_xx->rows == nx && K_xx->cols == nx && K_xx->slices == K_xX->slices,
       "K_xx must be nx x nx x B");
-  std::vector<double> w((size_t)nX);
-  for (int64_t c = 0; c < nX; ++c) w[(size_t)c] = y_X[c] - mu;
   DBuf dw;
-  upload(ctx, dw, w.data(), w.size(), "upload w");
+  PredOps op = handle_ops(ctx, nX, y_X, mu, invK_XX, dw);
   const int B = (int)K_xX->slices;
-  PredOps op;
-  op.ctx = ctx;
-  op.n = nX;
-  op.w = dw.d();
-  op.symm = [&](const double *V, int64_t ldv, int64_t k, double *out, DBuf &) {
-    inv_times(as(invK_XX), V, ldv, true, k, out);
-  };
   op.cross = [&](int64_t c0, int64_t nc, int64_t *ld, DBuf &scratch) -> const double * {
     return marginal_rows(as(K_xX), c0, nc, ld, scratch);
   };
@@ -772,7 +772,15 @@ int ace_pred_marginal_dev(ace_ctx *ctx, int64_t nX, int64_t nx, const double *y_
   op.kxx = [&](int64_t *ld, DBuf &scratch) -> const double * {
     return marginal_rows(as(K_xx), 0, nx, ld, scratch);
   };
-  pred_pipeline(op, nx, true, Z_x, calculate_ate, sigma, mu, 0.0, std_y, std_Z, map, ci, var, avg);
+  PredReq rq(nx, std_y, map, ci, var);
+  rq.marginal = true;
+  rq.Z_x = Z_x;
+  rq.ate = calculate_ate;
+  rq.sigma = sigma;
+  rq.mu = mu;
+  rq.std_Z = std_Z;
+  rq.avg = avg;
+  pred_pipeline(op, rq);
   return ACE_OK;
   ACE_CATCH
 }

@@ -242,6 +242,16 @@ struct PredOps {
   // K_xx (nx x nx) for the ATE / ATT / ATU forms; scratch holds nx * nx
   std::function<const double *(int64_t *ld, DBuf &scratch)> kxx;
 };
-void pred_pipeline(const PredOps &op, int64_t nx, bool marginal, const double *Z_x, int ate,
-                   double sigma, double mu, double mean_y, double std_y, double std_Z,
-                   double *map, double *ci, double *var, double *avg);
+// What the pipeline is asked for: pred_cpp (marginal = false) or
+// pred_marginal_cpp, the latter with ATE / ATT / ATU into avg (12) when ate.
+struct PredReq {
+  int64_t nx;  // test points
+  bool marginal = false;
+  const double *Z_x = nullptr;  // host, nx (ate only)
+  int ate = 0;
+  double sigma = 0.0, mu = 0.0, mean_y = 0.0, std_y, std_Z = 1.0;
+  double *map, *ci, *var, *avg = nullptr;
+  PredReq(int64_t nx_, double std_y_, double *map_, double *ci_, double *var_)
+      : nx(nx_), std_y(std_y_), map(map_), ci(ci_), var(var_) {}
+};
+void pred_pipeline(const PredOps &op, const PredReq &rq);

@@ -1,6 +1,14 @@
-// ace_predict.cpp -- products with the resident inverse of a model: A^-1 V
-// (ace_model_apply_inverse) and device-resident posterior prediction
-// (ace_model_predict / ace_model_predict_marginal).
+// ace_predict.cpp -- what a model does with the resident inverse of its last
+// para_update.  Shared: with_pred_scratch (the retained scratch and its
+// out-of-memory / keep policy), PredFront (the setup every path starts with)
+// and symm_resident (A^-1 V: ace_model_apply_inverse).  Paths:
+//   * pred_pipeline: pred_cpp / pred_marginal_cpp with ATE / ATT / ATU over
+//     abstract operands (the model's here, the handles' in ace_dmat.cpp);
+//   * predict_impl, group_pass: ace_model_predict, _predict_marginal,
+//     _predict_marginal_groups, _robust_treatment;
+//   * coef_pass, coef_cross: ace_model_coef_posterior, _predict_surface,
+//     _coef_cross;
+//   * joint_pass: ace_model_predict_joint (and ace_potrf_lower beside it).
 //
 // The reference's predict path (R/kernel_SE_R6.R:75-97) builds K_xX and
 // K_xx (or their n x n2 x B "elements" cubes) on the host, ships the stored
@@ -33,6 +41,7 @@
 #include "ace_common.h"
 #include "ace_internal.h"
 #include "ace_model.h"
+#include "ace_retry.h"
 
 using namespace ace;
 
@@ -41,9 +50,62 @@ namespace {
 // test points per chunk: K_xX and T' are n x 8192 each (4.3 GB at n = 65536)
 constexpr int64_t NXC = 8192;
 
+// retained scratch above this size is released after the call (n = 16384,
+// nx = 4096 keeps its 1.1 GB; n = 65536 with 8192-point chunks frees 8.6 GB)
+constexpr size_t PRED_KEEP_BYTES = size_t(4) << 30;
+
+// The large buffers (K_xX, T', K_xx chunks), kept in the context between
+// calls.  They carry no values from one call to the next, except the last
+// chunk's K_xX from the pipeline to the grouped pass of the same call
+// (KeptChunk).
 struct PredScratch {
   DBuf K, T, Kxx;
 };
+
+// the context's scratch; create: make it if there is none (else null)
+std::shared_ptr<PredScratch> pred_scratch(ace_ctx *ctx, bool create) {
+  std::shared_ptr<PredScratch> ps = std::static_pointer_cast<PredScratch>(ctx->pred_state);
+  if (!ps && create) {
+    ps = std::make_shared<PredScratch>();
+    ctx->pred_state = ps;
+  }
+  return ps;
+}
+
+void release_pred_state(ace_ctx *ctx) {
+  if (auto ps = pred_scratch(ctx, false)) {
+    ps->K.release();
+    ps->T.release();
+    ps->Kxx.release();
+  }
+  ctx->pred_state.reset();
+}
+
+// Runs body(PredScratch &) under the scratch policy.  The reference handed to
+// the body stays valid if an allocation failure inside it drops
+// ctx->pred_state (alloc): the wrapper holds the scratch for the run.  Out of
+// device memory frees the scratch -- all three buffers, including the ones
+// the failed run still referenced -- and the pooled sweep buffers, and the
+// body runs once more on a new one (it writes its outputs only at its end).
+template <class Body>
+void with_pred_scratch(ace_ctx *ctx, Body &&body) {
+  retry_once_on<Fail>(
+      ACE_ERR_OOM,
+      [&] {
+        const std::shared_ptr<PredScratch> ps = pred_scratch(ctx, true);
+        body(*ps);
+      },
+      [&] {
+        (void)hipGetLastError();
+        sync(ctx);  // the failed run's launches may still read the scratch
+        release_pred_state(ctx);
+        ctx->sweep_pool.clear();
+      },
+      [&] {
+        if (auto ps = pred_scratch(ctx, false))
+          if (ps->K.bytes + ps->T.bytes + ps->Kxx.bytes > PRED_KEEP_BYTES) release_pred_state(ctx);
+      });
+}
 
 // out (n x k, ld n) = A^-1 V, summed over the simulated ranks; on an RCCL
 // rank the caller all-reduces (the partial holds this rank's entries only).
@@ -78,42 +140,72 @@ bool pred_tri() {
   return v;
 }
 
-void require_inverse(ace_model *m) {
-  arg(m->ctx, m->has_data, "ace_model_set_data() not called");
-  arg(m->ctx, m->has_inverse, "no resident inverse: call ace_model_para_update() first");
-}
+// What every prediction path sets up before its own work, at the caller's
+// theta (Q6).  Zt = null uploads a basis of ones (the slice kernels of the
+// coefficient paths do not read it; upload_side wants one).  parts: FRONT_W
+// adds w = y - mu (a = tmp (y - mu) with tmp^T = T', src/pred_cpp.cpp:20, 70);
+// FRONT_TRI adds, where the triangular form applies (one GPU, ACE_PRED_TRI),
+// diag(A^-1) and what ainv_w needs.
+enum : unsigned { FRONT_W = 1, FRONT_TRI = 2 };
+struct PredFront {
+  ace_model *m;
+  const double mu;
+  DBuf dtab, dw, ddiag, dscal;
+  TabView tv{};
+  SideBufs test;
+  PairSide train{};
+  int b0, b1;        // the slices summed: all, or the marginal ones (src/pred_cpp.cpp:55-67)
+  bool tri = false;  // the triangular form: ddiag holds diag(A^-1)
 
-}  // namespace
+  PredFront(ace_model *m_, const double *theta, int64_t nx, const double *X2, const double *Zt,
+            bool marginal, unsigned parts)
+      : m(m_), mu(theta[1]) {
+    ace_ctx *ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    const Shape &s = m->s;
+    const int64_t n = m->n;
+    b0 = marginal && s.B > 1 ? 1 : 0;
+    b1 = marginal ? (s.B > 1 ? s.B : 1) : s.B;
+    std::vector<double> tab = make_tab(theta, s, false);
+    upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
+    tv = tab_view(dtab, s);
+    const std::vector<double> ones(Zt ? 0 : (size_t)(nx * s.ZS), 1.0);
+    upload_side(ctx, test, s, X2, Zt ? Zt : ones.data(), nx, nx);
+    train = m->shard ? shard_train_side(m->shard) : m->side.view(n);
+    if (!(parts & FRONT_W)) return;
+    alloc(ctx, dw, (size_t)n * sizeof(double), "alloc w");
+    ck(ctx, launch_center(m->shard ? shard_train_y(m->shard) : m->y.d(), n, mu, dw.d(), st),
+       "center y");
+    tri = (parts & FRONT_TRI) && !m->shard && pred_tri();
+    if (!tri) return;  // -A^-1 is stored: scale -1
+    alloc(ctx, ddiag, (size_t)n * sizeof(double), "alloc diag");
+    ck(ctx, launch_diag_scaled(m->sw.A.d(), m->naug, n, -1.0, ddiag.d(), st), "diag");
+    alloc(ctx, dscal, 8 * sizeof(double), "alloc scalars");
+  }
+  // dst (n) = A^-1 (y - mu) = A^-1 y - mu A^-1 1: the AUG rows the sweep left
+  // in A (k_alpha_from_aug with the caller's mu), no n^2 pass.  tri only.
+  // A launch, not a buffer of the front: the coefficient pass issues it at
+  // once, the pipeline after its own uploads.
+  void ainv_w(double *dst) const {
+    ck(m->ctx, launch_alpha_from_aug(m->sw.A.d(), m->naug, m->npad, m->n, mu, 0, dst, dscal.d(),
+                                     m->ctx->stream, nullptr),
+       "A^-1 w");
+  }
+};
 
-namespace {
-void pred_pipeline_once(const PredOps &op, int64_t nx, bool marginal, const double *Z_x, int ate,
-                        double sigma, double mu, double mean_y, double std_y, double std_Z,
-                        double *map, double *ci, double *var, double *avg) {
+void pipeline_body(const PredOps &op, const PredReq &rq, PredScratch &ps) {
   ace_ctx *ctx = op.ctx;
   hipStream_t st = ctx->stream;
-  const int64_t n = op.n;
-  // the large buffers live in the context between calls (ctx->pred_state);
-  // this reference keeps them valid if an allocation failure drops it there
-  std::shared_ptr<PredScratch> ps = std::static_pointer_cast<PredScratch>(ctx->pred_state);
-  if (!ps) {
-    ps = std::make_shared<PredScratch>();
-    ctx->pred_state = ps;
-  }
-  DBuf &dKc = ps->K, &dT = ps->T, &dKmxx = ps->Kxx;
+  const int64_t n = op.n, nx = rq.nx;
+  const int ate = rq.ate;
+  DBuf &dKc = ps.K, &dT = ps.T, &dKmxx = ps.Kxx;
   DBuf dad, dkd, dtmp, dW3, dS3, dU3, dq3, dvt, ddot;
   const int64_t chunk = std::min<int64_t>(NXC, nx);
   alloc(ctx, dT, (size_t)(chunk * n) * sizeof(double), "alloc T");
   alloc(ctx, dad, (size_t)(2 * nx) * sizeof(double), "alloc sums");  // [a | d]
   alloc(ctx, dkd, (size_t)nx * sizeof(double), "alloc diag");
-  std::vector<double> zx;
-  if (ate) {  // weights 1, Z_x, (Z_x == 0) (src/pred_cpp.cpp:89-106)
-    zx.assign(Z_x, Z_x + nx);
-    std::vector<double> W3((size_t)(3 * nx));
-    for (int64_t r = 0; r < nx; ++r) {
-      W3[(size_t)r] = 1.0;
-      W3[(size_t)(nx + r)] = zx[(size_t)r];
-      W3[(size_t)(2 * nx + r)] = (zx[(size_t)r] == 0) ? 1.0 : 0.0;
-    }
+  if (ate) {
+    const std::vector<double> W3 = ate_weights(rq.Z_x, nx);
     upload(ctx, dW3, W3.data(), W3.size(), "upload weights");
     alloc(ctx, dS3, (size_t)(3 * n) * sizeof(double), "alloc s");
     alloc(ctx, dU3, (size_t)(3 * n) * sizeof(double), "alloc u");
@@ -181,60 +273,18 @@ void pred_pipeline_once(const PredOps &op, int64_t nx, bool marginal, const doub
   download(ctx, ad.data(), dad.d(), ad.size(), "download sums");
   download(ctx, kd.data(), dkd.d(), kd.size(), "download diag");
   sync(ctx);
-  if (!marginal) {
-    finish_pred(nx, ad.data(), kd.data(), ad.data() + nx, sigma, mu, mean_y, std_y, map, ci, var);
+  if (!rq.marginal) {
+    finish_pred(nx, ad.data(), kd.data(), ad.data() + nx, rq.sigma, rq.mu, rq.mean_y, rq.std_y,
+                rq.map, rq.ci, rq.var);
     return;
   }
   std::vector<double> post(3);
   for (int j = 0; j < 3; ++j) post[(size_t)j] = q3[(size_t)j] - dots[(size_t)j];
-  finish_marginal(nx, ad.data(), kd.data(), ad.data() + nx, std_y, std_Z,
-                  ate ? zx.data() : nullptr, ate ? post.data() : nullptr, map, ci, var, avg);
+  finish_marginal(nx, ad.data(), kd.data(), ad.data() + nx, rq.std_y, rq.std_Z,
+                  ate ? rq.Z_x : nullptr, ate ? post.data() : nullptr, rq.map, rq.ci, rq.var,
+                  rq.avg);
 }
 
-// retained scratch above this size is released after the call (n = 16384,
-// nx = 4096 keeps its 1.1 GB; n = 65536 with 8192-point chunks frees 8.6 GB)
-constexpr size_t PRED_KEEP_BYTES = size_t(4) << 30;
-
-void release_pred_state(ace_ctx *ctx) {
-  if (auto ps = std::static_pointer_cast<PredScratch>(ctx->pred_state)) {
-    ps->K.release();
-    ps->T.release();
-    ps->Kxx.release();
-  }
-  ctx->pred_state.reset();
-}
-}  // namespace
-
-// The device prediction pipeline (pred_cpp / pred_marginal_cpp semantics)
-// over abstract operands -- the device model's resident inverse here, and the
-// device-matrix handles of the R6-faithful path in ace_dmat.cpp.  The large
-// scratch (K_xX, T', K_xx chunks) stays in the context between calls; an
-// allocation failure inside the call frees it -- all three buffers, including
-// the ones the failed call still referenced -- and runs the call once more
-// (outputs are written only at its end), and scratch above PRED_KEEP_BYTES
-// is not kept past the call.
-void pred_pipeline(const PredOps &op, int64_t nx, bool marginal, const double *Z_x, int ate,
-                   double sigma, double mu, double mean_y, double std_y, double std_Z,
-                   double *map, double *ci, double *var, double *avg) {
-  ace_ctx *ctx = op.ctx;
-  try {
-    pred_pipeline_once(op, nx, marginal, Z_x, ate, sigma, mu, mean_y, std_y, std_Z, map, ci, var, avg);
-  } catch (const Fail &f) {
-    if (f.code != ACE_ERR_OOM) throw;
-    (void)hipGetLastError();
-    sync(ctx);  // the failed call's launches may still read the scratch
-    release_pred_state(ctx);
-    ctx->sweep_pool.clear();
-    pred_pipeline_once(op, nx, marginal, Z_x, ate, sigma, mu, mean_y, std_y, std_Z, map, ci, var, avg);
-  }
-  if (auto ps = std::static_pointer_cast<PredScratch>(ctx->pred_state))
-    if (ps->K.bytes + ps->T.bytes + ps->Kxx.bytes > PRED_KEEP_BYTES) release_pred_state(ctx);
-}
-
-namespace {
-
-// ace_model_predict (marginal = false) / ace_model_predict_marginal: the
-// model's resident inverse, K_xX assembled from the resident training side.
 // The grouped pass after the marginal pipeline (ace_model_predict_marginal_groups,
 // ace_model_robust_treatment): gcov = E^T (Km_xx - Km_xX A^-1 Km_xX^T) E for
 // the indicator E of `label`; prepare (optional) runs after map / ci / var
@@ -246,108 +296,29 @@ struct GroupReq {
   std::function<void()> prepare;
 };
 
-void predict_impl(ace_model *m, const double *theta, int64_t nx, const double *X2,
-                  const double *Zt, bool marginal, const double *Z_x, int ate, double mean_y,
-                  double std_y, double std_Z, double *map, double *ci, double *var, double *avg,
-                  const GroupReq *grp = nullptr) {
+// The chunk of K_xX the pipeline assembled last (rows c0 .. c0 + nc at K):
+// still in the scratch when the pipeline kept it.
+struct KeptChunk {
+  int64_t c0 = -1, nc = 0;
+  const double *K = nullptr;
+};
+
+void group_pass(const PredFront &f, const PredOps &op, int64_t nx, const GroupReq &grp,
+                KeptChunk kept, PredScratch &ps) {
+  ace_model *m = f.m;
   ace_ctx *ctx = m->ctx;
   hipStream_t st = ctx->stream;
   const Shape &s = m->s;
   const int64_t n = m->n;
-  const int B = s.B;
-  const int b0 = marginal && B > 1 ? 1 : 0;  // src/pred_cpp.cpp:55-67
-  const int b1 = marginal ? (B > 1 ? B : 1) : B;
-  const double mu = theta[1];
-  // kernels at the caller's theta (Q6)
-  std::vector<double> tab = make_tab(theta, s, false);
-  DBuf dtab, dw;
-  upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
-  const TabView tv = tab_view(dtab, s);
-  SideBufs test;
-  upload_side(ctx, test, s, X2, Zt, nx, nx);
-  const PairSide train = m->shard ? shard_train_side(m->shard) : m->side.view(n);
-  // w = y - mu: a = tmp (y - mu) with tmp^T = T' (src/pred_cpp.cpp:20, 70)
-  alloc(ctx, dw, (size_t)n * sizeof(double), "alloc w");
-  ck(ctx, launch_center(m->shard ? shard_train_y(m->shard) : m->y.d(), n, mu, dw.d(), st),
-     "center y");
-  PredOps op;
-  op.ctx = ctx;
-  op.n = n;
-  op.w = dw.d();
-  op.symm = [&](const double *V, int64_t ldv, int64_t k, double *out, DBuf &tmp) {
-    symm_resident(m, V, ldv, true, k, out, tmp);
-  };
-  DBuf ddiag, dscal;
-  if (!m->shard && pred_tri()) {  // -A^-1 is stored: scale -1
-    alloc(ctx, ddiag, (size_t)n * sizeof(double), "alloc diag");
-    ck(ctx, launch_diag_scaled(m->sw.A.d(), m->naug, n, -1.0, ddiag.d(), st), "diag");
-    op.sdiag = ddiag.d();
-    op.trmm = [&](const double *V, int64_t ldv, int64_t k, double *out) {
-      ck(ctx, launch_trmm_lower(m->sw.A.d(), m->naug, n, V, ldv, k, -1.0, out, n, st), "trmm");
-    };
-    op.symv = [&](const double *V, int64_t ldv, int64_t k, double *out, DBuf &tmp) {
-      symm_resident(m, V, ldv, false, k, out, tmp);
-    };
-    // A^-1 (y - mu) = A^-1 y - mu A^-1 1: the AUG rows the sweep left in A
-    // (k_alpha_from_aug with the caller's mu), no n^2 pass
-    alloc(ctx, dscal, 8 * sizeof(double), "alloc scalars");
-    op.ainv_w = [&](double *dst) {
-      ck(ctx, launch_alpha_from_aug(m->sw.A.d(), m->naug, m->npad, n, mu, 0, dst, dscal.d(), st,
-                                    nullptr),
-         "A^-1 w");
-    };
-  }
-  if (m->shard) op.allreduce = [&](double *b, int64_t c) { shard_allreduce_sum(m->shard, b, c); };
-  // the chunk K_xX's scratch holds after the pipeline (the grouped pass reuses it)
-  int64_t last_c0 = -1, last_nc = 0;
-  const double *last_K = nullptr;
-  op.cross = [&](int64_t c0, int64_t nc, int64_t *ld, DBuf &scratch) -> const double * {
-    alloc(ctx, scratch, (size_t)(nc * n) * sizeof(double), "alloc K_xX");
-    last_c0 = c0;
-    last_nc = nc;
-    last_K = scratch.d();
-    PairSide tc = test.view(nc);
-    tc.X += c0 * s.PM;
-    tc.Z += c0 * s.ZS;
-    tc.LZ += c0 * s.ZS;
-    // kernmat_*_cpp(X2, X, Z2, Z): test side first
-    ck(ctx, launch_assembly(2, s.kind, s.PM, tc, train, B, s.ZS, tv, scratch.d(), nc, nullptr, st,
-                            b0, b1),
-       "cross assembly");
-    *ld = nc;
-    return scratch.d();
-  };
-  op.kdiag = [&](double *dst) {
-    ck(ctx, launch_kdiag(s.kind, test.view(nx), s.ZS, tv, b0, b1, dst, st), "kernel diagonal");
-  };
-  op.kxx = [&](int64_t *ld, DBuf &scratch) -> const double * {
-    alloc(ctx, scratch, (size_t)(nx * nx) * sizeof(double), "alloc K_xx");
-    ck(ctx, launch_assembly(1, s.kind, s.PM, test.view(nx), test.view(nx), B, s.ZS, tv,
-                            scratch.d(), nx, nullptr, st, b0, b1),
-       "symmetric assembly");
-    *ld = nx;
-    return scratch.d();
-  };
-  pred_pipeline(op, nx, marginal, Z_x, ate, theta[0], mu, mean_y, std_y, std_Z, map, ci, var, avg);
-  if (!grp) return;
-  if (grp->prepare) grp->prepare();
-  const int G = grp->G;
-  // like the pipeline: an allocation failure frees the retained scratch and
-  // the pass runs once more (gcov is written only at its end)
-  auto groups_once = [&]() {
+  const int G = grp.G;
   // S = Km_xX^T E (n x G), chunk by chunk from the last one down: that one is
-  // still in the scratch when the pipeline kept it, the others are assembled
-  // again; the order does not depend on which, so neither do the sums
-  std::shared_ptr<PredScratch> ps = std::static_pointer_cast<PredScratch>(ctx->pred_state);
-  if (!ps) {
-    ps = std::make_shared<PredScratch>();
-    ctx->pred_state = ps;
-    last_K = nullptr;
-  }
+  // still in the scratch when the pipeline kept it (a new scratch holds no
+  // buffer, so it never matches), the others are assembled again; the order
+  // does not depend on which, so neither do the sums
   const int64_t chunk = std::min<int64_t>(NXC, nx);
   DBuf dlab, dE, dS, dU, dtmp, dwork, dpart, dR, dQ;
   alloc(ctx, dlab, (size_t)nx * sizeof(int32_t), "alloc labels");
-  upload_bytes(ctx, dlab.p, grp->label, (size_t)nx * sizeof(int32_t), "upload labels");
+  upload_bytes(ctx, dlab.p, grp.label, (size_t)nx * sizeof(int32_t), "upload labels");
   alloc(ctx, dE, (size_t)(nx * G) * sizeof(double), "alloc E");
   ck(ctx, launch_label_matrix(dlab.i(), nx, G, dE.d(), st), "label matrix");
   alloc(ctx, dS, (size_t)(n * G) * sizeof(double), "alloc S");
@@ -360,12 +331,13 @@ void predict_impl(ace_model *m, const double *theta, int64_t nx, const double *X
   for (int64_t c0 = (nx - 1) / chunk * chunk; c0 >= 0; c0 -= chunk) {
     const int64_t nc = std::min<int64_t>(chunk, nx - c0);
     int64_t ldk = nc;
-    const double *Kc = (last_K && last_K == ps->K.d() && last_c0 == c0 && last_nc == nc)
-                           ? last_K
-                           : op.cross(c0, nc, &ldk, ps->K);
+    const double *Kc = (kept.K && kept.K == ps.K.d() && kept.c0 == c0 && kept.nc == nc)
+                           ? kept.K
+                           : op.cross(c0, nc, &ldk, ps.K);
     ck(ctx, launch_gemm_tn(n, G, nc, Kc, ldk, dE.d() + c0, nx, dS.d(), n, !first, dwork.d(), st),
        "S += K^T E");
     first = false;
+    kept.K = nullptr;  // only the first chunk of this loop can be the kept one
   }
   // U = A^-1 S (this rank's share when sharded), Q_inv = S^T U
   symm_resident(m, dS.d(), n, false, G, dU.d(), dtmp);
@@ -375,27 +347,78 @@ void predict_impl(ace_model *m, const double *theta, int64_t nx, const double *X
   // R = Km_xx E without Km_xx, Q_xx = E^T R
   alloc(ctx, dpart, (size_t)(group_sums_parts(nx) * nx * G) * sizeof(double), "alloc R partials");
   alloc(ctx, dR, (size_t)(nx * G) * sizeof(double), "alloc R");
-  ck(ctx, launch_group_sums(s.kind, s.PM, test.view(nx), B, s.ZS, tv, b0, b1, dlab.i(), G,
+  ck(ctx, launch_group_sums(s.kind, s.PM, f.test.view(nx), s.B, s.ZS, f.tv, f.b0, f.b1, dlab.i(), G,
                             dpart.d(), dR.d(), st),
      "grouped kernel sums");
   ck(ctx, launch_gemm_tn(G, G, nx, dE.d(), nx, dR.d(), nx, Qxx, G, false, dwork.d(), st), "E^T R");
   std::vector<double> q((size_t)(2 * G * G));
   download(ctx, q.data(), dQ.d(), q.size(), "download group sums");
   sync(ctx);
-  for (int e = 0; e < G * G; ++e) grp->gcov[e] = q[(size_t)(G * G + e)] - q[(size_t)e];
+  for (int e = 0; e < G * G; ++e) grp.gcov[e] = q[(size_t)(G * G + e)] - q[(size_t)e];
+}
+
+// ace_model_predict (rq.marginal = false) / ace_model_predict_marginal: the
+// model's resident inverse, K_xX assembled from the resident training side;
+// rq's sigma and mu come from theta.  grp: the grouped pass after it.
+void predict_impl(ace_model *m, const double *theta, const double *X2, const double *Zt,
+                  PredReq rq, const GroupReq *grp = nullptr) {
+  ace_ctx *ctx = m->ctx;
+  hipStream_t st = ctx->stream;
+  const Shape &s = m->s;
+  const int64_t n = m->n, nx = rq.nx;
+  rq.sigma = theta[0];
+  rq.mu = theta[1];
+  const PredFront f(m, theta, nx, X2, Zt, rq.marginal, FRONT_W | FRONT_TRI);
+  PredOps op;
+  op.ctx = ctx;
+  op.n = n;
+  op.w = f.dw.d();
+  op.symm = [&](const double *V, int64_t ldv, int64_t k, double *out, DBuf &tmp) {
+    symm_resident(m, V, ldv, true, k, out, tmp);
   };
-  try {
-    groups_once();
-  } catch (const Fail &f) {
-    if (f.code != ACE_ERR_OOM) throw;
-    (void)hipGetLastError();
-    sync(ctx);  // the failed pass's launches may still read the scratch
-    release_pred_state(ctx);
-    ctx->sweep_pool.clear();
-    groups_once();
+  if (f.tri) {  // -A^-1 is stored: scale -1
+    op.sdiag = f.ddiag.d();
+    op.trmm = [&](const double *V, int64_t ldv, int64_t k, double *out) {
+      ck(ctx, launch_trmm_lower(m->sw.A.d(), m->naug, n, V, ldv, k, -1.0, out, n, st), "trmm");
+    };
+    op.symv = [&](const double *V, int64_t ldv, int64_t k, double *out, DBuf &tmp) {
+      symm_resident(m, V, ldv, false, k, out, tmp);
+    };
+    op.ainv_w = [&](double *dst) { f.ainv_w(dst); };
   }
-  if (auto ps = std::static_pointer_cast<PredScratch>(ctx->pred_state))
-    if (ps->K.bytes + ps->T.bytes + ps->Kxx.bytes > PRED_KEEP_BYTES) release_pred_state(ctx);
+  if (m->shard) op.allreduce = [&](double *b, int64_t c) { shard_allreduce_sum(m->shard, b, c); };
+  KeptChunk kept;
+  op.cross = [&](int64_t c0, int64_t nc, int64_t *ld, DBuf &scratch) -> const double * {
+    alloc(ctx, scratch, (size_t)(nc * n) * sizeof(double), "alloc K_xX");
+    kept.c0 = c0;
+    kept.nc = nc;
+    kept.K = scratch.d();
+    // kernmat_*_cpp(X2, X, Z2, Z): test side first
+    ck(ctx, launch_assembly(2, s.kind, s.PM, chunk_view(f.test, s, c0, nc), f.train, s.B, s.ZS,
+                            f.tv, scratch.d(), nc, nullptr, st, f.b0, f.b1),
+       "cross assembly");
+    *ld = nc;
+    return scratch.d();
+  };
+  op.kdiag = [&](double *dst) {
+    ck(ctx, launch_kdiag(s.kind, f.test.view(nx), s.ZS, f.tv, f.b0, f.b1, dst, st),
+       "kernel diagonal");
+  };
+  op.kxx = [&](int64_t *ld, DBuf &scratch) -> const double * {
+    alloc(ctx, scratch, (size_t)(nx * nx) * sizeof(double), "alloc K_xx");
+    ck(ctx, launch_assembly(1, s.kind, s.PM, f.test.view(nx), f.test.view(nx), s.B, s.ZS, f.tv,
+                            scratch.d(), nx, nullptr, st, f.b0, f.b1),
+       "symmetric assembly");
+    *ld = nx;
+    return scratch.d();
+  };
+  pred_pipeline(op, rq);
+  if (!grp) return;
+  if (grp->prepare) grp->prepare();
+  // (gcov is written only at the pass's end; a second run starts from what
+  // the pipeline left, which a new scratch never matches)
+  const KeptChunk after_pipeline = kept;
+  with_pred_scratch(ctx, [&](PredScratch &ps) { group_pass(f, op, nx, *grp, after_pipeline, ps); });
 }
 
 // ACE_COEF_CHUNK: test points per chunk of the coefficient pass (default and
@@ -415,30 +438,21 @@ void slice_assembly(ace_ctx *ctx, const Shape &s, PairSide tc, PairSide train, T
      "slice assembly");
 }
 
-// ace_model_coef_cross: the cube Kc (nx x n x B), chunked like the pass
+// ace_model_coef_cross: the cube Kc (nx x n x B), chunked like the pass; it
+// needs neither w nor an inverse
 void coef_cross(ace_model *m, const double *theta, int64_t nx, const double *X2, double *out) {
   ace_ctx *ctx = m->ctx;
   const Shape &s = m->s;
   const int64_t n = m->n;
   const int B = s.B;
-  std::vector<double> tab = make_tab(theta, s, false);
-  DBuf dtab, dK;
-  upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
-  const TabView tv = tab_view(dtab, s);
-  SideBufs test;
-  std::vector<double> ones((size_t)(nx * s.ZS), 1.0);
-  upload_side(ctx, test, s, X2, ones.data(), nx, nx);
-  const PairSide train = m->shard ? shard_train_side(m->shard) : m->side.view(n);
+  const PredFront f(m, theta, nx, X2, nullptr, false, 0);
+  DBuf dK;
   const int64_t chunk = std::min<int64_t>(coef_chunk(B), nx);
   alloc(ctx, dK, (size_t)(chunk * B * n) * sizeof(double), "alloc Kc");
   std::vector<double> h((size_t)(chunk * B * n));
   for (int64_t c0 = 0; c0 < nx; c0 += chunk) {
     const int64_t nc = std::min<int64_t>(chunk, nx - c0), ldk = nc * B;
-    PairSide tc = test.view(nc);
-    tc.X += c0 * s.PM;
-    tc.Z += c0 * s.ZS;
-    tc.LZ += c0 * s.ZS;
-    slice_assembly(ctx, s, tc, train, tv, dK.d());
+    slice_assembly(ctx, s, chunk_view(f.test, s, c0, nc), f.train, f.tv, dK.d());
     download(ctx, h.data(), dK.d(), (size_t)(ldk * n), "download Kc");
     sync(ctx);
     // (q: the device's training point, the caller's perm[q] when the model
@@ -459,63 +473,37 @@ void coef_cross(ace_model *m, const double *theta, int64_t nx, const double *X2,
 // the inverse as predict_impl takes it (strictly lower triangle on one GPU,
 // the full symmetric product otherwise), and the B x B Gram sums per point
 // (k_coef_gram).  Outputs are written only at the end.
-void coef_once(ace_model *m, const double *theta, int64_t nx, const double *X2, double *mean,
-               double *P) {
+void coef_pass(ace_model *m, const double *theta, int64_t nx, const double *X2, double *mean,
+               double *P, PredScratch &ps) {
   ace_ctx *ctx = m->ctx;
   hipStream_t st = ctx->stream;
   const Shape &s = m->s;
   const int64_t n = m->n;
   const int B = s.B;
-  const double mu = theta[1];
-  std::vector<double> tab = make_tab(theta, s, false);
-  DBuf dtab, dw, dsv, ddiag, dscal, dtmp, dpart, dres;
-  upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
-  const TabView tv = tab_view(dtab, s);
-  // (the slice kernel does not read the test side's basis; upload_side wants one)
-  SideBufs test;
-  std::vector<double> ones((size_t)(nx * s.ZS), 1.0);
-  upload_side(ctx, test, s, X2, ones.data(), nx, nx);
-  const PairSide train = m->shard ? shard_train_side(m->shard) : m->side.view(n);
-  alloc(ctx, dw, (size_t)n * sizeof(double), "alloc w");
-  ck(ctx, launch_center(m->shard ? shard_train_y(m->shard) : m->y.d(), n, mu, dw.d(), st),
-     "center y");
-  const bool tri = !m->shard && pred_tri();
-  if (tri) {  // -A^-1 is stored: scale -1
-    alloc(ctx, ddiag, (size_t)n * sizeof(double), "alloc diag");
-    ck(ctx, launch_diag_scaled(m->sw.A.d(), m->naug, n, -1.0, ddiag.d(), st), "diag");
+  const PredFront f(m, theta, nx, X2, nullptr, false, FRONT_W | FRONT_TRI);
+  DBuf dsv, dtmp, dpart, dres;
+  if (f.tri) {
     alloc(ctx, dsv, (size_t)n * sizeof(double), "alloc s");
-    alloc(ctx, dscal, 8 * sizeof(double), "alloc scalars");
-    ck(ctx, launch_alpha_from_aug(m->sw.A.d(), m->naug, m->npad, n, mu, 0, dsv.d(), dscal.d(), st,
-                                  nullptr),
-       "A^-1 w");
-  }
-  std::shared_ptr<PredScratch> ps = std::static_pointer_cast<PredScratch>(ctx->pred_state);
-  if (!ps) {
-    ps = std::make_shared<PredScratch>();
-    ctx->pred_state = ps;
+    f.ainv_w(dsv.d());
   }
   const int64_t chunk = std::min<int64_t>(coef_chunk(B), nx);
   const int64_t per = (int64_t)B * (B + 1);  // results per point
-  alloc(ctx, ps->K, (size_t)(chunk * B * n) * sizeof(double), "alloc Kc");
-  alloc(ctx, ps->T, (size_t)(chunk * B * n) * sizeof(double), "alloc T");
+  alloc(ctx, ps.K, (size_t)(chunk * B * n) * sizeof(double), "alloc Kc");
+  alloc(ctx, ps.T, (size_t)(chunk * B * n) * sizeof(double), "alloc T");
   alloc(ctx, dpart, (size_t)coef_gram_work(n, chunk, B) * sizeof(double), "alloc Gram partials");
   alloc(ctx, dres, (size_t)(nx * per) * sizeof(double), "alloc Gram sums");
   for (int64_t c0 = 0; c0 < nx; c0 += chunk) {
     const int64_t nc = std::min<int64_t>(chunk, nx - c0), ldk = nc * B;
-    PairSide tc = test.view(nc);
-    tc.X += c0 * s.PM;
-    tc.Z += c0 * s.ZS;
-    tc.LZ += c0 * s.ZS;
-    double *Kc = ps->K.d(), *T = ps->T.d(), *res = dres.d() + c0 * per;
-    slice_assembly(ctx, s, tc, train, tv, Kc);
-    if (tri) {
+    double *Kc = ps.K.d(), *T = ps.T.d(), *res = dres.d() + c0 * per;
+    slice_assembly(ctx, s, chunk_view(f.test, s, c0, nc), f.train, f.tv, Kc);
+    if (f.tri) {
       ck(ctx, launch_trmm_lower(m->sw.A.d(), m->naug, n, Kc, ldk, ldk, -1.0, T, n, st), "trmm");
-      ck(ctx, launch_coef_gram(true, Kc, ldk, T, n, n, nc, B, dsv.d(), ddiag.d(), dpart.d(), res,
+      ck(ctx, launch_coef_gram(true, Kc, ldk, T, n, n, nc, B, dsv.d(), f.ddiag.d(), dpart.d(), res,
                                st),
          "coefficient Gram");
     } else {
       symm_resident(m, Kc, ldk, true, ldk, T, dtmp);
-      ck(ctx, launch_coef_gram(false, Kc, ldk, T, n, n, nc, B, dw.d(), nullptr, dpart.d(), res,
+      ck(ctx, launch_coef_gram(false, Kc, ldk, T, n, n, nc, B, f.dw.d(), nullptr, dpart.d(), res,
                                st),
          "coefficient Gram");
       if (m->shard) shard_allreduce_sum(m->shard, res, nc * per);
@@ -532,23 +520,6 @@ void coef_once(ace_model *m, const double *theta, int64_t nx, const double *X2, 
   }
 }
 
-void coef_impl(ace_model *m, const double *theta, int64_t nx, const double *X2, double *mean,
-               double *P) {
-  ace_ctx *ctx = m->ctx;
-  try {
-    coef_once(m, theta, nx, X2, mean, P);
-  } catch (const Fail &f) {
-    if (f.code != ACE_ERR_OOM) throw;
-    (void)hipGetLastError();
-    sync(ctx);  // the failed pass's launches may still read the scratch
-    release_pred_state(ctx);
-    ctx->sweep_pool.clear();
-    coef_once(m, theta, nx, X2, mean, P);
-  }
-  if (auto ps = std::static_pointer_cast<PredScratch>(ctx->pred_state))
-    if (ps->K.bytes + ps->T.bytes + ps->Kxx.bytes > PRED_KEEP_BYTES) release_pred_state(ctx);
-}
-
 // cov_c = diag(exp(lambda_b)) - P_c in place: the prior of g(x_c) is
 // diagonal, k_b(x, x) = exp(lambda_b), lambda_b = theta[2 + b] (make_tab)
 void coef_cov_from_gram(const double *theta, int64_t nx, int B, double *cov) {
@@ -558,6 +529,14 @@ void coef_cov_from_gram(const double *theta, int64_t nx, int B, double *cov) {
       const double prior = b == b2 ? std::exp(theta[2 + b]) : 0.0;
       for (int64_t c = 0; c < nx; ++c) e[c] = prior - e[c];
     }
+}
+
+// mean (nx x B) and cov (nx x B x B) of the coefficient functions
+void coef_posterior(ace_model *m, const double *theta, int64_t nx, const double *X2, double *mean,
+                    double *cov) {
+  with_pred_scratch(m->ctx,
+                    [&](PredScratch &ps) { coef_pass(m, theta, nx, X2, mean, cov, ps); });
+  coef_cov_from_gram(theta, nx, m->s.B, cov);
 }
 
 // ace_model_predict_joint: the joint posterior at nx <= JOINT_NX test points
@@ -580,50 +559,36 @@ struct JointReq {
   int64_t *info = nullptr;
 };
 
-void joint_once(ace_model *m, const double *theta, int64_t nx, const double *X2, const double *Zt,
-                const JointReq &rq) {
+void joint_pass(ace_model *m, const double *theta, int64_t nx, const double *X2, const double *Zt,
+                const JointReq &rq, PredScratch &ps) {
   ace_ctx *ctx = m->ctx;
   hipStream_t st = ctx->stream;
   const Shape &s = m->s;
   const int64_t n = m->n;
   const int B = s.B;
   const bool marginal = rq.marginal;
-  const int b0 = marginal && B > 1 ? 1 : 0;  // src/pred_cpp.cpp:55-67
-  const int b1 = marginal ? (B > 1 ? B : 1) : B;
   const double mu = theta[1];
   const bool factor = rq.L || rq.S > 0;
-  std::vector<double> tab = make_tab(theta, s, false);  // kernels at the caller's theta (Q6)
-  DBuf dtab, dw, dad, dtmp, dC, dL, dxi, dD, dmap, dflag;
-  upload(ctx, dtab, tab.data(), tab.size(), "upload tables");
-  const TabView tv = tab_view(dtab, s);
-  SideBufs test;
-  upload_side(ctx, test, s, X2, Zt, nx, nx);
-  const PairSide train = m->side.view(n);
-  alloc(ctx, dw, (size_t)n * sizeof(double), "alloc w");
-  ck(ctx, launch_center(m->y.d(), n, mu, dw.d(), st), "center y");
-  std::shared_ptr<PredScratch> ps = std::static_pointer_cast<PredScratch>(ctx->pred_state);
-  if (!ps) {
-    ps = std::make_shared<PredScratch>();
-    ctx->pred_state = ps;
-  }
-  alloc(ctx, ps->K, (size_t)(nx * n) * sizeof(double), "alloc K_xX");
-  alloc(ctx, ps->T, (size_t)(nx * n) * sizeof(double), "alloc T");
-  alloc(ctx, ps->Kxx, (size_t)(nx * nx) * sizeof(double), "alloc K_xx");
+  const PredFront f(m, theta, nx, X2, Zt, marginal, FRONT_W);
+  DBuf dad, dtmp, dC, dL, dxi, dD, dmap, dflag;
+  alloc(ctx, ps.K, (size_t)(nx * n) * sizeof(double), "alloc K_xX");
+  alloc(ctx, ps.T, (size_t)(nx * n) * sizeof(double), "alloc T");
+  alloc(ctx, ps.Kxx, (size_t)(nx * nx) * sizeof(double), "alloc K_xx");
   alloc(ctx, dC, (size_t)(nx * nx) * sizeof(double), "alloc C");
   alloc(ctx, dad, (size_t)(2 * nx) * sizeof(double), "alloc sums");
   // kernmat_*_cpp(X2, X, Z2, Z): test side first
-  ck(ctx, launch_assembly(2, s.kind, s.PM, test.view(nx), train, B, s.ZS, tv, ps->K.d(), nx,
-                          nullptr, st, b0, b1),
+  ck(ctx, launch_assembly(2, s.kind, s.PM, f.test.view(nx), f.train, B, s.ZS, f.tv, ps.K.d(), nx,
+                          nullptr, st, f.b0, f.b1),
      "cross assembly");
-  symm_resident(m, ps->K.d(), nx, true, nx, ps->T.d(), dtmp);
-  ck(ctx, launch_pred_cols(ps->T.d(), n, ps->K.d(), nx, n, nx, dw.d(), dad.d(), dad.d() + nx, st),
+  symm_resident(m, ps.K.d(), nx, true, nx, ps.T.d(), dtmp);
+  ck(ctx, launch_pred_cols(ps.T.d(), n, ps.K.d(), nx, n, nx, f.dw.d(), dad.d(), dad.d() + nx, st),
      "pred sums");
-  ck(ctx, launch_assembly(1, s.kind, s.PM, test.view(nx), test.view(nx), B, s.ZS, tv,
-                          ps->Kxx.d(), nx, nullptr, st, b0, b1),
+  ck(ctx, launch_assembly(1, s.kind, s.PM, f.test.view(nx), f.test.view(nx), B, s.ZS, f.tv,
+                          ps.Kxx.d(), nx, nullptr, st, f.b0, f.b1),
      "symmetric assembly");
   const double sc = marginal ? rq.std_y / rq.std_Z : rq.std_y;
   const double noise = (!marginal && rq.noise) ? std::exp(theta[0]) : 0.0;
-  ck(ctx, launch_post_cov(ps->K.d(), nx, ps->T.d(), n, n, ps->Kxx.d(), nx, nx, noise, sc * sc,
+  ck(ctx, launch_post_cov(ps.K.d(), nx, ps.T.d(), n, n, ps.Kxx.d(), nx, nx, noise, sc * sc,
                           dC.d(), nx, st),
      "posterior covariance");
   if (factor) {
@@ -668,23 +633,6 @@ void joint_once(ace_model *m, const double *theta, int64_t nx, const double *X2,
   *rq.info = flag;
 }
 
-void joint_impl(ace_model *m, const double *theta, int64_t nx, const double *X2, const double *Zt,
-                const JointReq &rq) {
-  ace_ctx *ctx = m->ctx;
-  try {
-    joint_once(m, theta, nx, X2, Zt, rq);
-  } catch (const Fail &f) {
-    if (f.code != ACE_ERR_OOM) throw;
-    (void)hipGetLastError();
-    sync(ctx);  // the failed call's launches may still read the scratch
-    release_pred_state(ctx);
-    ctx->sweep_pool.clear();
-    joint_once(m, theta, nx, X2, Zt, rq);
-  }
-  if (auto ps = std::static_pointer_cast<PredScratch>(ctx->pred_state))
-    if (ps->K.bytes + ps->T.bytes + ps->Kxx.bytes > PRED_KEEP_BYTES) release_pred_state(ctx);
-}
-
 void unsupported(ace_ctx *ctx, bool ok, const char *msg) {
   if (ok) return;
   ctx->err = msg;
@@ -705,7 +653,42 @@ void group_sums_host(int64_t nx, int G, const int32_t *label, const double *map,
     }
 }
 
+// Every ace_model_* entry point below, in this order: the device, the
+// arguments all of them need (ok), the entry point's own checks (more), then
+// the model's state -- data, and a resident inverse unless need_inverse is off.
+void enter(ace_model *m, bool ok, const std::function<void()> &more = {},
+           bool need_inverse = true) {
+  ace_ctx *ctx = m->ctx;
+  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+  arg(ctx, ok, "bad shape / null argument");
+  if (more) more();
+  arg(ctx, m->has_data, "ace_model_set_data() not called");
+  if (need_inverse)
+    arg(ctx, m->has_inverse, "no resident inverse: call ace_model_para_update() first");
+}
+
+// the arguments of the four pipeline entry points
+bool pred_args(const ace_model *m, int64_t nx, const double *theta, const double *X2,
+               const double *Z2, const double *map, const double *ci, const double *var) {
+  return nx >= 1 && theta && map && ci && var && (m->s.p == 0 || X2) && (m->s.B == 1 || Z2);
+}
+
+PredReq marginal_req(int64_t nx, double std_y, double std_Z, double *map, double *ci, double *var) {
+  PredReq rq(nx, std_y, map, ci, var);
+  rq.marginal = true;
+  rq.std_Z = std_Z;
+  return rq;
+}
+
 }  // namespace
+
+// The device prediction pipeline (pred_cpp / pred_marginal_cpp semantics)
+// over abstract operands -- the device model's resident inverse here, and the
+// device-matrix handles of the R6-faithful path in ace_dmat.cpp -- in the
+// context's retained scratch (with_pred_scratch).
+void pred_pipeline(const PredOps &op, const PredReq &rq) {
+  with_pred_scratch(op.ctx, [&](PredScratch &ps) { pipeline_body(op, rq, ps); });
+}
 
 extern "C" {
 
@@ -713,9 +696,7 @@ int ace_model_apply_inverse(ace_model *m, int64_t k, const double *V, double *ou
   if (!m) return ACE_ERR_ARG;
   ace_ctx *ctx = m->ctx;
   ACE_TRY
-  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-  arg(ctx, k >= 1 && V && out, "bad shape / null argument");
-  require_inverse(m);
+  enter(m, k >= 1 && V && out);
   const int64_t n = m->n;
   DBuf dV, dout, dtmp;
   // a model that holds its points in the zero-pattern order (ace_model::perm):
@@ -746,11 +727,10 @@ int ace_model_predict(ace_model *m, const double *theta, int64_t nx, const doubl
   if (!m) return ACE_ERR_ARG;
   ace_ctx *ctx = m->ctx;
   ACE_TRY
-  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-  arg(ctx, nx >= 1 && theta && map && ci && var && (m->s.p == 0 || X2) && (m->s.B == 1 || Z2),
-      "bad shape / null argument");
-  require_inverse(m);
-  predict_impl(m, theta, nx, X2, Z2, false, nullptr, 0, mean_y, std_y, 1.0, map, ci, var, nullptr);
+  enter(m, pred_args(m, nx, theta, X2, Z2, map, ci, var));
+  PredReq rq(nx, std_y, map, ci, var);
+  rq.mean_y = mean_y;
+  predict_impl(m, theta, X2, Z2, rq);
   return ACE_OK;
   ACE_CATCH
 }
@@ -762,13 +742,14 @@ int ace_model_predict_marginal(ace_model *m, const double *theta, int64_t nx, co
   if (!m) return ACE_ERR_ARG;
   ace_ctx *ctx = m->ctx;
   ACE_TRY
-  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-  arg(ctx, nx >= 1 && theta && map && ci && var && (m->s.p == 0 || X2) && (m->s.B == 1 || dZ2),
-      "bad shape / null argument");
-  arg(ctx, !calculate_ate || (Z_x && avg), "calculate_ate needs Z_x and avg");
-  require_inverse(m);
-  predict_impl(m, theta, nx, X2, dZ2, true, Z_x, calculate_ate, 0.0, std_y, std_Z, map, ci, var,
-               avg);
+  enter(m, pred_args(m, nx, theta, X2, dZ2, map, ci, var), [&] {
+    arg(ctx, !calculate_ate || (Z_x && avg), "calculate_ate needs Z_x and avg");
+  });
+  PredReq rq = marginal_req(nx, std_y, std_Z, map, ci, var);
+  rq.Z_x = Z_x;
+  rq.ate = calculate_ate;
+  rq.avg = avg;
+  predict_impl(m, theta, X2, dZ2, rq);
   return ACE_OK;
   ACE_CATCH
 }
@@ -781,19 +762,14 @@ int ace_model_predict_marginal_groups(ace_model *m, const double *theta, int64_t
   if (!m) return ACE_ERR_ARG;
   ace_ctx *ctx = m->ctx;
   ACE_TRY
-  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-  arg(ctx, nx >= 1 && theta && map && ci && var && (m->s.p == 0 || X2) && (m->s.B == 1 || dZ2),
-      "bad shape / null argument");
-  arg(ctx, label && gsum && gcount && gcov, "null argument");
-  arg(ctx, G >= 1 && G <= 64, "G must be in [1, 64]");
-  for (int64_t i = 0; i < nx; ++i) arg(ctx, label[i] >= -1 && label[i] < G, "label outside [-1, G)");
-  require_inverse(m);
-  GroupReq grp;
-  grp.G = G;
-  grp.label = label;
-  grp.gcov = gcov;
-  predict_impl(m, theta, nx, X2, dZ2, true, nullptr, 0, 0.0, std_y, std_Z, map, ci, var, nullptr,
-               &grp);
+  enter(m, pred_args(m, nx, theta, X2, dZ2, map, ci, var), [&] {
+    arg(ctx, label && gsum && gcount && gcov, "null argument");
+    arg(ctx, G >= 1 && G <= 64, "G must be in [1, 64]");
+    for (int64_t i = 0; i < nx; ++i)
+      arg(ctx, label[i] >= -1 && label[i] < G, "label outside [-1, G)");
+  });
+  const GroupReq grp{G, label, gcov, nullptr};
+  predict_impl(m, theta, X2, dZ2, marginal_req(nx, std_y, std_Z, map, ci, var), &grp);
   group_sums_host(nx, G, label, map, gsum, gcount);
   return ACE_OK;
   ACE_CATCH
@@ -806,21 +782,16 @@ int ace_model_robust_treatment(ace_model *m, const double *theta, int64_t nx, co
   if (!m) return ACE_ERR_ARG;
   ace_ctx *ctx = m->ctx;
   ACE_TRY
-  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-  arg(ctx, nx >= 1 && theta && map && ci && var && (m->s.p == 0 || X2) && (m->s.B == 1 || dZ2),
-      "bad shape / null argument");
-  arg(ctx, Z_x && thresholds && level && avg && counts, "null argument");
-  arg(ctx, n_steps >= 1 && n_steps <= 31, "n_steps must be in [1, 31]");
-  for (int64_t i = 0; i < nx; ++i)
-    arg(ctx, Z_x[i] == 0.0 || Z_x[i] == 1.0, "Z_x must be 0 or 1 (binary treatment)");
-  require_inverse(m);
+  enter(m, pred_args(m, nx, theta, X2, dZ2, map, ci, var), [&] {
+    arg(ctx, Z_x && thresholds && level && avg && counts, "null argument");
+    arg(ctx, n_steps >= 1 && n_steps <= 31, "n_steps must be in [1, 31]");
+    for (int64_t i = 0; i < nx; ++i)
+      arg(ctx, Z_x[i] == 0.0 || Z_x[i] == 1.0, "Z_x must be 0 or 1 (binary treatment)");
+  });
   const int T = n_steps + 1, G = 2 * T;
   std::vector<int32_t> label((size_t)nx);
   std::vector<double> gcov((size_t)(G * G));
-  GroupReq grp;
-  grp.G = G;
-  grp.label = label.data();
-  grp.gcov = gcov.data();
+  GroupReq grp{G, label.data(), gcov.data(), nullptr};
   grp.prepare = [&]() {
     const int st = ace_robust_levels(nx, var, n_steps, thresholds, level);
     if (st != ACE_OK) {
@@ -829,8 +800,7 @@ int ace_model_robust_treatment(ace_model *m, const double *theta, int64_t nx, co
     }
     for (int64_t i = 0; i < nx; ++i) label[(size_t)i] = 2 * level[i] + (Z_x[i] == 1.0 ? 1 : 0);
   };
-  predict_impl(m, theta, nx, X2, dZ2, true, nullptr, 0, 0.0, std_y, std_Z, map, ci, var, nullptr,
-               &grp);
+  predict_impl(m, theta, X2, dZ2, marginal_req(nx, std_y, std_Z, map, ci, var), &grp);
   std::vector<double> gsum((size_t)G);
   std::vector<int64_t> gcount((size_t)G);
   group_sums_host(nx, G, label.data(), map, gsum.data(), gcount.data());
@@ -868,11 +838,8 @@ int ace_model_coef_posterior(ace_model *m, const double *theta, int64_t nx, cons
   if (!m) return ACE_ERR_ARG;
   ace_ctx *ctx = m->ctx;
   ACE_TRY
-  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-  arg(ctx, nx >= 1 && theta && mean && cov && (m->s.p == 0 || X2), "bad shape / null argument");
-  require_inverse(m);
-  coef_impl(m, theta, nx, X2, mean, cov);
-  coef_cov_from_gram(theta, nx, m->s.B, cov);
+  enter(m, nx >= 1 && theta && mean && cov && (m->s.p == 0 || X2));
+  coef_posterior(m, theta, nx, X2, mean, cov);
   return ACE_OK;
   ACE_CATCH
 }
@@ -882,9 +849,7 @@ int ace_model_coef_cross(ace_model *m, const double *theta, int64_t nx, const do
   if (!m) return ACE_ERR_ARG;
   ace_ctx *ctx = m->ctx;
   ACE_TRY
-  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-  arg(ctx, nx >= 1 && theta && Kc && (m->s.p == 0 || X2), "bad shape / null argument");
-  arg(ctx, m->has_data, "ace_model_set_data() not called");
+  enter(m, nx >= 1 && theta && Kc && (m->s.p == 0 || X2), {}, false);
   coef_cross(m, theta, nx, X2, Kc);
   return ACE_OK;
   ACE_CATCH
@@ -896,14 +861,10 @@ int ace_model_predict_surface(ace_model *m, const double *theta, int64_t nx, con
   if (!m) return ACE_ERR_ARG;
   ace_ctx *ctx = m->ctx;
   ACE_TRY
-  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
   const int B = m->s.B;
-  arg(ctx, nx >= 1 && nz >= 1 && theta && map && ci && var && (m->s.p == 0 || X2) && (B == 1 || Zb),
-      "bad shape / null argument");
-  require_inverse(m);
+  enter(m, nx >= 1 && nz >= 1 && theta && map && ci && var && (m->s.p == 0 || X2) && (B == 1 || Zb));
   std::vector<double> mean((size_t)(nx * B)), cov((size_t)(nx * B * B));
-  coef_impl(m, theta, nx, X2, mean.data(), cov.data());
-  coef_cov_from_gram(theta, nx, B, cov.data());
+  coef_posterior(m, theta, nx, X2, mean.data(), cov.data());
   // beta = (1, B(z)); marginal: (0, dB(z)), (1) for B == 1 (src/pred_cpp.cpp:55-67)
   std::vector<double> W((size_t)(nz * B));
   for (int64_t j = 0; j < nz; ++j) {
@@ -926,15 +887,13 @@ int ace_model_predict_joint(ace_model *m, const double *theta, int64_t nx, const
   if (!m) return ACE_ERR_ARG;
   ace_ctx *ctx = m->ctx;
   ACE_TRY
-  ck(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-  arg(ctx, nx >= 1 && theta && map && info && (m->s.p == 0 || X2) && (m->s.B == 1 || Zt),
-      "bad shape / null argument");
-  arg(ctx, S >= 0 && (S == 0 || (xi && draws)), "S > 0 needs xi and draws");
-  arg(ctx, jitter >= 0.0 && std::isfinite(jitter), "jitter must be finite and >= 0");
-  unsupported(ctx, !m->shard, "predict_joint: sharded models are not supported (single GPU only)");
-  unsupported(ctx, nx <= JOINT_NX, "predict_joint: nx <= 8192 (one chunk; C is 512 MB there)");
-  unsupported(ctx, S <= JOINT_S, "predict_joint: S <= 4096 draws per call");
-  require_inverse(m);
+  enter(m, nx >= 1 && theta && map && info && (m->s.p == 0 || X2) && (m->s.B == 1 || Zt), [&] {
+    arg(ctx, S >= 0 && (S == 0 || (xi && draws)), "S > 0 needs xi and draws");
+    arg(ctx, jitter >= 0.0 && std::isfinite(jitter), "jitter must be finite and >= 0");
+    unsupported(ctx, !m->shard, "predict_joint: sharded models are not supported (single GPU only)");
+    unsupported(ctx, nx <= JOINT_NX, "predict_joint: nx <= 8192 (one chunk; C is 512 MB there)");
+    unsupported(ctx, S <= JOINT_S, "predict_joint: S <= 4096 draws per call");
+  });
   JointReq rq;
   rq.marginal = marginal != 0;
   rq.noise = noise != 0;
@@ -949,7 +908,7 @@ int ace_model_predict_joint(ace_model *m, const double *theta, int64_t nx, const
   rq.L = L;
   rq.draws = draws;
   rq.info = info;
-  joint_impl(m, theta, nx, X2, Zt, rq);
+  with_pred_scratch(ctx, [&](PredScratch &ps) { joint_pass(m, theta, nx, X2, Zt, rq, ps); });
   return ACE_OK;
   ACE_CATCH
 }

@@ -12,7 +12,13 @@ para_update / train_stats, the device training loop under each optimizer with
 the clip firing and off, host-buffer and handle grad / stats, the batched
 para_update / train / predict / predict_marginal with ATE), both kernels,
 compared bit for bit per output at fixed small shapes (n and kernel are not
-read)."""
+read), or predict: in the same style, every output of the prediction host
+paths (csrc/ace_predict.cpp) and of the handle path's pred_cpp /
+pred_marginal_cpp, both kernels at n = 333, p = 2, B = 3 and n = 700, p = 20,
+B = 10 with 257 test points (8269 for the two-chunk cases), one simulated
+sharded model, and the coefficient paths once more in a process with
+ACE_COEF_CHUNK=7; run it as is and with ACE_PRED_TRI=0 in the environment
+(both builds then take the full symmetric product)."""
 import os
 import subprocess
 import sys
@@ -170,7 +176,101 @@ def run():
 run()
 np.savez({out!r}, **out)
 """
-SNIPS = {"para_update": SNIP, "cross": SNIP_CROSS, "formulas": SNIP_FORMULAS}
+# Every output of every entry point that goes through csrc/ace_predict.cpp's
+# host paths, and the handle path's two callers of its pipeline.  The part
+# named by CMP_PART runs: "all", or "coef7" -- the coefficient paths alone, in
+# a process started with ACE_COEF_CHUNK=7 so that their chunk loops run (the
+# library reads the switch once per process).
+SNIP_PREDICT = """
+import os, sys, numpy as np
+sys.path.insert(0, {root!r})
+import additivecausalexpansion_amd as A
+from additivecausalexpansion_amd import native as N
+from additivecausalexpansion_amd.synthetic import make_problem
+out = {{}}
+part = os.environ.get("CMP_PART", "all")
+NX, NX2, G = 257, 8192 + 77, 17
+def run():
+    def put(name, res, keys=None):
+        if not isinstance(res, dict):
+            res = {{"": res}}
+        for k in sorted(keys or res):
+            v = res[k]
+            if isinstance(v, dict):  # ate / att / atu
+                v = np.concatenate([np.ravel(v[q]) for q in ("map", "ci", "var")])
+            out[part + "/" + name + ("/" + k if k else "")] = np.ravel(np.asarray(v, dtype=np.float64))
+    def points(nx, p, B, seed):
+        _, X2, Z2, _, _ = make_problem(nx, p, B, seed=seed)
+        Z2 = np.asfortranarray(Z2)
+        return X2, Z2, np.asfortranarray(Z2 * 0.7 + 0.1), (np.arange(nx) % 3 == 0).astype(np.float64)
+    def fitted(kernel, n, p, B, **kw):
+        y, X, Z, th, sy = make_problem(n, p, B, seed=5)
+        m = A.DeviceModel(kernel, n, p, B, **kw)
+        m.set_data(y, X, Z, sy)
+        m.para_update(2, th.copy())   # the resident inverse is at th
+        mix = th + 0.02               # kernels at another theta (Q6)
+        mix[1] = 0.13
+        return m, y, X, Z, th, mix, sy
+    for kernel in ("SE", "Matern32"):
+        for n, p, B in ((333, 2, 3), (700, 20, 10)):
+            tag = kernel + "/n" + str(n)
+            m, y, X, Z, th, mix, sy = fitted(kernel, n, p, B)
+            X2, Z2, dZ2, zx = points(NX, p, B, 6)
+            put(tag + "/coef_posterior", m.coef_posterior(mix, X2))
+            put(tag + "/coef_cross", m.coef_cross(mix, X2))
+            for marg in (False, True):
+                put(tag + "/surface/marginal" + str(int(marg)),
+                    m.predict_surface(mix, X2, (dZ2 if marg else Z2)[:9], marg, 0.3, 1.7, 0.8))
+            if part == "coef7":
+                m.close()
+                continue
+            put(tag + "/predict", m.predict(mix, X2, Z2, 0.3, 1.7))
+            put(tag + "/marginal/ate0", m.predict_marginal(mix, X2, dZ2, None, 1.7, 0.8, False))
+            put(tag + "/marginal/ate1", m.predict_marginal(th, X2, dZ2, zx, 1.7, 0.8, True))
+            lab = (np.arange(NX) % G).astype(np.int32)
+            lab[5::13] = -1
+            put(tag + "/groups", m.predict_marginal_groups(mix, X2, dZ2, 1.7, 0.8, G, lab))
+            put(tag + "/robust", m.robust_treatment(th, X2, dZ2, zx, 1.7, 0.8, n_steps=3),
+                ("map", "ci", "var", "thresholds", "level", "avg", "counts"))
+            xi = np.asfortranarray(np.random.default_rng(7).standard_normal((NX, 5)))
+            for marg in (False, True):
+                put(tag + "/joint/marginal" + str(int(marg)),
+                    m.predict_joint(th, X2, dZ2 if marg else Z2, 0.3, 1.7, marginal=marg, std_Z=0.8,
+                                    jitter=1e-8, xi=xi, return_cov=True, return_factor=True))
+            put(tag + "/apply_inverse",
+                m.apply_inverse(np.random.default_rng(8).standard_normal((n, 3))))
+            if n == 333:  # two chunks; the grouped pass reuses the last one's scratch
+                X2b, Z2b, dZ2b, _ = points(NX2, p, B, 9)
+                put(tag + "/predict/two_chunks", m.predict(mix, X2b, Z2b, 0.3, 1.7))
+                put(tag + "/groups/two_chunks",
+                    m.predict_marginal_groups(mix, X2b, dZ2b, 1.7, 0.8, G,
+                                              (np.arange(NX2) % G).astype(np.int32)))
+            m.close()
+            # the handle path: pred_cpp / pred_marginal_cpp over DMat handles
+            cross = N.kernmat_SE_cpp if kernel == "SE" else N.kernmat_Matern32_cpp
+            sym = N.kernmat_SE_symmetric_cpp if kernel == "SE" else N.kernmat_Matern32_symmetric_cpp
+            inv = N.invkernel_cpp(sym(X, Z, th, device=True)["full"], th[0])["inv"]
+            put(tag + "/handles/pred",
+                N.pred_cpp(y, th[0], 0.13, inv, cross(X2, X, Z2, Z, th, device=True)["full"],
+                           sym(X2, Z2, th, device=True)["full"], 0.3, 1.7))
+            put(tag + "/handles/marginal",
+                N.pred_marginal_cpp(y, zx, th[0], 0.13, inv,
+                                    cross(X2, X, dZ2, Z, th, device=True)["elements"],
+                                    sym(X2, dZ2, th, device=True)["elements"], 0.0, 1.7, 0.8, True))
+    if part == "all":  # one simulated sharded model
+        m, y, X, Z, th, mix, sy = fitted("Matern32", 700, 20, 10, world=3, sharded=True)
+        X2, Z2, dZ2, zx = points(NX, 20, 10, 6)
+        put("sharded/predict", m.predict(mix, X2, Z2, 0.3, 1.7))
+        put("sharded/marginal/ate1", m.predict_marginal(th, X2, dZ2, zx, 1.7, 0.8, True))
+        m.close()
+run()
+np.savez({out!r}, **out)
+"""
+SNIPS = {"para_update": SNIP, "cross": SNIP_CROSS, "formulas": SNIP_FORMULAS,
+         "predict": SNIP_PREDICT}
+# the processes each build runs in for a mode: (extra environment, ...)
+PARTS = {"predict": ({"CMP_PART": "all"}, {"CMP_PART": "coef7", "ACE_COEF_CHUNK": "7"})}
+NAMED = ("formulas", "predict")  # named outputs in an npz, a verdict per output
 
 
 def bits_equal(a, b):
@@ -186,14 +286,19 @@ def main():
     res = []
     with tempfile.TemporaryDirectory() as d:
         for i, lib in enumerate((a, b)):
-            out = os.path.join(d, f"o{i}." + ("npz" if what == "formulas" else "npy"))
-            env = dict(os.environ, ACE_LIB_PATH=os.path.abspath(lib))
-            if i == 1 and os.environ.get("CMP_ENV_B"):  # "K=V ..." for the second run only
-                env.update(kv.split("=", 1) for kv in os.environ["CMP_ENV_B"].split())
-            subprocess.run([sys.executable, "-c", SNIPS[what].format(root=ROOT, n=n, kernel=kernel, out=out)],
-                           env=env, check=True, timeout=300)
-            res.append(dict(np.load(out)) if what == "formulas" else np.load(out))
-    if what == "formulas":
+            got = {}
+            for j, extra in enumerate(PARTS.get(what, ({},))):
+                out = os.path.join(d, f"o{i}_{j}." + ("npz" if what in NAMED else "npy"))
+                env = dict(os.environ, ACE_LIB_PATH=os.path.abspath(lib), **extra)
+                if i == 1 and os.environ.get("CMP_ENV_B"):  # "K=V ..." for the second run only
+                    env.update(kv.split("=", 1) for kv in os.environ["CMP_ENV_B"].split())
+                subprocess.run([sys.executable, "-c",
+                                SNIPS[what].format(root=ROOT, n=n, kernel=kernel, out=out)],
+                               env=env, check=True, timeout=300)
+                if what in NAMED:
+                    got.update(np.load(out))
+            res.append(got if what in NAMED else np.load(out))
+    if what in NAMED:
         keys = sorted(set(res[0]) | set(res[1]))
         diff = [k for k in keys if k not in res[0] or k not in res[1]
                 or not bits_equal(res[0][k], res[1][k])]
@@ -203,7 +308,7 @@ def main():
                   f"({0 if v is None else v.size} values, "
                   f"{0 if v is None else int(np.sum(~np.isfinite(v)))} non-finite)")
         nval = sum(v.size for v in res[1].values())
-        print(f"formulas: {len(keys) - len(diff)} of {len(keys)} outputs bit-identical "
+        print(f"{what}: {len(keys) - len(diff)} of {len(keys)} outputs bit-identical "
               f"({nval} values); differing: {diff if diff else 'none'}")
         sys.exit(0 if not diff else 1)
     same = np.array_equal(res[0], res[1])
