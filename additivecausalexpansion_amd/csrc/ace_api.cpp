@@ -557,31 +557,17 @@ void assemble_and_sweep(ace_ctx *ctx, SweepWork &w, const Shape &s, const PairSi
   ck(ctx, run_sweep(w.bufs(), st, &sy, tmg), "sweep");
 }
 
-// The gradient's tile list for n: diagonal 64-tiles first, then the strictly
-// lower ones dealt to the XCDs in S x S super-blocks (a launch's block b runs
-// on XCD b % 8).  *ndiag = -1 (and no list) for the row-major grid.
+// The gradient's tile list for n (grad_tile_order) on the device.
+// *ndiag = -1 (and no list) for the row-major grid.
 void build_grad_tiles(ace_ctx *ctx, int64_t n, DBuf &tiles, int64_t *ntiles, int64_t *ndiag,
                       const uint32_t *mask) {
   *ntiles = grad_ntiles(n);
   *ndiag = -1;
-  const int S = grad_order_block();
-  if (S <= 0) return;
-  const int64_t ntr = (n + AT - 1) / AT;
-  std::vector<Tile> lst, low;
-  for (int64_t I = 0; I < ntr; ++I) lst.push_back(Tile{(int)I, (int)I});
-  for (int64_t I = 1; I < ntr; ++I)
-    for (int64_t J = 0; J < I; ++J) low.push_back(Tile{(int)I, (int)J});
-  // with slice masks a tile's cost is its active slices (grouped points: up
-  // to B times apart); the cheap tiles then end each XCD's share of the launch
-  std::function<double(const Tile &)> cost;
-  if (mask)
-    cost = [mask](const Tile &t) { return 1.0 + __builtin_popcount(mask[t.I] & mask[t.J]); };
-  const std::vector<Tile> o = xcd_update_order(low, S, cost);
-  lst.insert(lst.end(), o.begin(), o.end());
+  if (grad_order_block() <= 0) return;
+  const std::vector<Tile> lst = grad_tile_order(n, grad_order_block(), mask, ndiag);
   alloc(ctx, tiles, lst.size() * sizeof(Tile), "alloc grad tiles");
   upload_bytes(ctx, tiles.p, lst.data(), lst.size() * sizeof(Tile), "upload grad tiles");
   *ntiles = (int64_t)lst.size();
-  *ndiag = ntr;
 }
 
 namespace {
@@ -680,11 +666,11 @@ void model_collect_timing(ace_model *m, int ts) {
   ck(m->ctx, hipEventElapsedTime(&ms, m->ev_asm[2 * ts], m->ev_grad[2 * ts + 1]), "elapsed");
   m->t_ms[5] += ms;
   m->t_launch[5] += 1;
-  const double n = (double)m->n, pairs = n * (n + 1) / 2, B = m->s.B, p = m->s.p;
   // work: the update launches' GEMM flops (counted per launch
   // from its tiles), pair kernels by their algorithmic flop formulas
-  m->t_work[1] += pairs * B * (3 * p + 3);
-  m->t_work[2] += pairs * (4 * B * p + 2 * p) + (m->s.kind == ACE_KERNEL_MATERN32 ? pairs * B * p : 0);
+  const double n = (double)m->n, pairs = n * (n + 1) / 2;
+  m->t_work[1] += asm_flops(pairs, m->s.B, m->s.p);
+  m->t_work[2] += grad_flops(pairs, m->s.B, m->s.p, m->s.kind == ACE_KERNEL_MATERN32);
 }
 
 // ace_model_train of an unsharded model: theta, the optimizer moments and

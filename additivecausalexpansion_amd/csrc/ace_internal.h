@@ -1,5 +1,8 @@
-// ace_internal.h -- shared declarations between the HIP kernels
-// (ace_kernels.hip, ace_sweep.hip) and the host orchestration (ace_api.cpp).
+// ace_internal.h -- shared declarations between the HIP kernel sources
+// (ace_pairs*.hip, ace_sweep.hip, ace_util.hip, ace_symm.hip, ace_joint.hip,
+// ace_train.hip) and the host orchestration (ace_api.cpp, ace_shard.cpp,
+// ace_predict.cpp, ace_dmat.cpp).  The sweep's host-only planning is
+// ace_sweep_plan.h.
 #pragma once
 #include <algorithm>
 #include <hip/hip_runtime.h>
@@ -28,7 +31,7 @@ inline int train_sync_every() {
   return v;
 }
 
-constexpr int AT = 64;     // assembly / gradient pair tile
+// (AT, the assembly / gradient pair tile: ace_sweep_plan.h)
 constexpr int PMAX = 64;   // largest supported covariate count p
 constexpr int BMAX = 32;   // largest supported component count B
 
@@ -272,7 +275,6 @@ struct ShardSweep {
   const Tile *tiles;  // own 128-tiles (row-major lower), device
   int64_t ntiles;
 };
-int shard_row_slots(int k, int G);
 hipError_t shard_pack(const ShardSweep &b, int k, hipStream_t st);
 hipError_t shard_unpack_chain(const ShardSweep &b, int k, int buf, hipStream_t st);
 // cross tiles of block k+1 with panel k (buffer buf)

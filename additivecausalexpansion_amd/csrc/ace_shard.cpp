@@ -163,8 +163,9 @@ struct RankState {
   DBuf tupd, tasm, tgrad;  // device tile lists
   int64_t nupd = 0, nasm = 0, nasm1 = 0, ngrad = 0, ndiag = 0;  // nasm1: first-part tiles
   std::vector<Tile> hupd;  // host copy (flop accounting)
-  // head schedule: the own tiles of group_head_tiles' lists (device, host
-  // offsets hoff[G 2Z + m]) and the head part's exchange buffer (Z NB x NB)
+  double gpairs = 0.0;     // point pairs of the gradient list (flop accounting)
+  // head schedule: rank_head_tiles' lists (device, host offsets
+  // hoff[G 2Z + m]) and the head part's exchange buffer (Z NB x NB)
   DBuf th, lowh;
   std::vector<int64_t> hoff;
   DBuf y, tab, alpha, scal, gpart, gwork, red, sums, augvec;
@@ -176,7 +177,7 @@ struct RankState {
 struct ShardModel {
   ace_ctx *ctx = nullptr;
   Shape s{};
-  int64_t n = 0, npad = 0, naug = 0, ntr = 0;
+  int64_t n = 0, npad = 0, naug = 0;
   int G = 1, rank = 0;
   int Z = 2;          // sweep steps per bulk launch of the head schedule (sweep_group_n())
   bool sim = true;    // every rank simulated in this process (device copies)
@@ -205,7 +206,8 @@ struct ShardModel {
   // one-rank collective as the identity)
   bool live() const { return comm != nullptr; }
   DBuf vote;                                       // shard_any: one double
-  std::vector<hipEvent_t> ev;                      // lookahead events
+  SweepEvents E{1, 2};                             // names the lookahead events ...
+  std::vector<hipEvent_t> ev;                      // ... E.count() of them
   // timing of local rank 0 (update launches, assembly, gradient)
   std::vector<hipEvent_t> ev_upd;
   std::vector<double> upd_flops;
@@ -225,14 +227,6 @@ struct ShardModel {
 };
 
 namespace {
-
-int64_t ncols_local(int64_t naug, int G, int r) {
-  const int64_t nblk = (naug + NB - 1) / NB;  // column blocks incl. the AUG block
-  int64_t cnt = 0;
-  for (int64_t j = r; j < nblk; j += G) ++cnt;
-  return cnt * NB;
-}
-
 
 void upload_tiles(ace_ctx *ctx, DBuf &b, const std::vector<Tile> &t) {
   alloc(ctx, b, std::max<size_t>(t.size(), 1) * sizeof(Tile), "alloc tiles");
@@ -259,25 +253,6 @@ ShardSweep sweep_view(const ShardModel &m, RankState &R, int which) {
   b.tiles = reinterpret_cast<const Tile *>(R.tupd.p);
   b.ntiles = R.nupd;
   return b;
-}
-
-// The head schedule's tile lists on rank R: group_head_tiles' lists (the
-// single-GPU head / tail split, ace_sweep_plan.cpp) restricted to the rank's own
-// tiles (column block owned), offsets hoff[G 2Z + m].
-void build_head_lists(ace_ctx *ctx, RankState &R, int64_t naug, int steps, int G, int Z) {
-  constexpr int KT = NB / UT;
-  std::vector<int64_t> off;
-  const std::vector<Tile> all = group_head_tiles(naug, steps, Z, update_order_block(), off);
-  std::vector<Tile> mine;
-  R.hoff.assign(off.size(), 0);
-  for (size_t m = 0; m + 1 < off.size(); ++m) {
-    for (int64_t i = off[m]; i < off[m + 1]; ++i) {
-      const Tile &t = all[(size_t)i];
-      if (t.I >= 0 && (t.J / KT) % G == R.r) mine.push_back(t);
-    }
-    R.hoff[m + 1] = (int64_t)mine.size();
-  }
-  upload_tiles(ctx, R.th, mine);
 }
 
 // ---- collectives over the local ranks -------------------------------------
@@ -433,7 +408,8 @@ void run_sweep_sharded_steps(ShardModel &m, int which, bool timed) {
   // one stream (their exchanges are synchronous)
   const bool lookahead = !m.sim && !m.host;
   hipStream_t side = lookahead ? ctx->side : st;
-  const int steps = (int)(m.npad / NB);
+  const SweepEvents &E = m.E;
+  const int steps = E.steps;
   std::vector<ShardSweep> v;
   for (auto &R : m.ranks) v.push_back(sweep_view(m, *R, which));
   auto rec = [&](int idx, hipStream_t s) {
@@ -447,23 +423,23 @@ void run_sweep_sharded_steps(ShardModel &m, int which, bool timed) {
     exchange(m, k, &RankState::low, m.naug - (int64_t)k * NB, true, m.comm, side);
     for (auto &b : v) ck(ctx, shard_unpack_chain(b, k, buf, side), "shard panel");
   };
-  rec(2 * steps, st);  // inputs ready
-  wait(side, 2 * steps);
+  rec(E.ready(), st);  // once more (shard_eval: after the first part): the whole assembly
+  wait(side, E.ready());
   prepare(0, 0);
-  rec(0, side);
+  rec(E.step_panel_done(0), side);
   m.upd_used = 0;
   for (int k = 0; k < steps; ++k) {
     const int buf = k & 1;
     const bool more = k + 1 < steps;
-    wait(st, 2 * k);  // panel k ready
+    wait(st, E.step_panel_done(k));
     if (more) {
       // side stream, under the bulk update k: cross of block k+1 (after the
       // bulk update k-1), then pack / exchange / sweep of panel k+1
-      rec(2 * k + 1, st);
-      wait(side, 2 * k + 1);
+      rec(E.step_bulk_before(k), st);
+      wait(side, E.step_bulk_before(k));
       for (auto &b : v) ck(ctx, shard_update_cross(b, k, buf, side), "shard cross update");
       prepare(k + 1, buf ^ 1);
-      rec(2 * (k + 1), side);
+      rec(E.step_panel_done(k + 1), side);
     }
     const bool tm = timed && m.upd_used + 2 <= (int)m.ev_upd.size();
     for (size_t j = 0; j < v.size(); ++j) {
@@ -505,32 +481,21 @@ void run_sweep_sharded_steps(ShardModel &m, int which, bool timed) {
 // to run_sweep_sharded_steps (tests/test_shard_gpu.py).
 void run_sweep_sharded_heads(ShardModel &m, int which, bool timed) {
   ace_ctx *ctx = m.ctx;
-  const int steps = (int)(m.npad / NB);
-  const int Z = m.Z, NS = 2 * Z;
-  const int ng = (steps + Z - 1) / Z;
+  const SweepEvents &E = m.E;
+  const int steps = E.steps, Z = E.Z, NS = 2 * Z, ng = E.groups();
   constexpr int KT = NB / UT;
   const int64_t naug = m.naug;
   hipStream_t st = ctx->stream, side = ctx->side, side2 = ctx->side2;
   auto zsize = [&](int g) { return std::min(Z, steps - Z * g); };
   std::vector<ShardSweep> v;
   for (auto &R : m.ranks) v.push_back(sweep_view(m, *R, which));
-  auto EV = [&](int i) { return m.ev[(size_t)i]; };
-  const int E_IN = 0;  // recorded by shard_eval: the first group's columns assembled
-  auto E_READY = [&](int g) { return 1 + g; };          // group g's head path done
-  auto E_READY2 = [&](int g) { return 1 + ng + g; };    // group g's tail path done
-  auto E_SP = [&](int k) { return 2 + 3 * ng + 2 * k; };  // panel k's sub-steps done
-  auto E_GH = [&](int k) { return 3 + 3 * ng + 2 * k; };  // panel k's head GEMM done
-  // main, before bulk g: bulk g-1 done and group g's head and tail paths
-  // done -- what group g+1's lists need (its tiles were last touched by bulk
-  // g-1; the W rows of its blocks come from group g's tail panel GEMMs)
-  auto E_PRE = [&](int g) { return 2 + 3 * ng + 2 * steps + g; };
-  // bulk g done (g = -1: the main stream's work before the sweep): the head
-  // path of group g+2 waits for it and group g+1's tail path directly -- one
-  // cross-stream hop instead of two through E_PRE (single GPU: the same in
-  // run_sweep_heads, profiles/r05_v14_qdirect.txt)
-  auto E_BULK = [&](int g) { return 3 + 4 * ng + 2 * steps + g; };
-  auto rec = [&](int i, hipStream_t s_) { ck(ctx, hipEventRecord(EV(i), s_), "event"); };
-  auto wait = [&](hipStream_t s_, int i) { ck(ctx, hipStreamWaitEvent(s_, EV(i), 0), "event wait"); };
+  // E.ready(): recorded by shard_eval, the first group's columns assembled.
+  // E.bulk_before(g) is what group g+1's lists need: its tiles were last
+  // touched by bulk g-1, the W rows of its blocks come from group g's tail
+  // panel GEMMs.  The head path of group g+2 waits for E.bulk_done(g) and group
+  // g+1's tail path directly: one cross-stream hop, not two (as run_sweep_heads)
+  auto rec = [&](int i, hipStream_t s_) { ck(ctx, hipEventRecord(m.ev[(size_t)i], s_), "event"); };
+  auto wait = [&](hipStream_t s_, int i) { ck(ctx, hipStreamWaitEvent(s_, m.ev[(size_t)i], 0), "event wait"); };
   auto hend_of = [&](int G) { return (int64_t)(Z * G + zsize(G)) * NB; };
   // own tiles of list m of group G (group_head_tiles' numbering)
   auto hlist = [&](size_t q, int G, int mm, int64_t &n) {
@@ -597,37 +562,37 @@ void run_sweep_sharded_heads(ShardModel &m, int which, bool timed) {
       const int k = kb + j;
       // head
       for (auto &b : v) ck(ctx, shard_chain(b, k, k % NS, side), "shard chain");
-      rec(E_SP(k), side);
+      rec(E.substeps_done(k), side);
       for (auto &b : v) ck(ctx, shard_pgemm(b, k, k % NS, (k + 1) * KT, hT, true, side), "shard head GEMM");
-      rec(E_GH(k), side);
+      rec(E.head_gemm_done(k), side);
       if (j + 1 < zb) {
         launch(G, 2 + j, 1, k, k + 1, true, side);  // panel k on Q_{j+1}
         head_in(k + 1, G, true);
       }
       // tail
-      wait(side2, E_SP(k));
+      wait(side2, E.substeps_done(k));
       for (auto &b : v) ck(ctx, shard_pgemm(b, k, k % NS, (k + 1) * KT, hT, false, side2), "shard tail GEMM");
       if (j + 1 < zb) {
-        wait(side2, E_GH(k));
+        wait(side2, E.head_gemm_done(k));
         launch(G, zb + j + 1, j + 1, kb, k + 1, false, side2);  // T_{j+1}
         tail_in(k + 1, G, true);
       }
     }
-    rec(E_READY(G), side);
-    rec(E_READY2(G), side2);
+    rec(E.head_done(G), side);
+    rec(E.tail_done(G), side2);
   };
-  wait(side, E_IN);
-  wait(side2, E_IN);
+  wait(side, E.ready());
+  wait(side2, E.ready());
   produce(0);
-  rec(E_BULK(-1), st);
+  rec(E.bulk_done(-1), st);
   m.upd_used = 0;
   for (int g = 0; g < ng; ++g) {
     const int kg = Z * g;
     const bool more = g + 1 < ng;
     const int kb = Z * (g + 1), zb = more ? zsize(g + 1) : 0;
-    wait(st, E_READY(g));
-    wait(st, E_READY2(g));
-    rec(E_PRE(g), st);
+    wait(st, E.head_done(g));
+    wait(st, E.tail_done(g));
+    rec(E.bulk_before(g), st);
     const bool tm = timed && m.upd_used + 2 <= (int)m.ev_upd.size();
     const int kx0 = more ? kb : -1, kx1 = more ? kb + zb : -1;
     for (size_t j = 0; j < v.size(); ++j) {
@@ -643,10 +608,10 @@ void run_sweep_sharded_heads(ShardModel &m, int which, bool timed) {
       }
     }
     if (!more) break;
-    rec(E_BULK(g), st);
-    wait(side, E_READY2(g));
-    wait(side, E_BULK(g - 1));
-    wait(side2, E_PRE(g));
+    rec(E.bulk_done(g), st);
+    wait(side, E.tail_done(g));
+    wait(side, E.bulk_done(g - 1));
+    wait(side2, E.bulk_before(g));
     produce(g + 1);
   }
 }
@@ -678,7 +643,6 @@ ShardModel *shard_create_any(ace_ctx *ctx, const Shape &s, int64_t n, int world,
   m->n = n;
   m->npad = round_up(n, NB);
   m->naug = m->npad + AUG;
-  m->ntr = (n + AT - 1) / AT;
   m->G = world;
   m->rank = rank;
   m->Z = sweep_group_n(m->naug);
@@ -701,6 +665,7 @@ ShardModel *shard_create_any(ace_ctx *ctx, const Shape &s, int64_t n, int world,
   }
   const int nlocal = m->sim ? world : 1;
   const int steps = (int)(npad / NB);
+  m->E = SweepEvents{steps, m->Z};
   // the head schedule in every mode (the host-callback group's head and tail
   // exchanges block the host one at a time, in issue order)
   m->heads = pair_steps() && steps >= 2;
@@ -726,7 +691,8 @@ ShardModel *shard_create_any(ace_ctx *ctx, const Shape &s, int64_t n, int world,
     }
     for (int b = 0; b < 2; ++b) alloc(ctx, R->S[b], (size_t)(SUB * NB) * sizeof(double), "alloc S");
     if (m->heads) {
-      build_head_lists(ctx, *R, naug, steps, world, m->Z);
+      upload_tiles(ctx, R->th,
+                   rank_head_tiles(naug, steps, m->Z, update_order_block(), world, R->r, R->hoff));
       alloc(ctx, R->lowh, (size_t)(m->Z * NB * NB) * sizeof(double), "alloc head exchange");
     }
     alloc(ctx, R->SW, (size_t)SW_DOUBLES * sizeof(double), "alloc SW");
@@ -743,19 +709,12 @@ ShardModel *shard_create_any(ace_ctx *ctx, const Shape &s, int64_t n, int world,
     if (const int S = update_order_block(); S > 0) R->hupd = xcd_update_order(R->hupd, S);
     R->nupd = (int64_t)R->hupd.size();
     upload_tiles(ctx, R->tupd, R->hupd);
-    std::vector<Tile> ta = own_tiles(npad / AT, AT, world, R->r);
-    // the first group's panels' columns first (the head schedule's first
-    // side path runs under the rest of the assembly, as model_pipeline's)
-    const int jb = m->Z * NB / AT;
-    R->nasm1 = std::stable_partition(ta.begin(), ta.end(), [&](const Tile &t) { return t.J < jb; }) -
-               ta.begin();
+    const std::vector<Tile> ta = rank_asm_tiles(npad, m->Z, world, R->r, &R->nasm1);
     R->nasm = (int64_t)ta.size();
     upload_tiles(ctx, R->tasm, ta);
-    std::vector<Tile> tg = own_tiles(m->ntr, AT, world, R->r);
-    // diagonal tiles first: the gradient kernel runs them separately
-    std::stable_partition(tg.begin(), tg.end(), [](const Tile &t) { return t.I == t.J; });
+    const std::vector<Tile> tg = rank_grad_tiles(n, world, R->r, &R->ndiag);
     R->ngrad = (int64_t)tg.size();
-    for (const Tile &t : tg) R->ndiag += t.I == t.J;
+    R->gpairs = tile_list_pairs(tg);
     upload_tiles(ctx, R->tgrad, tg);
     alloc(ctx, R->y, (size_t)npad * sizeof(double), "alloc y");
     alloc(ctx, R->tab, (size_t)(2 * s.B * s.PM + s.B) * sizeof(double), "alloc tab");
@@ -770,10 +729,7 @@ ShardModel *shard_create_any(ace_ctx *ctx, const Shape &s, int64_t n, int world,
     alloc(ctx, R->augvec, (size_t)(2 * npad + 8) * sizeof(double), "alloc aug vector");
     m->ranks.push_back(std::move(R));
   }
-  // lookahead events: the step schedule's 2 steps + 1, the head schedule's
-  // 4 + 5 ngroups + 2 steps (E_IN .. E_BULK)
-  const int ngr = (steps + m->Z - 1) / m->Z;
-  m->ev.assign((size_t)std::max(2 * steps + 1, 4 + 5 * ngr + 2 * steps), nullptr);
+  m->ev.assign((size_t)m->E.count(), nullptr);
   for (auto &e : m->ev) ck(ctx, hipEventCreateWithFlags(&e, ACE_SYNC_EVENT_FLAGS), "event");
   m->ev_upd.assign((size_t)(2 * steps), nullptr);
   m->upd_flops.assign((size_t)steps, 0.0);
@@ -852,7 +808,7 @@ void shard_eval(ShardModel *m, const double *theta, int use_mu, int which, bool 
         ck(ctx, hipMemsetAsync(R.flag.p, 0, sizeof(int), st), "memset flag");
       }
     }
-    if (part == 0) ck(ctx, hipEventRecord(m->ev[0], st), "event");  // the sweep's inputs ready
+    if (part == 0) ck(ctx, hipEventRecord(m->ev[(size_t)m->E.ready()], st), "event");  // inputs ready
   }
   if (timed) ck(ctx, hipEventRecord(m->ev_asm[1], st), "event");
   run_sweep_sharded(*m, which, timed);
@@ -959,11 +915,9 @@ void shard_collect_timing(ShardModel *m, double *t_ms, int64_t *t_launch, double
     t_work[0] += m->upd_flops[(size_t)(j / 2)];
   }
   // pair kernels: local rank 0's share of the algorithmic flops
-  const RankState &R = *m->ranks[0];
-  const double pairs = (double)(R.ngrad - R.ndiag) * AT * AT + (double)R.ndiag * AT * (AT + 1) / 2;
-  const double B = m->s.B, p = m->s.p;
-  t_work[1] += pairs * B * (3 * p + 3);
-  t_work[2] += pairs * (4 * B * p + 2 * p) + (m->s.kind == ACE_KERNEL_MATERN32 ? pairs * B * p : 0);
+  const double pairs = m->ranks[0]->gpairs;
+  t_work[1] += asm_flops(pairs, m->s.B, m->s.p);
+  t_work[2] += grad_flops(pairs, m->s.B, m->s.p, m->s.kind == ACE_KERNEL_MATERN32);
 }
 
 // Collective OR of a per-rank flag (the interrupt poll of ace_model_para_update):

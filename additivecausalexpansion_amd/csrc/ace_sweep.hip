@@ -2285,8 +2285,6 @@ hipError_t run_sweep(const SweepBufs &b, hipStream_t st, const SweepSync *sy,
 }
 
 // ---- sharded step pieces (driven by ace_shard.cpp) --------------------------
-int shard_row_slots(int k, int G) { return (k + G - 1) / G; }
-
 // Rank r's all-gather operand of step k lies in place in recv (slot r), so
 // the collective needs no local copy (and none at all for one rank).
 static double *send_of(const ShardSweep &b, int k) {

@@ -141,6 +141,53 @@ std::vector<Tile> group_head_tiles(int64_t naug, int steps, int Z, int S,
   return all;
 }
 
+std::vector<Tile> rank_head_tiles(int64_t naug, int steps, int Z, int S, int G, int r,
+                                  std::vector<int64_t> &off) {
+  std::vector<int64_t> all_off;
+  const std::vector<Tile> all = group_head_tiles(naug, steps, Z, S, all_off);
+  std::vector<Tile> mine;
+  off.assign(all_off.size(), 0);
+  for (size_t m = 0; m + 1 < all_off.size(); ++m) {
+    for (int64_t i = all_off[m]; i < all_off[m + 1]; ++i)
+      if (const Tile &t = all[(size_t)i]; t.I >= 0 && owns_col((int64_t)t.J * UT, G, r)) mine.push_back(t);
+    off[m + 1] = (int64_t)mine.size();
+  }
+  return mine;
+}
+
+std::vector<Tile> rank_asm_tiles(int64_t npad, int Z, int G, int r, int64_t *nfirst) {
+  std::vector<Tile> t = own_tiles(npad / AT, AT, G, r);
+  *nfirst = std::stable_partition(t.begin(), t.end(), [&](const Tile &x) { return x.J < Z * NB / AT; }) - t.begin();
+  return t;
+}
+
+std::vector<Tile> rank_grad_tiles(int64_t n, int G, int r, int64_t *ndiag) {
+  std::vector<Tile> t = own_tiles((n + AT - 1) / AT, AT, G, r);
+  *ndiag = std::stable_partition(t.begin(), t.end(), [](const Tile &x) { return x.I == x.J; }) - t.begin();
+  return t;
+}
+
+std::vector<Tile> grad_tile_order(int64_t n, int S, const uint32_t *mask, int64_t *ndiag) {
+  const int64_t ntr = (n + AT - 1) / AT;
+  std::vector<Tile> lst, low;
+  for (int64_t I = 0; I < ntr; ++I)
+    for (int64_t J = 0; J <= I; ++J) (J == I ? lst : low).push_back(Tile{(int)I, (int)J});
+  std::function<double(const Tile &)> cost;
+  if (mask)
+    cost = [mask](const Tile &t) { return 1.0 + __builtin_popcount(mask[t.I] & mask[t.J]); };
+  const std::vector<Tile> o = xcd_update_order(low, S, cost);
+  lst.insert(lst.end(), o.begin(), o.end());
+  *ndiag = ntr;
+  return lst;
+}
+
+double tile_list_pairs(const std::vector<Tile> &tl) {
+  double pairs = 0.0;
+  for (const Tile &t : tl)
+    if (t.I >= 0) pairs += t.I == t.J ? AT * (AT + 1) / 2 : AT * AT;  // (I < 0: padding)
+  return pairs;
+}
+
 std::vector<Tile> own_tiles(int64_t ntile, int T, int G, int r) {
   std::vector<Tile> t;
   for (int64_t I = 0; I < ntile; ++I)

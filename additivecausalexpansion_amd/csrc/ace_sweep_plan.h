@@ -1,6 +1,7 @@
 // ace_sweep_plan.h -- the sweep's host-only planning: blocking, tile lists,
 // the work of a launch on a tile, the named lookahead events, the small-n
-// rules.  Pure functions of (naug, steps, Z, G, r) and no HIP header, so
+// rules, for the single-GPU sweep and the sharded one (ace_shard.cpp).  Pure
+// functions of (naug or n, steps, Z, S, G, r) and no HIP header, so
 // tests/sweep_plan_check.cpp checks them with a host compiler alone.
 #pragma once
 #include <stdint.h>
@@ -19,6 +20,7 @@ constexpr int NB = ACE_NB;  // outer pivot block = panel width
 constexpr int SUB = 64;    // inner pivot block, eliminated inside LDS
 constexpr int UT = 128;    // update tile (MFMA f64 16x16x4, 4 waves x 64x64)
 constexpr int AUG = 128;   // augmented right-hand-side rows (y, 1) appended to A
+constexpr int AT = 64;     // assembly / gradient pair tile
 // GEMM flops of one full update tile against one panel
 constexpr double TILE_FLOPS = 2.0 * UT * UT * NB;
 
@@ -30,6 +32,11 @@ __host__ __device__
 inline __attribute__((always_inline)) bool owns_col(int64_t c, int G, int r) {
   return G == 1 || (c / NB) % G == r;
 }
+// columns of rank r's local array: its column blocks, the AUG block included
+inline int64_t ncols_local(int64_t naug, int G, int r) { return ((naug + NB - 1) / NB - r + G - 1) / G * NB; }
+// NB x NB row pieces A[k, j < k] a rank contributes to step k's all-gather
+// (ShardSweep::recv: G slots of this many)
+inline int shard_row_slots(int k, int G) { return (k + G - 1) / G; }
 
 // A pair / update tile (row tile I, column tile J) of a per-rank tile list.
 // Entries with I < 0 are padding of an XCD-dealt order.
@@ -96,6 +103,33 @@ std::vector<Tile> pair_bulk_orders(int64_t naug, int steps, int S, int64_t *len,
 // 2Z lists per group at off[G 2Z + m] (see ace_sweep_plan.cpp).
 std::vector<Tile> group_head_tiles(int64_t naug, int steps, int Z, int S,
                                    std::vector<int64_t> &off);
+// ... restricted to rank r's own tiles (column block owned), in the same
+// order and without the padding: the sharded head schedule's lists
+std::vector<Tile> rank_head_tiles(int64_t naug, int steps, int Z, int S, int G, int r,
+                                  std::vector<int64_t> &off);
+// Rank r's assembly list: its lower AT-tiles of [0, npad), the first group's
+// panels' columns (J < Z NB / AT) first, *nfirst of them (the sweep's first
+// lookahead runs under the rest of the assembly)
+std::vector<Tile> rank_asm_tiles(int64_t npad, int Z, int G, int r, int64_t *nfirst);
+// Rank r's gradient list: its lower AT-tiles of [0, n), the *ndiag diagonal
+// ones first (the gradient kernel runs them separately)
+std::vector<Tile> rank_grad_tiles(int64_t n, int G, int r, int64_t *ndiag);
+// The single-GPU gradient order: the *ndiag diagonal AT-tiles of [0, n), then
+// the strictly lower ones dealt to the XCDs in S x S super-blocks.  mask (one
+// word per AT-block, PairSide::mask; may be null): a tile's cost is its
+// active slices (grouped points: up to B times apart), and each XCD's cheap
+// tiles end its share of the launch.
+std::vector<Tile> grad_tile_order(int64_t n, int S, const uint32_t *mask, int64_t *ndiag);
+
+// ---- the pair kernels' work of a timed evaluation -----------------------------
+// point pairs of a list of lower AT-tiles, every tile counted whole
+double tile_list_pairs(const std::vector<Tile> &tl);
+// algorithmic flops of the assembly and of the gradient over
+// `pairs` point pairs with B components and p covariates
+inline double asm_flops(double pairs, double B, double p) { return pairs * B * (3 * p + 3); }
+inline double grad_flops(double pairs, double B, double p, bool matern) {
+  return pairs * (4 * B * p + 2 * p) + (matern ? pairs * B * p : 0);
+}
 
 // ---- the lookahead events of one sweep (SweepSync::ev) ------------------------
 // One name per event; every name is an index of its own below count() (the
@@ -121,12 +155,16 @@ struct SweepEvents {
   // before bulk k (bulk k - 1 and what preceded the sweep)
   int step_panel_done(int k) const { return step0() + 2 * k; }
   int step_bulk_before(int k) const { return step0() + 2 * k + 1; }
-  int count() const { return step0() + 2 * steps; }
+  // the sharded head schedule: the main stream before bulk g (bulk g - 1 and
+  // group g's head and tail paths done)
+  int bulk_before(int g) const { return before0() + g; }
+  int count() const { return before0() + groups(); }
 
  private:
   int group0() const { return 4 + groups(); }
   int panel0() const { return group0() + 4 * groups(); }
   int step0() const { return panel0() + 2 * steps; }
+  int before0() const { return step0() + 2 * steps; }
 };
 
 // ---- the small-n regime ---------------------------------------------------------

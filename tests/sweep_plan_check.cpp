@@ -1,6 +1,7 @@
 // Stand-alone check of the sweep's host-only planning (csrc/ace_sweep_plan.*):
-// the event names, the tile lists of both schedules, the tile-work rule and
-// the small-n layout rules.  Built and run by tests/test_sweep_plan_cpu.py
+// the event names, the tile lists of both schedules on one GPU and sharded
+// over ranks, the tile-work rule, the pair kernels' work counts and the
+// small-n layout rules.  Built and run by tests/test_sweep_plan_cpu.py
 // with a host compiler and AddressSanitizer + UBSan; needs no GPU.
 #include <stdio.h>
 
@@ -26,7 +27,8 @@ static int failures = 0;
   } while (0)
 
 constexpr int KT = NB / UT;
-constexpr int S_DEFAULT = 2;  // update_order_block()'s default
+constexpr int S_DEFAULT = 2;       // update_order_block()'s default
+constexpr int S_GRAD_DEFAULT = 4;  // grad_order_block()'s default
 
 // ---- 1. events: every name an index of its own below count() ----------------
 static void check_events(int steps, int Z) {
@@ -45,6 +47,7 @@ static void check_events(int steps, int Z) {
     add(E.tail_done(g));
     add(E.q_done(g));
     add(E.last_tail(g));
+    add(E.bulk_before(g));
   }
   for (int k = 0; k < steps; ++k) {
     add(E.substeps_done(k));
@@ -180,6 +183,153 @@ static void check_ranks(int steps, int Z, int G) {
   }
 }
 
+// ---- 3b. the sharded schedules (ace_shard.cpp), every rank walked in turn -----
+// a rank's launch: as Walk::launch, and every tile's column block is the rank's
+static void rank_launch(Walk &w, int G, int r, const Tile *tl, int64_t n, int kb, int npan, int kx0, int kx1) {
+  for (int64_t i = 0; i < n; ++i)
+    CHECK(tl[i].I < 0 || owns_col((int64_t)tl[i].J * UT, G, r), "rank %d of %d launches on tile (%d, %d)", r, G,
+          tl[i].I, tl[i].J);
+  w.launch(tl, n, kb, npan, kx0, kx1);
+}
+// a rank's bulk list (RankState::hupd)
+static std::vector<Tile> rank_bulk_tiles(int64_t nT, int G, int r) {
+  return xcd_update_order(own_tiles(nT, UT, G, r), S_DEFAULT);
+}
+
+// run_sweep_sharded_heads
+static void check_sharded_head_schedule(int steps, int Z, int G) {
+  const int64_t naug = (int64_t)steps * NB + AUG, nT = naug / UT;
+  const int ng = (steps + Z - 1) / Z;
+  auto zsize = [&](int g) { return std::min(Z, steps - Z * g); };
+  std::vector<int64_t> aoff;
+  const std::vector<Tile> all = group_head_tiles(naug, steps, Z, S_DEFAULT, aoff);
+  Walk w{nT, steps, {}, 0.0};
+  for (int r = 0; r < G; ++r) {
+    std::vector<int64_t> hoff;
+    const std::vector<Tile> h = rank_head_tiles(naug, steps, Z, S_DEFAULT, G, r, hoff);
+    // the single-GPU lists restricted to the rank, in the same order
+    CHECK(hoff.size() == aoff.size() && hoff.back() == (int64_t)h.size(), "rank %d of %d: head offsets", r, G);
+    for (size_t m = 0; m + 1 < aoff.size() && m + 1 < hoff.size(); ++m) {
+      int64_t at = hoff[m];
+      for (int64_t i = aoff[m]; i < aoff[m + 1]; ++i) {
+        const Tile &t = all[(size_t)i];
+        if (t.I < 0 || !owns_col((int64_t)t.J * UT, G, r)) continue;
+        CHECK(at < hoff[m + 1] && h[(size_t)at].I == t.I && h[(size_t)at].J == t.J,
+              "steps %d Z %d rank %d of %d: head list %zu differs at tile (%d, %d)", steps, Z, r, G, m, t.I, t.J);
+        ++at;
+      }
+      CHECK(at == hoff[m + 1], "steps %d Z %d rank %d of %d: head list %zu has extra tiles", steps, Z, r, G, m);
+    }
+    const std::vector<Tile> bulk = rank_bulk_tiles(nT, G, r);
+    auto list = [&](int g, int m, int kb, int npan) {
+      const int64_t i = (int64_t)g * 2 * Z + m;
+      rank_launch(w, G, r, h.data() + hoff[(size_t)i], hoff[(size_t)i + 1] - hoff[(size_t)i], kb, npan, -1, -1);
+    };
+    auto produce = [&](int g) {
+      const int kb = Z * g, zb = zsize(g);
+      if (g > 0) {
+        list(g, 0, Z * (g - 1), zsize(g - 1));  // Q
+        list(g, 1, Z * (g - 1), zsize(g - 1));  // the rest of the cross
+      }
+      for (int j = 0; j + 1 < zb; ++j) {
+        list(g, 2 + j, kb + j, 1);       // panel kb + j on Q_{j+1}
+        list(g, zb + j + 1, kb, j + 1);  // T_{j+1}
+      }
+    };
+    produce(0);
+    for (int g = 0; g < ng; ++g) {
+      const bool more = g + 1 < ng;
+      const int kx0 = more ? Z * (g + 1) : -1, kx1 = more ? Z * (g + 1) + zsize(g + 1) : -1;
+      rank_launch(w, G, r, bulk.data(), (int64_t)bulk.size(), Z * g, zsize(g), kx0, kx1);
+      if (more) produce(g + 1);
+    }
+  }
+  char what[64];
+  snprintf(what, sizeof what, "sharded head schedule, %d ranks", G);
+  w.verify(what, Z);
+}
+
+// run_sweep_sharded_steps: the cross launch is a grid over the block's rows
+// and columns whose workgroups keep to the rank's columns (k_update_x)
+static void check_sharded_step_schedule(int steps, int G) {
+  const int64_t naug = (int64_t)steps * NB + AUG, nT = naug / UT;
+  Walk w{nT, steps, {}, 0.0};
+  for (int r = 0; r < G; ++r) {
+    const std::vector<Tile> own = own_tiles(nT, UT, G, r), bulk = rank_bulk_tiles(nT, G, r);
+    for (int k = 0; k < steps; ++k) {
+      const bool more = k + 1 < steps;
+      if (more) {
+        std::vector<Tile> x;
+        for (const Tile &t : own)
+          if (in_blocks(t, k + 1, k + 2)) x.push_back(t);
+        rank_launch(w, G, r, x.data(), (int64_t)x.size(), k, 1, -1, -1);
+      }
+      rank_launch(w, G, r, bulk.data(), (int64_t)bulk.size(), k, 1, more ? k + 1 : -1, k + 2);
+    }
+  }
+  char what[64];
+  snprintf(what, sizeof what, "sharded one-step schedule, %d ranks", G);
+  w.verify(what, 1);
+}
+
+// a rank's assembly and gradient lists, and the layout helpers
+static void check_rank_lists(int steps, int Z, int G) {
+  const int64_t npad = (int64_t)steps * NB, naug = npad + AUG, n = npad - 37;
+  const int64_t na = npad / AT, ng = (n + AT - 1) / AT;
+  std::set<std::pair<int, int>> seen_a, seen_g;
+  int64_t cols = 0;
+  for (int r = 0; r < G; ++r) {
+    cols += ncols_local(naug, G, r);
+    int64_t nfirst = -1, ndiag = -1;
+    const std::vector<Tile> ta = rank_asm_tiles(npad, Z, G, r, &nfirst);
+    const std::vector<Tile> tg = rank_grad_tiles(n, G, r, &ndiag);
+    CHECK(nfirst >= 0 && nfirst <= (int64_t)ta.size() && ndiag >= 0 && ndiag <= (int64_t)tg.size(),
+          "rank %d of %d: list counts", r, G);
+    for (size_t i = 0; i < ta.size(); ++i) {
+      const Tile &t = ta[i];
+      CHECK(t.J >= 0 && t.J <= t.I && t.I < na && owns_col((int64_t)t.J * AT, G, r) && seen_a.insert({t.I, t.J}).second,
+            "steps %d rank %d of %d: assembly tile (%d, %d)", steps, r, G, t.I, t.J);
+      // the first part is exactly the tiles in the first group's columns
+      CHECK(((int64_t)i < nfirst) == ((int64_t)t.J * AT < (int64_t)Z * NB),
+            "steps %d Z %d rank %d of %d: assembly tile (%d, %d) at %zu, first part %lld", steps, Z, r, G, t.I, t.J,
+            i, (long long)nfirst);
+    }
+    for (size_t i = 0; i < tg.size(); ++i) {
+      const Tile &t = tg[i];
+      CHECK(t.J >= 0 && t.J <= t.I && t.I < ng && owns_col((int64_t)t.J * AT, G, r) && seen_g.insert({t.I, t.J}).second,
+            "steps %d rank %d of %d: gradient tile (%d, %d)", steps, r, G, t.I, t.J);
+      CHECK(((int64_t)i < ndiag) == (t.I == t.J), "steps %d rank %d of %d: gradient tile (%d, %d) at %zu, ndiag %lld",
+            steps, r, G, t.I, t.J, i, (long long)ndiag);
+    }
+  }
+  CHECK((int64_t)seen_a.size() == na * (na + 1) / 2, "steps %d G %d: %zu assembly tiles", steps, G, seen_a.size());
+  CHECK((int64_t)seen_g.size() == ng * (ng + 1) / 2, "steps %d G %d: %zu gradient tiles", steps, G, seen_g.size());
+  CHECK(cols == (naug + NB - 1) / NB * NB, "naug %lld G %d: %lld local columns", (long long)naug, G, (long long)cols);
+}
+
+// the single-GPU gradient order: the diagonal, then every strictly lower tile once
+static std::vector<uint32_t> test_mask(int64_t ntr) {
+  std::vector<uint32_t> m((size_t)ntr);
+  for (int64_t k = 0; k < ntr; ++k) m[(size_t)k] = (uint32_t)((k * 2654435761u) >> 7) & 0x1ffu;
+  return m;
+}
+static void check_grad_order(int64_t n, int S, bool masked) {
+  const int64_t ntr = (n + AT - 1) / AT;
+  const std::vector<uint32_t> mk = test_mask(ntr);
+  int64_t ndiag = -1;
+  const std::vector<Tile> o = grad_tile_order(n, S, masked ? mk.data() : nullptr, &ndiag);
+  CHECK(ndiag == ntr && (int64_t)o.size() >= ntr * (ntr + 1) / 2, "gradient order n %lld: counts", (long long)n);
+  std::set<std::pair<int, int>> seen;
+  for (size_t i = 0; i < o.size(); ++i) {
+    const Tile &t = o[i];
+    if ((int64_t)i < ndiag) CHECK(t.I == (int)i && t.J == (int)i, "gradient order n %lld: entry %zu", (long long)n, i);
+    else if (t.I >= 0)
+      CHECK(t.J >= 0 && t.J < t.I && t.I < ntr && seen.insert({t.I, t.J}).second,
+            "gradient order n %lld: tile (%d, %d)", (long long)n, t.I, t.J);
+  }
+  CHECK((int64_t)seen.size() == ntr * (ntr - 1) / 2, "gradient order n %lld: %zu lower tiles", (long long)n, seen.size());
+}
+
 // ---- 4. the lists and counters of the commit before the plan moved here ------
 static uint64_t fnv(uint64_t h, int64_t v) {
   for (int i = 0; i < 8; ++i) {
@@ -246,6 +396,24 @@ static const Pinned PINNED[] = {
     {"pair_bulk_orders steps=13 Z=4 G=3 r=2", 0x387eb5fd1582f63dull},
     {"xcd_update_order steps=13 S=2", 0xede58f8ffde48a85ull},
     {"xcd_update_order steps=13 S=4", 0x8c023ab8212e0085ull},
+    // the lists ace_shard.cpp and ace_api.cpp built inline before these
+    // functions (profiles/shard_plan_ab.txt)
+    {"rank_head_tiles steps=5 Z=2 G=3 r=0", 0xee47bb4e3e91e65full},
+    {"rank_asm_tiles steps=5 Z=2 G=3 r=0", 0x23e467b27e77bf4full},
+    {"rank_grad_tiles steps=5 Z=2 G=3 r=0", 0x61b771322ec8facdull},
+    {"rank_head_tiles steps=7 Z=3 G=4 r=3", 0x6dd8ff935494a117ull},
+    {"rank_asm_tiles steps=7 Z=3 G=4 r=3", 0x09a3f10f9f573ec5ull},
+    {"rank_grad_tiles steps=7 Z=3 G=4 r=3", 0x83cbd224f5c57241ull},
+    {"rank_head_tiles steps=13 Z=4 G=2 r=1", 0x696c56d3c601f4d0ull},
+    {"rank_asm_tiles steps=13 Z=4 G=2 r=1", 0xb5bf936d0c2d9536ull},
+    {"rank_grad_tiles steps=13 Z=4 G=2 r=1", 0x4fd62174b86d83ddull},
+    {"rank_head_tiles steps=8 Z=4 G=8 r=5", 0x590b1709c698db5dull},
+    {"rank_asm_tiles steps=8 Z=4 G=8 r=5", 0x5763832f033c9bc5ull},
+    {"rank_grad_tiles steps=8 Z=4 G=8 r=5", 0x9912334ff03acf41ull},
+    {"grad_tile_order n=1700 mask=0", 0x1a60bbb1e7bb1cceull},
+    {"grad_tile_order n=1700 mask=1", 0xda73f24a0eb038ceull},
+    {"grad_tile_order n=3301 mask=0", 0x07ea701f2748ed31ull},
+    {"grad_tile_order n=3301 mask=1", 0x548c46a9bc8259b1ull},
 };
 static const PinnedValue PINNED_VALUES[] = {
     {"update_gemm_tiles k=4 kx=5", 255.875},
@@ -256,6 +424,15 @@ static const PinnedValue PINNED_VALUES[] = {
     {"sweep_flops", 38508953600},
     {"list flops, one step k=4 kx=5 (rank 1 of 3)", 619708416},
     {"list flops, group g=1 (rank 1 of 3)", 1133510656},
+    // the pair kernels' work of a timed evaluation at n = 1700, B = 10, p = 20:
+    // model_collect_timing, then shard_collect_timing on rank 0 of 3
+    {"model assembly flops", 910885500},
+    {"model gradient flops SE", 1214514000},
+    {"model gradient flops Matern", 1503684000},
+    {"shard pairs (rank 0 of 3)", 641376},
+    {"shard assembly flops", 404066880},
+    {"shard gradient flops SE", 538755840},
+    {"shard gradient flops Matern", 667031040},
 };
 
 static void check_pinned() {
@@ -285,6 +462,31 @@ static void check_pinned() {
     snprintf(name, sizeof name, "xcd_update_order steps=13 S=%d", S);
     got.push_back({name, hash_list(xcd_update_order(own_tiles((13 * NB + AUG) / UT, UT, 1, 0), S), {})});
   }
+  // (7, 3, 4, 3): steps % Z != 0 and a rank without a column of the first group
+  struct {
+    int steps, Z, G, r;
+  } const pts[] = {{5, 2, 3, 0}, {7, 3, 4, 3}, {13, 4, 2, 1}, {8, 4, 8, 5}};
+  for (auto &q : pts) {
+    const int64_t npad = (int64_t)q.steps * NB, n = npad - 37;
+    int64_t cnt = 0;
+    snprintf(name, sizeof name, "rank_head_tiles steps=%d Z=%d G=%d r=%d", q.steps, q.Z, q.G, q.r);
+    const std::vector<Tile> h = rank_head_tiles(npad + AUG, q.steps, q.Z, S_DEFAULT, q.G, q.r, off);
+    got.push_back({name, hash_list(h, off)});
+    snprintf(name, sizeof name, "rank_asm_tiles steps=%d Z=%d G=%d r=%d", q.steps, q.Z, q.G, q.r);
+    const std::vector<Tile> ta = rank_asm_tiles(npad, q.Z, q.G, q.r, &cnt);
+    got.push_back({name, hash_list(ta, {cnt})});
+    snprintf(name, sizeof name, "rank_grad_tiles steps=%d Z=%d G=%d r=%d", q.steps, q.Z, q.G, q.r);
+    const std::vector<Tile> tg = rank_grad_tiles(n, q.G, q.r, &cnt);
+    got.push_back({name, hash_list(tg, {cnt})});
+  }
+  for (int64_t n : {1700, 3301})
+    for (int masked = 0; masked < 2; ++masked) {
+      const std::vector<uint32_t> mk = test_mask((n + AT - 1) / AT);
+      int64_t ndiag = 0;
+      snprintf(name, sizeof name, "grad_tile_order n=%lld mask=%d", (long long)n, masked);
+      const std::vector<Tile> o = grad_tile_order(n, S_GRAD_DEFAULT, masked ? mk.data() : nullptr, &ndiag);
+      got.push_back({name, hash_list(o, {ndiag})});
+    }
   for (auto &g : got) printf("hash %-44s 0x%016llxull\n", g.first.c_str(), (unsigned long long)g.second);
   CHECK(got.size() == sizeof PINNED / sizeof *PINNED, "%zu lists, %zu pinned", got.size(),
         sizeof PINNED / sizeof *PINNED);
@@ -295,6 +497,9 @@ static void check_pinned() {
   // the five counters: 13 steps, groups of 3
   const int64_t naug = 13 * NB + AUG, nT = naug / UT;
   const std::vector<Tile> own = xcd_update_order(own_tiles(nT, UT, 3, 1), S_DEFAULT);
+  const double mpairs = 1700.0 * 1701.0 / 2;
+  int64_t nd = 0;
+  const double spairs = tile_list_pairs(rank_grad_tiles(1700, 3, 0, &nd));
   const std::pair<const char *, double> vals[] = {
       {"update_gemm_tiles k=4 kx=5", update_gemm_tiles(naug, 4 * NB, 5, false)},
       {"update_gemm_tiles k=4 kx=5 look", update_gemm_tiles(naug, 4 * NB, 5, true)},
@@ -304,6 +509,13 @@ static void check_pinned() {
       {"sweep_flops", sweep_flops(naug, 13 * NB)},
       {"list flops, one step k=4 kx=5 (rank 1 of 3)", tile_list_work(own, nT, 4 * KT, 1, 5, 6) * TILE_FLOPS},
       {"list flops, group g=1 (rank 1 of 3)", tile_list_work(own, nT, 3 * KT, 3, 6, 9) * TILE_FLOPS},
+      {"model assembly flops", asm_flops(mpairs, 10, 20)},
+      {"model gradient flops SE", grad_flops(mpairs, 10, 20, false)},
+      {"model gradient flops Matern", grad_flops(mpairs, 10, 20, true)},
+      {"shard pairs (rank 0 of 3)", spairs},
+      {"shard assembly flops", asm_flops(spairs, 10, 20)},
+      {"shard gradient flops SE", grad_flops(spairs, 10, 20, false)},
+      {"shard gradient flops Matern", grad_flops(spairs, 10, 20, true)},
   };
   size_t i = 0;
   for (auto &v : vals) {
@@ -344,8 +556,18 @@ int main() {
       check_events(steps, Z);
       if (steps >= 2) check_head_schedule(steps, Z);
       for (int G = 1; G <= 3; ++G) check_ranks(steps, Z, G);
+      for (int G = 1; G <= 4; ++G) {
+        if (steps >= 2) check_sharded_head_schedule(steps, Z, G);
+        if (Z == 2) check_sharded_step_schedule(steps, G);
+        check_rank_lists(steps, Z, G);
+      }
     }
   }
+  check_sharded_head_schedule(13, 3, 8);
+  check_sharded_step_schedule(13, 8);
+  check_rank_lists(13, 3, 8);
+  for (int64_t n : {1, 64, 65, 1700})
+    for (int masked = 0; masked < 2; ++masked) check_grad_order(n, S_GRAD_DEFAULT, masked != 0);
   check_pinned();
   check_layout();
   if (failures) {

@@ -1,8 +1,9 @@
 """AddressSanitizer + UBSan run of the sweep's host-only planning
 (csrc/ace_sweep_plan.cpp) through tests/sweep_plan_check.cpp: the event names,
-both schedules' tile lists walked launch by launch, the work counts, the
-lists and counters pinned to the commit before the plan became a unit of its
-own, and the small-n layout rules.  CPU only."""
+both schedules' tile lists walked launch by launch (single GPU, and sharded
+over 1 .. 4 and 8 ranks), the work counts, the lists and counters pinned to
+the commits before each part of the plan moved into the unit, and the small-n
+layout rules.  CPU only."""
 import os
 import shutil
 import subprocess
