@@ -116,6 +116,10 @@ SIGNATURES = {
                                                ctypes.c_int, ctypes.c_double, _I64, _D, _D, _D, _D,
                                                _D, _I64P]),
     "ace_potrf_lower": (ctypes.c_int, [_I64, _D, _I64, ctypes.c_double, _D, _I64, _I64P]),
+    "ace_model_cv": (ctypes.c_int, [_vp, _D, _I64, _I64P, _I64P, ctypes.c_double, ctypes.c_double,
+                                    _D, _D, _D, _D, _D, _I32]),
+    "ace_cv_from_inverse": (ctypes.c_int, [_vp, _I64, _D, _I64, _D, _I64, _I64P, _I64P, _D, _D, _D,
+                                           _D, _I32]),
     "ace_model_profile": (ctypes.c_int, [_vp, ctypes.c_int]),
     "ace_model_kernel_time": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                              ctypes.POINTER(_I64),

@@ -15,9 +15,10 @@ SOURCES = ["csrc/ace_pairs.hip", "csrc/ace_pairs_mm.hip", "csrc/ace_sweep.hip", 
            "csrc/ace_symm.hip", "csrc/ace_joint.hip", "csrc/ace_api.cpp", "csrc/ace_host.cpp", "csrc/ace_shard.cpp",
            "csrc/ace_predict.cpp", "csrc/ace_dmat.cpp", "csrc/ace_train.hip",
            "csrc/ace_batch.hip", "csrc/ace_batch_predict.hip", "csrc/ace_batch.cpp",
-           "csrc/ace_sweep_plan.cpp"]
+           "csrc/ace_sweep_plan.cpp", "csrc/ace_cv.hip", "csrc/ace_cv.cpp", "csrc/ace_cv_plan.cpp"]
 HEADERS = ["csrc/ace_internal.h", "csrc/ace_common.h", "csrc/ace_model.h", "csrc/ace_batch.h",
            "csrc/ace_formulas.h", "csrc/ace_wgtime.h", "csrc/ace_sweep_plan.h", "csrc/ace_retry.h",
+           "csrc/ace_cv.h", "csrc/ace_cv_plan.h",
            "../include/ace_hip.h"]
 OUT = os.path.join(HERE, "libace_hip.so")
 OBJDIR = os.path.join(HERE, "build")

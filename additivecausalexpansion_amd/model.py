@@ -283,6 +283,29 @@ class DeviceModel:
             out["draws"] = draws if S else np.empty((nx, 0), order="F")
         return out
 
+    def cv(self, theta, folds, mean_y, std_y):
+        """ace_model_cv: cross-validation from the resident inverse, without
+        a refit.  folds: a list of integer arrays of the caller's rows (they
+        may overlap and need not cover the data).  Returns {"map", "var",
+        "resid": packed in the folds' order, original units; "lpd", "mahal",
+        "status": per fold; "off": the packed offsets}.  status > 0: that
+        fold's block of the inverse is not positive definite at that pivot
+        -- its outputs are NaN, the other folds are unaffected.  The inverse
+        is the last para_update's, mu = theta[1] (Q6), as predict uses them.
+        Single-GPU models."""
+        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
+        nf, off, idx = native.pack_folds(folds)
+        tot = int(off[-1])
+        mp, var, res = (np.empty(max(tot, 1)) for _ in range(3))
+        lpd, mh = np.empty(nf), np.empty(nf)
+        st = np.zeros(nf, dtype=np.int32)
+        check(lib().ace_model_cv(self.handle, ptr(th), nf, native.iptr(off), native.iptr(idx),
+                                 float(mean_y), float(std_y), ptr(mp), ptr(var), ptr(res), ptr(lpd),
+                                 ptr(mh), st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+              self.ctx.handle)
+        return {"map": mp[:tot], "var": var[:tot], "resid": res[:tot], "lpd": lpd, "mahal": mh,
+                "status": st, "off": off}
+
     def comm_calls(self):
         """ace_model_comm_calls: collectives this rank issued since creation,
         {"broadcast", "allgather", "allreduce", "groups"} (zeros when simulated)."""
@@ -671,6 +694,14 @@ class _KernelClass:
             raise AceError("predict_joint needs the fit's device-resident inverse "
                            "(para_update on the same data)")
         return self._model.predict_joint(self.parameters, X2, Z2, mean_y, std_y, **kw)
+
+    def cross_validate(self, y, X, Z, folds, mean_y, std_y):
+        """Cross-validation from the fit's resident inverse, without a refit
+        (DeviceModel.cv; folds a list of index arrays)."""
+        if not self._resident(y, X, Z):
+            raise AceError("cross_validate needs the fit's device-resident inverse "
+                           "(para_update on the same data)")
+        return self._model.cv(self.parameters, folds, mean_y, std_y)
 
     def mean_solution(self, y):
         """R/kernel_SE_R6.R:99-102 (private in the SE class)."""

@@ -492,3 +492,46 @@ def potrf_lower(A, jitter=0.0, lda=None):
     info = ctypes.c_int64(0)
     check(lib().ace_potrf_lower(n, ptr(Af), ld, float(jitter), ptr(L), n, ctypes.byref(info)))
     return L, int(info.value)
+
+
+def pack_folds(folds):
+    """(nf, off, idx) of a list of integer index arrays: the packed fold list
+    of ace_model_cv / ace_cv_from_inverse (fold f = idx[off[f]:off[f + 1]])."""
+    fl = [np.ascontiguousarray(np.ravel(f), dtype=np.int64) for f in folds]
+    if not fl:
+        raise AceError("folds must hold at least one fold")
+    off = np.zeros(len(fl) + 1, dtype=np.int64)
+    np.cumsum([f.size for f in fl], out=off[1:])
+    idx = np.concatenate(fl) if off[-1] else np.zeros(1, dtype=np.int64)
+    return len(fl), off, np.ascontiguousarray(idx, dtype=np.int64)
+
+
+def iptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def cv_from_inverse(P, alpha, folds, ctx=None):
+    """ace_cv_from_inverse: for every fold F (a list of integer arrays) of a
+    symmetric P (n x n, the lower triangle is read) and alpha (n):
+    {"resid": B_F^-1 alpha_F and "var": diag(B_F^-1), packed in the folds'
+    order; "logdet": log det B_F, "mahal": alpha_F^T B_F^-1 alpha_F and
+    "status" per fold; "off"} with B_F = P[F, F].  status = 0, or the 1-based
+    index of the first pivot (rows sorted) that is <= 0 or not finite; that
+    fold's outputs are NaN and the others are unaffected."""
+    Pf = fmat(P)
+    if Pf.ndim != 2 or Pf.shape[0] != Pf.shape[1]:
+        raise AceError("P must be a square matrix")
+    n = Pf.shape[0]
+    al = np.ascontiguousarray(np.ravel(alpha), dtype=np.float64)
+    if al.size != n:
+        raise AceError("alpha must have n entries")
+    nf, off, idx = pack_folds(folds)
+    tot = int(off[-1])
+    r, v = np.empty(max(tot, 1)), np.empty(max(tot, 1))
+    ld, mh = np.empty(nf), np.empty(nf)
+    st = np.zeros(nf, dtype=np.int32)
+    h = _ctx(ctx)
+    check(lib().ace_cv_from_inverse(h, n, ptr(Pf), n, ptr(al), nf, iptr(off), iptr(idx), ptr(r),
+                                    ptr(v), ptr(ld), ptr(mh),
+                                    st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), h)
+    return {"resid": r[:tot], "var": v[:tot], "logdet": ld, "mahal": mh, "status": st, "off": off}

@@ -439,6 +439,76 @@ def posterior_draws(fit, newX=None, newZ=None, marginal=False, n_draws=1000, see
     return out
 
 
+def cross_validate(fit, folds=10, seed=0, groups=None):
+    """Cross-validation of a fit without refitting: the held-out prediction of
+    every fold from the fit's resident inverse, hyperparameters and mu held
+    fixed (Rasmussen & Williams §5.4.2 and its block form; DeviceModel.cv).
+    folds: an int K -- the random partition np.array_split(default_rng(seed)
+    .permutation(n), K); "loo" -- leave-one-out; or a list of index arrays
+    (they may overlap and need not cover the data).  groups (labels per row)
+    means leave-one-group-out, one fold per distinct label.
+    Returns, for disjoint folds, "map", "var", "ci" (n x 2: map -+ 1.96
+    sqrt(var)), "resid" (held-out y - map), "z" = resid / sqrt(var), each of
+    length n in original units and NaN where a row is in no fold, and "fold"
+    (the fold id per row, -1 if in none); for overlapping folds the same
+    arrays packed fold after fold ("off" the offsets, no "fold").  Per fold:
+    "lpd" (the joint log predictive density of its held-out rows), "mahal",
+    "size", "status"; and "elpd" = sum lpd, "rmse", "coverage" (the share of
+    held-out y inside ci).  The inverse is the last para_update's, theta_{T-1}'s,
+    while mu is the final one (Q6): the model predict_ace uses in-sample."""
+    K = fit["Kernel"]
+    y = fit["train_data"]["y"]
+    X = fit["train_data"]["X"]
+    mom = fit["moments"]
+    n = X.shape[0]
+    if groups is not None:
+        g = np.ravel(np.asarray(groups))
+        if g.size != n:
+            raise AceError("groups must have one label per training row")
+        fl = [np.flatnonzero(g == u) for u in np.unique(g)]
+    elif isinstance(folds, str):
+        if folds != "loo":
+            raise AceError('folds must be an int, "loo" or a list of index arrays')
+        fl = [np.array([i]) for i in range(n)]
+    elif np.ndim(folds) == 0:
+        k = int(folds)
+        if not 2 <= k <= n:
+            raise AceError("folds must be between 2 and n")
+        fl = np.array_split(np.random.default_rng(seed).permutation(n), k)
+    else:
+        fl = [np.ravel(np.asarray(f)).astype(np.int64) for f in folds]
+    r = K.cross_validate(y, X, fit["Basis"].B, fl, mom[0, 0], mom[0, 1])
+    bad = np.flatnonzero(r["status"] != 0)
+    if bad.size:
+        f = int(bad[0])
+        raise AceError(
+            f"cross_validate: fold {f} ({fl[f].size} rows) is not positive definite at pivot "
+            f"{int(r['status'][f])}: its block of the inverse cannot be conditioned on. Note that "
+            "the fit's inverse is the last para_update's (theta_{T-1}'s) while mu is the final "
+            "one (Q6)")
+    idx = np.concatenate(fl)
+    yo = mom[0, 0] + mom[0, 1] * np.ravel(y)[idx]
+    sd = np.sqrt(r["var"])
+    ci = np.column_stack([r["map"] - 1.96 * sd, r["map"] + 1.96 * sd])
+    out = {"lpd": r["lpd"], "mahal": r["mahal"], "size": np.array([f.size for f in fl]),
+           "status": r["status"], "elpd": float(np.sum(r["lpd"])),
+           "rmse": float(np.sqrt(np.mean(r["resid"] ** 2))),
+           "coverage": float(np.mean((yo >= ci[:, 0]) & (yo <= ci[:, 1])))}
+    packed = {"map": r["map"], "var": r["var"], "ci": ci, "resid": r["resid"],
+              "z": r["resid"] / sd}
+    if np.unique(idx).size != idx.size:  # overlapping folds: packed fold after fold
+        out.update(packed, off=r["off"])
+        return out
+    for k, v in packed.items():
+        full = np.full((n,) + v.shape[1:], np.nan)
+        full[idx] = v
+        out[k] = full
+    fid = np.full(n, -1, dtype=np.int64)
+    fid[idx] = np.repeat(np.arange(len(fl)), [f.size for f in fl])
+    out["fold"] = fid
+    return out
+
+
 def predict_ace_batch(fits, newXs=None, newZs=None, marginal=False,
                       return_average_treatments=False, normalize=True):
     """predict_ace of M fits of small models (n <= 512 each, one kernel, p and

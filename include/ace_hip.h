@@ -431,6 +431,42 @@ int ace_model_predict_joint(ace_model *m, const double *theta, int64_t nx, const
  * ace_last_error(NULL) has the message.  n <= 32768. */
 int ace_potrf_lower(int64_t n, const double *A, int64_t lda, double jitter, double *L, int64_t ldl,
                     int64_t *info);
+/* Cross-validation from the resident inverse, without a refit.
+ * With S = A^-1 of the last para_update, the hyperparameters and mu =
+ * theta[1] held fixed, and alpha = S (y - mu 1) (formed as ace_model_predict
+ * forms its map), the held-out rows F of a fold (m of them) need only
+ * B_F = S[F, F] and alpha_F:
+ *   r_F = B_F^-1 alpha_F = y_F - E[y_F | y_-F],  C_F = B_F^-1 = Cov[y_F | y_-F]
+ *   (noise included, like ace_model_predict's var),  mahal_F = alpha_F^T r_F,
+ *   lpd_F = -1/2 mahal_F + 1/2 log det B_F - (m/2) log 2 pi - m log std_y.
+ * Folds: fold f holds the caller's rows idx[off[f] .. off[f + 1]), nf >= 1,
+ * off[0] = 0, off non-decreasing, no fold empty, every index in [0, n) and at
+ * most once per fold; folds may overlap and need not cover the data.
+ * Outputs (any may be NULL), in original units: map = mean_y + std_y (y_i -
+ * r_i), var = std_y^2 diag(C_F), resid = std_y r_i, each off[nf] long in
+ * idx's order; lpd, mahal, status one per fold.  status[f] = 0, or the
+ * 1-based index (within the fold's rows sorted by device position) of the
+ * first pivot that is <= 0 or not finite -- a numerical outcome: that fold's
+ * outputs are NaN, the other folds are unaffected and the call still returns
+ * ACE_OK.  Every output is bitwise reproducible and independent of the other
+ * folds of the call and of the order of a fold's indices.
+ * Dispatch: every fold of one row -- one pass over the diagonal; folds up to
+ * 512 rows -- one workgroup each; larger folds -- the whole-chip sweep, one
+ * after another.  The inverse is theta_{T-1}'s while mu is the caller's (Q6):
+ * what ace_model_predict uses in-sample.
+ * ACE_ERR_UNSUPPORTED: a sharded model, or no resident inverse (no
+ * para_update yet).  ACE_ERR_ARG: a malformed fold list. */
+int ace_model_cv(ace_model *m, const double *theta, int64_t nf, const int64_t *off,
+                 const int64_t *idx, double mean_y, double std_y, double *map, double *var,
+                 double *resid, double *lpd, double *mahal, int *status);
+/* The same core on host buffers: P (n x n, ldp) any symmetric matrix of which
+ * the lower triangle is read, alpha (n).  resid = B_F^-1 alpha_F and var =
+ * diag(B_F^-1) (off[nf] each, idx's order), logdet = log det B_F, mahal and
+ * status per fold; any output may be NULL.  Scratch of its own on ctx's
+ * device. */
+int ace_cv_from_inverse(ace_ctx *ctx, int64_t n, const double *P, int64_t ldp,
+                        const double *alpha, int64_t nf, const int64_t *off, const int64_t *idx,
+                        double *resid, double *var, double *logdet, double *mahal, int *status);
 /* Per-kernel device timing for the roofline report: when enabled, HIP
  * events bracket every launch of the dense update kernel (`which` = 0),
  * the assembly kernel (1) and the gradient kernel (2) on the model's
