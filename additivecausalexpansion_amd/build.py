@@ -18,7 +18,7 @@ SOURCES = ["csrc/ace_pairs.hip", "csrc/ace_pairs_mm.hip", "csrc/ace_sweep.hip", 
            "csrc/ace_sweep_plan.cpp", "csrc/ace_cv.hip", "csrc/ace_cv.cpp", "csrc/ace_cv_plan.cpp"]
 HEADERS = ["csrc/ace_internal.h", "csrc/ace_common.h", "csrc/ace_model.h", "csrc/ace_batch.h",
            "csrc/ace_formulas.h", "csrc/ace_wgtime.h", "csrc/ace_sweep_plan.h", "csrc/ace_retry.h",
-           "csrc/ace_cv.h", "csrc/ace_cv_plan.h",
+           "csrc/ace_cv.h", "csrc/ace_cv_plan.h", "csrc/ace_wg_geom.h",
            "../include/ace_hip.h"]
 OUT = os.path.join(HERE, "libace_hip.so")
 OBJDIR = os.path.join(HERE, "build")

@@ -190,14 +190,14 @@ int ace_batch_create(ace_ctx *ctx, int kind, int64_t M, int64_t nmax, int p, int
     }
     const Shape &s = b->s;
     b->s.PM = batch_pm_bucket(p < 1 ? 1 : p);
-    if (batch_lds_bytes((int)nmax, s.B, s.PM) > 160 * 1024) {
+    if (batch_lds_bytes((int)nmax, s.B, s.PM) > LDS_MAX) {
       ctx->err = "unsupported shape: the theta tables do not fit one workgroup's LDS";
       throw Fail{ACE_ERR_UNSUPPORTED};
     }
     b->P = 2 + s.B * (s.p + 1);
     b->M = M;
     b->nmax = nmax;
-    b->ld = batch_rows((int)nmax);
+    b->ld = wg_rows((int)nmax);
     b->ldo = b->P + 4;
     b->n.assign((size_t)M, 0);
     b->std_y.assign((size_t)M, 1.0);

@@ -5,22 +5,16 @@
 #include <stdint.h>
 
 #include "ace_formulas.h"
+#include "ace_wg_geom.h"
 
 namespace ace {
 
-constexpr int BATCH_NMAX = 512;  // rows of the largest model one workgroup takes
-constexpr int BT = 16;           // pivot block = MFMA fragment width
+constexpr int BATCH_NMAX = WG_NMAX;  // rows of the largest model one workgroup takes
 
 // Feature-count buckets of k_batch_eval (its own, coarser than pm_bucket's).
 int batch_pm_bucket(int p);
-// rows (= leading dimension) of a model's scratch matrix: n padded to BT,
-// plus one BT block whose first two rows carry the right-hand sides y and 1
-__host__ __device__ constexpr int batch_rows(int n) { return (n + BT - 1) / BT * BT + BT; }
-// LDS pitch of a pivot panel (16 mod 32 doubles: the two 16-lane groups of a
-// half wave read different banks)
-__host__ __device__ constexpr int batch_pitch(int nmax) {
-  return batch_rows(nmax) % 32 == 16 ? batch_rows(nmax) : batch_rows(nmax) + 16;
-}
+// A model's scratch matrix has wg_rows(nmax) rows (= leading dimension); the
+// first two rows of its last block carry the right-hand sides y and 1.
 // threads of the batch kernels: eight waves where the per-lane feature arrays leave
 // room for them (two waves per SIMD hide the scratch matrix's latency), four above
 __host__ __device__ constexpr int batch_threads(int PM) { return PM <= 16 ? 512 : 256; }

@@ -26,30 +26,25 @@
 //   W = P D^-1;  A[i, j] -= W_i P_j^T for i, j outside K  (v_mfma_f64_16x16x4_f64,
 //   W and P staged in LDS);  A[:, K] = W;  A[K, K] = N.
 // After the last block the n x n part holds -A^-1 (lower), the two rows under
-// it (A^-1 [y, 1])^T and their corner -[y, 1]^T A^-1 [y, 1].
+// it (A^-1 [y, 1])^T and their corner -[y, 1]^T A^-1 [y, 1].  k_cv_fold
+// (ace_cv.hip) holds the same loop with one statement changed (it records the
+// first bad pivot's index): a correction to either belongs in both.  Their
+// geometry and LDS map are stated once, in ace_wg_geom.h.
 #include "../../include/ace_hip.h"
 #include "ace_batch.h"
 #include "ace_internal.h"
 
 namespace ace {
 
-namespace {
-
-constexpr int DP = BT + 1;  // pitch of the pivot block in LDS
-
-// LDS map (doubles).  Fixed head: scal[16], the pivot block D[2][BT][DP].
-// Behind it one region used twice: by the sweep as the panels P and W
-// (BT x pitch each, k-major), before and after it as the theta tables
-// (wk | wg | lam | e^theta0), alpha, the gradient sums and a reduction pad.
-constexpr int L_SCAL = 0, L_D = 16, L_REG = L_D + 2 * BT * DP;
-
-}  // namespace
-
+// LDS: the sweep's map (ace_wg_geom.h).  The region behind its fixed head is
+// used twice: by the sweep as the panels P and W, before and after it as the
+// theta tables (wk | wg | lam | e^theta0), alpha, the gradient sums and a
+// reduction pad.
 size_t batch_lds_bytes(int nmax, int B, int PM) {
-  const size_t panels = 2 * (size_t)BT * batch_pitch(nmax);
+  const size_t sweep = (size_t)wg_sweep_lds_bytes(nmax);
   const size_t rest = (size_t)(2 * B * PM + B + 1) + (size_t)nmax + (size_t)(B * (PM + 1) + 1) +
                       (size_t)(batch_threads(PM) / 64) * (PM + 1) + 8;
-  return (L_REG + (panels > rest ? panels : rest)) * sizeof(double);
+  return std::max(sweep, (WG_L_REG + rest) * sizeof(double));
 }
 
 template <int KIND, int PM>
@@ -67,7 +62,7 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
   const int n = a.n[j], B = a.B, p = a.p, ZS = a.ZS;
   const int npad = (n + BT - 1) / BT * BT, Nt = npad + BT, nt = Nt / BT;
   const int64_t ld = a.ld;
-  const int pitch = batch_pitch(a.nmax);
+  const int pitch = wg_pitch(a.nmax);
   const double *__restrict__ X = a.X + (int64_t)j * a.nmax * PM;
   const double *__restrict__ Z = a.Z + (int64_t)j * a.nmax * ZS;
   const double *__restrict__ LZ = a.LZ + (int64_t)j * a.nmax * ZS;
@@ -76,7 +71,7 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
   double *A = a.A + (int64_t)j * ld * ld;
   double *out = a.out + (int64_t)j * a.ldo;
 
-  double *sScal = lds + L_SCAL, *sD = lds + L_D, *reg = lds + L_REG;
+  double *sScal = lds + WG_L_SCAL, *sD = lds + WG_L_D, *reg = lds + WG_L_REG;
   double *sP = reg, *sW = reg + BT * pitch;
   const int nk = B * PM;
   double *sWk = reg, *sWg = reg + nk, *sLam = reg + 2 * nk;  // e^theta0 at sLam[B]
@@ -173,11 +168,11 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
     }
 #pragma unroll 1
     for (int s = 0; s < BT; ++s) {
-      double *buf = sD + (s & 1) * BT * DP;
-      if (dth && (da == s || db == s)) buf[da * DP + db] = d;
+      double *buf = sD + (s & 1) * BT * WG_DP;
+      if (dth && (da == s || db == s)) buf[da * WG_DP + db] = d;
       __syncthreads();
-      const double piv = buf[s * DP + s];
-      const double das = buf[da * DP + s], dsb = buf[s * DP + db];
+      const double piv = buf[s * WG_DP + s];
+      const double das = buf[da * WG_DP + s], dsb = buf[s * WG_DP + db];
       const double rp = 1.0 / piv;
       if (tid == 0) {
         logdet += log(piv);
@@ -189,7 +184,7 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
       else d = d - (das * dsb) * rp;
     }
     __syncthreads();
-    if (dth) sD[da * DP + db] = d;  // N = -D^-1
+    if (dth) sD[da * WG_DP + db] = d;  // N = -D^-1
     if (dth && da >= db) A[(k0 + da) + (int64_t)(k0 + db) * ld] = d;
     __syncthreads();
     // W = P D^-1 = -P N: to A's column block (and its mirror), -W to LDS
@@ -209,7 +204,7 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_eval(BatchView a) {
       for (int k = 0; k < BT; ++k) {
         double s = 0.0;
 #pragma unroll
-        for (int l = 0; l < BT; ++l) s = fma(pr[l], sD[l * DP + k], s);
+        for (int l = 0; l < BT; ++l) s = fma(pr[l], sD[l * WG_DP + k], s);
         sW[k * pitch + i] = s;  // -W
         if (i > k0) A[i + (int64_t)(k0 + k) * ld] = -s;
         else A[(k0 + k) + (int64_t)i * ld] = -s;
@@ -460,21 +455,13 @@ int batch_pm_bucket(int p) {
 
 template <int KIND, int PM>
 static hipError_t eval_pm(const BatchView &v, hipStream_t st) {
-  const size_t lds = batch_lds_bytes(v.nmax, v.B, PM);
-  static size_t set = 0;  // the attribute holds the largest size asked for so far
-  if (lds > 64 * 1024 && lds > set) {
-    const hipError_t e = hipFuncSetAttribute((const void *)k_batch_eval<KIND, PM>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    set = lds;
-  }
-  hipLaunchKernelGGL((k_batch_eval<KIND, PM>), dim3((unsigned)v.M), dim3(batch_threads(PM)), lds, st, v);
-  return hipGetLastError();
+  return launch_lds(k_batch_eval<KIND, PM>, dim3((unsigned)v.M), dim3(batch_threads(PM)),
+                    batch_lds_bytes(v.nmax, v.B, PM), st, v);
 }
 
 hipError_t launch_batch_eval(int kind, const BatchView &v, hipStream_t st) {
   if (v.M <= 0) return hipSuccess;
-  if (v.nmax > BATCH_NMAX || batch_lds_bytes(v.nmax, v.B, v.PM) > 160 * 1024)
+  if (v.nmax > BATCH_NMAX || batch_lds_bytes(v.nmax, v.B, v.PM) > LDS_MAX)
     return hipErrorInvalidValue;
   switch (v.PM) {
 #define ACE_CASE(Q) \

@@ -313,22 +313,13 @@ __global__ __launch_bounds__(batch_threads(PM)) void k_batch_predict(BatchPredVi
 
 template <int KIND, int PM>
 static hipError_t predict_pm(const BatchPredView &v, hipStream_t st) {
-  const size_t lds = batch_predict_lds_bytes(v.nmax, v.B, PM);
-  static size_t set = 0;  // the attribute holds the largest size asked for so far
-  if (lds > 64 * 1024 && lds > set) {
-    const hipError_t e = hipFuncSetAttribute((const void *)k_batch_predict<KIND, PM>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    set = lds;
-  }
-  hipLaunchKernelGGL((k_batch_predict<KIND, PM>), dim3((unsigned)v.M), dim3(batch_threads(PM)), lds,
-                     st, v);
-  return hipGetLastError();
+  return launch_lds(k_batch_predict<KIND, PM>, dim3((unsigned)v.M), dim3(batch_threads(PM)),
+                    batch_predict_lds_bytes(v.nmax, v.B, PM), st, v);
 }
 
 hipError_t launch_batch_predict(int kind, const BatchPredView &v, hipStream_t st) {
   if (v.M <= 0) return hipSuccess;
-  if (v.nmax > BATCH_NMAX || batch_predict_lds_bytes(v.nmax, v.B, v.PM) > 160 * 1024)
+  if (v.nmax > BATCH_NMAX || batch_predict_lds_bytes(v.nmax, v.B, v.PM) > LDS_MAX)
     return hipErrorInvalidValue;
   switch (v.PM) {
 #define ACE_CASE(Q) \

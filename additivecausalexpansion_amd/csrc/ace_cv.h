@@ -36,7 +36,7 @@ struct CvRes {
 // Fold desc[j], j < nd, into its working matrix: +S[F, F] in the leading
 // m x m block, unit diagonal on the padding, alpha_F in row npad of the
 // columns k < m, zeros in the rest of the right-hand-side block.
-// npad_sweep == 0: the workgroup layout (npad = ld - CV_BT); the lower
+// npad_sweep == 0: the workgroup layout (npad = ld - BT); the lower
 // triangle alone is written and k_cv_fold reads through it.  npad_sweep > 0:
 // a SweepWork's A (ld = naug): both triangles of the npad x npad block from
 // the same source element (exactly symmetric) and every AUG row; af

@@ -23,29 +23,44 @@
 // not leave the loop (every barrier is reached); the fold's outputs are
 // overwritten with NaN at the end.
 //
-// The sweep is the one of ace_batch.hip at a block width of one MFMA
-// fragment: for pivot block K (16 indices)
+// The sweep is the one of k_batch_eval (ace_batch.hip) at a block width of one
+// MFMA fragment: for pivot block K (16 indices)
 //   P = A[:, K] (all rows, read through the lower triangle), D = A[K, K],
 //   N = sweep(D) = -D^-1 (16 scalar steps through LDS),
 //   W = P D^-1;  A[i, j] -= W_i P_j^T outside K (v_mfma_f64_16x16x4_f64, W and
 //   P staged in LDS);  A[:, K] = W;  A[K, K] = N.
-#include "ace_batch.h"
+// The loop is k_batch_eval's with one statement changed (the first bad
+// pivot's index is recorded, not a flag): a correction to either belongs in
+// both.  The working matrix's rows, the LDS map and its size are
+// ace_wg_geom.h's, as the plan (ace_cv_plan.cpp) and the batched engine use
+// them.
 #include "ace_cv.h"
-#include "ace_formulas.h"
+#include "ace_internal.h"
 
 namespace ace {
 
-static_assert(CV_BT == BT && CV_WG_MAX == BATCH_NMAX, "the batched engine's blocking");
-static_assert(cv_rows(1) == batch_rows(1) && cv_rows(500) == batch_rows(500) &&
-                  cv_pitch(17) == batch_pitch(17) && cv_pitch(CV_WG_MAX) == batch_pitch(BATCH_NMAX),
-              "ace_cv_plan.h restates batch_rows / batch_pitch");
-
 namespace {
 
-constexpr int DP = BT + 1;           // pitch of the pivot block in LDS
-constexpr int FOLD_THREADS = 512;    // eight waves
-constexpr int L_SCAL = 0, L_D = 16, L_REG = L_D + 2 * BT * DP;
-static_assert(L_REG == CV_LDS_HEAD, "ace_cv_plan.h's LDS head");
+constexpr int FOLD_THREADS = 512;  // eight waves
+
+// One swept fold's outputs, by every thread of its NTHR-thread workgroup: A
+// (ld) holds -B_F^-1 in its leading block, B_F^-1 alpha_F in row npad and the
+// corner -alpha_F^T B_F^-1 alpha_F.  status != 0: NaN in their place.
+template <int NTHR>
+__device__ __forceinline__ void fold_out(const double *A, int64_t ld, int64_t npad, const CvDesc &d,
+                                         const CvRes &res, double logdet, int status) {
+  const double kNaN = __builtin_nan("");
+  const bool fail = status != 0;
+  for (int64_t k = threadIdx.x; k < d.m; k += NTHR) {
+    res.r[d.off + k] = fail ? kNaN : A[npad + k * ld];
+    res.v[d.off + k] = fail ? kNaN : -A[k + k * ld];
+  }
+  if (threadIdx.x == 0) {
+    res.logdet[d.fold] = fail ? kNaN : logdet;
+    res.mahal[d.fold] = fail ? kNaN : -A[npad + npad * ld];
+    res.status[d.fold] = status;
+  }
+}
 
 }  // namespace
 
@@ -100,11 +115,11 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_cv_fold(const CvDesc *__restri
   const CvDesc dsc = desc[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int m = (int)dsc.m, Nt = (int)dsc.ld, npad = Nt - BT, nt = Nt / BT;
+  const int Nt = (int)dsc.ld, npad = Nt - BT, nt = Nt / BT;
   const int64_t ld = dsc.ld;
   double *A = Wm + dsc.scratch;
-  double *sScal = lds + L_SCAL, *sD = lds + L_D;
-  double *sP = lds + L_REG, *sW = sP + BT * pitch;
+  double *sScal = lds + WG_L_SCAL, *sD = lds + WG_L_D;
+  double *sP = lds + WG_L_REG, *sW = sP + BT * pitch;
 
   const int lr = lane & 15, lk = lane >> 4;
   // this thread's element of the pivot block (the first 256 threads hold one)
@@ -131,11 +146,11 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_cv_fold(const CvDesc *__restri
     }
 #pragma unroll 1
     for (int s = 0; s < BT; ++s) {
-      double *buf = sD + (s & 1) * BT * DP;
-      if (dth && (da == s || db == s)) buf[da * DP + db] = d;
+      double *buf = sD + (s & 1) * BT * WG_DP;
+      if (dth && (da == s || db == s)) buf[da * WG_DP + db] = d;
       __syncthreads();
-      const double piv = buf[s * DP + s];
-      const double das = buf[da * DP + s], dsb = buf[s * DP + db];
+      const double piv = buf[s * WG_DP + s];
+      const double das = buf[da * WG_DP + s], dsb = buf[s * WG_DP + db];
       const double rp = 1.0 / piv;
       if (tid == 0) {
         logdet += log(piv);
@@ -147,7 +162,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_cv_fold(const CvDesc *__restri
       else d = d - (das * dsb) * rp;
     }
     __syncthreads();
-    if (dth) sD[da * DP + db] = d;  // N = -D^-1
+    if (dth) sD[da * WG_DP + db] = d;  // N = -D^-1
     if (dth && da >= db) A[(k0 + da) + (int64_t)(k0 + db) * ld] = d;
     __syncthreads();
     // W = P D^-1 = -P N: to A's column block (and its mirror), -W to LDS
@@ -167,7 +182,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_cv_fold(const CvDesc *__restri
       for (int k = 0; k < BT; ++k) {
         double s = 0.0;
 #pragma unroll
-        for (int l = 0; l < BT; ++l) s = fma(pr[l], sD[l * DP + k], s);
+        for (int l = 0; l < BT; ++l) s = fma(pr[l], sD[l * WG_DP + k], s);
         sW[k * pitch + i] = s;  // -W
         if (i > k0) A[i + (int64_t)(k0 + k) * ld] = -s;
         else A[(k0 + k) + (int64_t)i * ld] = -s;
@@ -231,33 +246,17 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_cv_fold(const CvDesc *__restri
     sScal[1] = (double)bad;
   }
   __syncthreads();
-  const double kNaN = __builtin_nan("");
-  const bool fail = sScal[1] != 0.0;
-  for (int k = tid; k < m; k += NTHR) {
-    res.r[dsc.off + k] = fail ? kNaN : A[npad + (int64_t)k * ld];
-    res.v[dsc.off + k] = fail ? kNaN : -A[k + (int64_t)k * ld];
-  }
-  if (tid == 0) {
-    res.logdet[dsc.fold] = fail ? kNaN : sScal[0];
-    res.mahal[dsc.fold] = fail ? kNaN : -A[npad + (int64_t)npad * ld];
-    res.status[dsc.fold] = (int)sScal[1];
-  }
+  fold_out<NTHR>(A, ld, npad, dsc, res, sScal[0], (int)sScal[1]);
 }
 
 hipError_t launch_cv_fold(const CvDesc *desc, int64_t nd, int64_t mmax, double *W, CvRes res,
                           hipStream_t st) {
   if (nd <= 0) return hipSuccess;
   if (mmax < 1 || mmax > CV_WG_MAX || nd > 2147483647LL) return hipErrorInvalidValue;
-  const size_t lds = (size_t)cv_lds_bytes(mmax);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void *)k_cv_fold,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k_cv_fold, dim3((unsigned)nd), dim3(FOLD_THREADS), lds, st, desc, W, res,
-                     (int)cv_pitch(mmax));
-  return hipGetLastError();
+  const size_t lds = (size_t)wg_sweep_lds_bytes(mmax);
+  if (lds > LDS_MAX) return hipErrorInvalidValue;
+  return launch_lds(k_cv_fold, dim3((unsigned)nd), dim3(FOLD_THREADS), lds, st, desc, W, res,
+                    (int)wg_pitch(mmax));
 }
 
 // ---------------------------------------------------------------------------
@@ -308,18 +307,7 @@ __global__ __launch_bounds__(256) void k_cv_sweep_out(const double *__restrict__
     if (b != 0 && (first == 0 || b < first)) first = b;
   }
   const int fl = *flag;
-  const int status = first != 0 ? first : (fl != 0 ? -fl : 0);
-  const bool fail = status != 0;
-  const double kNaN = __builtin_nan("");
-  for (int64_t k = tid; k < d.m; k += 256) {
-    res.r[d.off + k] = fail ? kNaN : A[npad + k * ld];
-    res.v[d.off + k] = fail ? kNaN : -A[k + k * ld];
-  }
-  if (tid == 0) {
-    res.logdet[d.fold] = fail ? kNaN : ls;
-    res.mahal[d.fold] = fail ? kNaN : -A[npad + npad * ld];
-    res.status[d.fold] = status;
-  }
+  fold_out<256>(A, ld, npad, d, res, ls, first != 0 ? first : (fl != 0 ? -fl : 0));
 }
 
 hipError_t launch_cv_sweep_out(const double *A, int64_t ld, int64_t npad, const double *piv,

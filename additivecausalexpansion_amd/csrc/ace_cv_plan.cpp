@@ -65,8 +65,8 @@ std::string cv_plan(int64_t n, int64_t nf, const int64_t *off, const int64_t *id
       c.cls = CV_LOO;
     } else if (c.m <= wg_max) {
       c.cls = CV_WG;
-      c.mpad = (c.m + CV_BT - 1) / CV_BT * CV_BT;
-      c.ld = cv_rows(c.m);
+      c.mpad = (c.m + BT - 1) / BT * BT;
+      c.ld = wg_rows(c.m);
       c.scratch = p.wg_doubles;
       p.wg_doubles += c.ld * c.ld;
       p.wg_mmax = std::max(p.wg_mmax, c.m);
@@ -76,7 +76,7 @@ std::string cv_plan(int64_t n, int64_t nf, const int64_t *off, const int64_t *id
       p.sweep.push_back(f);
     }
   }
-  p.lds_bytes = p.wg.empty() ? 0 : cv_lds_bytes(p.wg_mmax);
+  p.lds_bytes = p.wg.empty() ? 0 : wg_sweep_lds_bytes(p.wg_mmax);
   return "";
 }
 

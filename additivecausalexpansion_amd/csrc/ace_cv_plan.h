@@ -9,26 +9,17 @@
 #include <string>
 #include <vector>
 
+#include "ace_wg_geom.h"
+
 namespace ace {
 
-// largest fold one workgroup takes (k_cv_fold): the batched engine's bound
-constexpr int CV_WG_MAX = 512;
-constexpr int CV_BT = 16;  // pivot block = MFMA fragment width (ace_batch.h's BT)
+// largest fold one workgroup takes (k_cv_fold): the workgroup sweep's bound
+constexpr int CV_WG_MAX = WG_NMAX;
 
-// A workgroup fold's working matrix: m padded to CV_BT plus one CV_BT block
-// whose first row carries the right-hand side alpha_F; column-major, ld = rows
-// (batch_rows / batch_pitch of ace_batch.h, restated without the HIP header;
-// ace_cv.hip asserts they agree).
-constexpr int64_t cv_rows(int64_t m) { return (m + CV_BT - 1) / CV_BT * CV_BT + CV_BT; }
-constexpr int64_t cv_pitch(int64_t mmax) {
-  return cv_rows(mmax) % 32 == 16 ? cv_rows(mmax) : cv_rows(mmax) + 16;
-}
-// dynamic LDS of k_cv_fold in doubles: scalars, the pivot block twice, and
-// the panels P and W (CV_BT x pitch each)
-constexpr int64_t CV_LDS_HEAD = 16 + 2 * CV_BT * (CV_BT + 1);
-constexpr int64_t cv_lds_bytes(int64_t mmax) {
-  return (CV_LDS_HEAD + 2 * CV_BT * cv_pitch(mmax)) * (int64_t)sizeof(double);
-}
+// A workgroup fold's working matrix: m padded to BT plus one BT block whose
+// first row carries the right-hand side alpha_F; column-major, ld = rows =
+// wg_rows(m).  k_cv_fold's dynamic LDS is the sweep's, wg_sweep_lds_bytes of
+// the call's largest m.
 
 enum CvClass : int {
   CV_LOO = 0,    // every fold of the call has one row: elementwise (k_cv_loo)
@@ -40,8 +31,8 @@ struct CvFold {
   int64_t off = 0;      // first entry in rows / scatter (the caller's off[f])
   int64_t m = 0;        // rows held out
   int cls = CV_WG;
-  int64_t mpad = 0;     // CV_WG: m padded to CV_BT
-  int64_t ld = 0;       // CV_WG: cv_rows(m)
+  int64_t mpad = 0;     // CV_WG: m padded to BT
+  int64_t ld = 0;       // CV_WG: wg_rows(m)
   int64_t scratch = 0;  // CV_WG: first double of the fold's working matrix
 };
 

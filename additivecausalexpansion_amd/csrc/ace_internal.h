@@ -1,6 +1,6 @@
 // ace_internal.h -- shared declarations between the HIP kernel sources
 // (ace_pairs*.hip, ace_sweep.hip, ace_util.hip, ace_symm.hip, ace_joint.hip,
-// ace_train.hip) and the host orchestration (ace_api.cpp, ace_shard.cpp,
+// ace_train.hip, ace_batch*.hip, ace_cv.hip) and the host orchestration (ace_api.cpp, ace_shard.cpp,
 // ace_predict.cpp, ace_dmat.cpp).  The sweep's host-only planning is
 // ace_sweep_plan.h.
 #pragma once
@@ -11,8 +11,25 @@
 
 #include "ace_formulas.h"
 #include "ace_sweep_plan.h"
+#include "ace_wg_geom.h"
 
 namespace ace {
+
+// One launch with `lds` bytes of dynamic LDS (up to LDS_MAX; a shape whose
+// request can exceed it is refused by its launcher).  Above LDS_DEFAULT a
+// kernel has to be allowed the size first: the attribute is set at every such
+// launch, with no record kept, so it holds on whichever device is current.
+template <class... P, class... A>
+hipError_t launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                      A... args) {
+  if (lds > LDS_DEFAULT) {
+    const hipError_t e = hipFuncSetAttribute((const void *)kernel,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+  return hipGetLastError();
+}
 
 // Environment switches (ACE_*): the integer value of `name`, dflt when unset.
 // Every switch is read once per process, as

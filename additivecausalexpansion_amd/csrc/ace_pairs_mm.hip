@@ -1361,7 +1361,6 @@ constexpr size_t group_mm_lds(int PM, int B, int kind) {
 // once they pass 40 KB, so its total is not monotone in B.  The maxima, all
 // SE at PM = 64 and B = 32: assembly 115712 B, gradient 127936 B, cross
 // 148992 B, grouped sums 149248 B.
-constexpr size_t LDS_MAX = 160 * 1024;
 constexpr bool mm_lds_fits() {
   for (int PM : PM_BUCKETS)
     for (int B = 1; B <= BMAX; ++B)
@@ -1390,20 +1389,6 @@ static hipError_t with_pm(int PM, F &&f) {
 template <class F>
 static hipError_t with_kind(int kind, F &&f) {
   return kind == 0 ? f(std::integral_constant<int, 0>{}) : f(std::integral_constant<int, 1>{});
-}
-
-// One launch with `lds` bytes of dynamic LDS (above 64 KB a kernel has to be
-// allowed it first)
-template <class... P, class... A>
-static hipError_t launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds,
-                             hipStream_t st, A... args) {
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute((const void *)kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
-  return hipGetLastError();
 }
 
 template <int PM, int KIND, bool PS, bool DG>

@@ -557,17 +557,11 @@ static hipError_t coef_gram_launch(const double *Kc, int64_t ldk, const double *
                                    const double *D, double *part, hipStream_t st) {
   constexpr int BP = 16 * NBK;
   const size_t lds = (size_t)(BP * GKP + GC * BP * GWP + 2 * GQ) * sizeof(double);
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute((const void *)k_coef_gram<TRI, NBK>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
   int np = 0;
   const int64_t qs = coef_gram_split(n, &np);
   const dim3 grid((unsigned)((ncx + GC - 1) / GC), (unsigned)np);
-  hipLaunchKernelGGL((k_coef_gram<TRI, NBK>), grid, dim3(256), lds, st, Kc, ldk, W, ldw, n, ncx, B,
-                     qs, vec, D, part, ncx * B * (B + 1));
-  return hipGetLastError();
+  return launch_lds(k_coef_gram<TRI, NBK>, grid, dim3(256), lds, st, Kc, ldk, W, ldw, n, ncx, B, qs,
+                    vec, D, part, ncx * B * (B + 1));
 }
 
 hipError_t launch_coef_gram(bool tri, const double *Kc, int64_t ldk, const double *W, int64_t ldw,

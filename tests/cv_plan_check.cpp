@@ -92,12 +92,12 @@ int main() {
     CHECK(p.wg.size() == 4 && p.sweep.size() == 1 && p.sweep[0] == 2 && p.wg_mmax == 512);
     CHECK(p.folds[0].ld == 32 && p.folds[1].ld == 528 && p.folds[3].ld == 32 && p.folds[4].ld == 48);
     CHECK(p.folds[1].mpad == 512 && p.folds[4].mpad == 32);
-    CHECK(p.lds_bytes == cv_lds_bytes(512) && p.lds_bytes <= 160 * 1024);
+    CHECK(p.lds_bytes == wg_sweep_lds_bytes(512) && p.lds_bytes <= LDS_MAX);
     // scratch: disjoint, in order, ld^2 each
     int64_t end = 0;
     for (const int64_t f : p.wg) {
       const CvFold &c = p.folds[(size_t)f];
-      CHECK(c.scratch == end && c.ld == cv_rows(c.m));
+      CHECK(c.scratch == end && c.ld == wg_rows(c.m));
       end = c.scratch + c.ld * c.ld;
     }
     CHECK(end == p.wg_doubles);
@@ -122,7 +122,7 @@ int main() {
     CHECK(p.folds[0].cls == CV_WG && p.wg.size() == 3);
   }
   // the pitch keeps the two 16-lane groups of a half wave on different banks
-  for (int64_t m = 1; m <= 512; ++m) CHECK(cv_pitch(m) % 32 == 16 && cv_pitch(m) >= cv_rows(m));
+  for (int64_t m = 1; m <= 512; ++m) CHECK(wg_pitch(m) % 32 == 16 && wg_pitch(m) >= wg_rows(m));
 
   if (fails) {
     std::printf("cv_plan_check: %d FAILED\n", fails);

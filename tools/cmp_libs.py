@@ -10,7 +10,8 @@ tile kernels; n = 700 is the shape the tests use), or formulas: every output
 of every entry point that evaluates a formula of csrc/ace_formulas.h (fused
 para_update / train_stats, the device training loop under each optimizer with
 the clip firing and off, host-buffer and handle grad / stats, the batched
-para_update / train / predict / predict_marginal with ATE), both kernels,
+para_update / train / predict / predict_marginal with ATE, and one ragged batch of n = 16,
+17, 33 and 512), both kernels,
 compared bit for bit per output at fixed small shapes (n and kernel are not
 read), or predict: in the same style, every output of the prediction host
 paths (csrc/ace_predict.cpp) and of the handle path's pred_cpp /
@@ -18,7 +19,10 @@ pred_marginal_cpp, both kernels at n = 333, p = 2, B = 3 and n = 700, p = 20,
 B = 10 with 257 test points (8269 for the two-chunk cases), one simulated
 sharded model, and the coefficient paths once more in a process with
 ACE_COEF_CHUNK=7; run it as is and with ACE_PRED_TRI=0 in the environment
-(both builds then take the full symmetric product)."""
+(both builds then take the full symmetric product), or cv: every output array
+of DeviceModel.cv, status included, both kernels, one fitted model at n = 700,
+p = 2, B = 3: one call with folds of 1, 15, 16, 17, 33, 64, 100 and 512 rows,
+an all-one-row call, and the first call again with ACE_CV_WG_MAX=16."""
 import os
 import subprocess
 import sys
@@ -173,6 +177,51 @@ def run():
                 put(tag + "/train/" + opt + "/clip" + str(int(clip)), T, stats, iters, conv, status,
                     *[bm.inverse(j) for j in range(3)])
                 bm.close()
+        # one ragged batch over the workgroup sweep's block edges and its row limit
+        nr = (16, 17, 33, 512)
+        probs = [problem(n, 3, 4, 30 + j) for j, n in enumerate(nr)]
+        bm = BatchModel(kernel, len(nr), max(nr), 3, 4)
+        for j, q in enumerate(probs):
+            bm.set_data(j, q[0], q[1], q[2], q[4])
+        T = np.asfortranarray(np.column_stack([q[3] for q in probs]))
+        for it in (1, 2):
+            g, st, mu = bm.para_update(it, T)
+            put(kernel + "/batch/ragged/it" + str(it), g, st, mu, T)
+            T = np.asfortranarray(T + 0.01 * g / max(1.0, float(np.abs(g).max())))
+        put(kernel + "/batch/ragged/inverse", *[bm.inverse(j) for j in range(len(nr))])
+        bm.close()
+run()
+np.savez({out!r}, **out)
+"""
+# Cross-validation from the resident inverse (csrc/ace_cv.hip): one fitted
+# model per kernel; folds on the workgroup sweep's block edges, at an odd tile
+# count (where its 2 x 2 turn clamps) and at 512 rows (LDS above 64 KB); the
+# elementwise class; and the first call again with every fold above 16 rows
+# sent through the whole-chip sweep.
+SNIP_CV = """
+import os, sys, numpy as np
+sys.path.insert(0, {root!r})
+import additivecausalexpansion_amd as A
+from additivecausalexpansion_amd.synthetic import make_problem
+out = {{}}
+def run():
+    n, p, B = 700, 2, 3
+    rng = np.random.default_rng(11)
+    folds = [np.sort(rng.permutation(n)[:m]) for m in (1, 15, 16, 17, 33, 64, 100, 512)]
+    for kernel in ("SE", "Matern32"):
+        y, X, Z, th, sy = make_problem(n, p, B, seed=5)
+        m = A.DeviceModel(kernel, n, p, B)
+        m.set_data(y, X, Z, sy)
+        m.para_update(2, th.copy())
+        def put(name, res):
+            for k in sorted(res):
+                out[kernel + "/" + name + "/" + k] = np.ravel(np.asarray(res[k]))
+        put("folds", m.cv(th, folds, 0.3, sy))
+        put("loo", m.cv(th, [np.array([i]) for i in range(n)], 0.3, sy))
+        os.environ["ACE_CV_WG_MAX"] = "16"  # read per call
+        put("folds_wg16", m.cv(th, folds, 0.3, sy))
+        del os.environ["ACE_CV_WG_MAX"]
+        m.close()
 run()
 np.savez({out!r}, **out)
 """
@@ -267,15 +316,15 @@ run()
 np.savez({out!r}, **out)
 """
 SNIPS = {"para_update": SNIP, "cross": SNIP_CROSS, "formulas": SNIP_FORMULAS,
-         "predict": SNIP_PREDICT}
+         "predict": SNIP_PREDICT, "cv": SNIP_CV}
 # the processes each build runs in for a mode: (extra environment, ...)
 PARTS = {"predict": ({"CMP_PART": "all"}, {"CMP_PART": "coef7", "ACE_COEF_CHUNK": "7"})}
-NAMED = ("formulas", "predict")  # named outputs in an npz, a verdict per output
+NAMED = ("formulas", "predict", "cv")  # named outputs in an npz, a verdict per output
 
 
 def bits_equal(a, b):
     """Equal bit for bit (a NaN equals only the same NaN)."""
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def main():
