@@ -111,6 +111,14 @@ SIGNATURES = {
     "ace_model_predict_surface": (ctypes.c_int, [_vp, _D, _I64, _D, _I64, _D, ctypes.c_int,
                                                  ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                                  _D, _D, _D]),
+    "ace_model_coef_groups": (ctypes.c_int, [_vp, _D, _I64, _D, ctypes.c_int, _I32, _D, _D,
+                                             _I64P]),
+    "ace_coef_group_contract": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _I64, _D, _D, _I64P, _D,
+                                               ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                               _D, _D, _D, _D]),
+    "ace_model_average_response": (ctypes.c_int, [_vp, _D, _I64, _D, ctypes.c_int, _I32, _I64, _D,
+                                                  ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                                  ctypes.c_double, _D, _D, _D, _D]),
     "ace_model_predict_joint": (ctypes.c_int, [_vp, _D, _I64, _D, _D, ctypes.c_int,
                                                ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                                ctypes.c_int, ctypes.c_double, _I64, _D, _D, _D, _D,

@@ -336,4 +336,49 @@ int ace_coef_contract(int64_t nx, int B, int64_t nz, const double *mean, const d
   return ACE_OK;
 }
 
+// A group-summed coefficient posterior (ace_model_coef_groups) contracted with
+// nz weight rows into group averages: ace_coef_contract's tail per (group g,
+// row j) on gmean_g / |g| and the diagonal block C_gg / |g|^2, output index
+// g + G j; cov (optional) the signed scale^2 W_j^T C_gg W_j' / |g|^2.  An
+// empty group divides 0 by 0: NaN, as marginal_averages gives it.
+int ace_coef_group_contract(int G, int B, int64_t nz, const double *gmean, const double *gcov,
+                            const int64_t *gcount, const double *W, double offset, double scale,
+                            double shift, double *map, double *ci, double *var, double *cov) {
+  if (G < 1 || nz < 1 || B < 1 || !gmean || !gcov || !gcount || !W || !map || !ci || !var)
+    return ACE_ERR_ARG;
+  const int64_t N = (int64_t)G * nz, GB = (int64_t)G * B;
+  std::vector<double> t((size_t)(nz * B));  // t[j + nz b'] = sum_b W_j[b] C_gg[b][b']
+  for (int g = 0; g < G; ++g) {
+    const double cnt = (double)gcount[g];
+    for (int64_t j = 0; j < nz; ++j)
+      for (int b2 = 0; b2 < B; ++b2) {
+        double s = 0.0;
+        for (int b = 0; b < B; ++b)
+          s += W[j + nz * b] * gcov[(g + (int64_t)G * b) + GB * (g + (int64_t)G * b2)];
+        t[(size_t)(j + nz * b2)] = s;
+      }
+    for (int64_t j = 0; j < nz; ++j) {
+      double a = 0.0, q = 0.0;
+      for (int b = 0; b < B; ++b) a += W[j + nz * b] * gmean[g + (int64_t)G * b];
+      for (int b2 = 0; b2 < B; ++b2) q += t[(size_t)(j + nz * b2)] * W[j + nz * b2];
+      const int64_t e = g + (int64_t)G * j;
+      const double yx = offset + scale * (a / cnt + shift);
+      const double sd = scale * std::sqrt(std::fabs(q)) / cnt;
+      map[e] = yx;
+      ci[e] = yx - 1.96 * sd;
+      ci[e + N] = yx + 1.96 * sd;
+      var[e] = std::pow(sd, 2);
+      if (!cov) continue;
+      for (int64_t j2 = 0; j2 <= j; ++j2) {  // the lower half, mirrored: exactly symmetric
+        double q2 = 0.0;
+        for (int b2 = 0; b2 < B; ++b2) q2 += t[(size_t)(j + nz * b2)] * W[j2 + nz * b2];
+        const double c = (scale * scale) * q2 / (cnt * cnt);
+        cov[g + (int64_t)G * (j + nz * j2)] = c;
+        cov[g + (int64_t)G * (j2 + nz * j)] = c;
+      }
+    }
+  }
+  return ACE_OK;
+}
+
 }  // extern "C"

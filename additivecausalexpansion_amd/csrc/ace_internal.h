@@ -155,6 +155,17 @@ int group_sums_parts(int64_t n);
 hipError_t launch_group_sums(int kind, int PM, PairSide S, int B, int ZS, TabView tab, int b0,
                              int b1, const int *label, int G, double *part, double *R,
                              hipStream_t st);
+// Per-slice grouped sums over two point sets (k_group_slices_mm): out (R.n x
+// (G B), ld R.n), column block b = K_b(R, C) E for every slice b < B, with
+// K_b(r, c) = k_b(x_r, x_c) beta_b(z_r) -- the row side's basis factor (1 for
+// slice 0), none on the column side, whose Z / LZ are not read -- and E the
+// indicator of the C.n labels in [-1, G), 1 <= G <= 64.  part:
+// group_slices_parts(R.n, C.n) * R.n * G * B doubles of partial sums, reduced
+// in a fixed order (bitwise reproducible, whatever ACE_GROUP_SLICES).
+int group_slices_parts(int64_t nrows, int64_t ncols);
+hipError_t launch_group_slices(int kind, int PM, PairSide R, PairSide C, int B, int ZS,
+                               TabView tab, const int *label, int G, double *part, double *out,
+                               hipStream_t st);
 hipError_t launch_grad_mm(int kind, int PM, PairSide S, int B, int ZS, TabView tab,
                           const double *A, int64_t ld, double sA, const double *alpha,
                           double *gpart, hipStream_t st, const Tile *tiles, int64_t ntiles, int G,

@@ -1795,6 +1795,198 @@ hipError_t launch_group_sums(int kind, int PM, PairSide S, int B, int ZS, TabVie
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Per-slice grouped sums over two point sets (the group-averaged coefficient
+// posterior, ace_predict.cpp): R_b = K_b(R, C) E (R.n x G) for every slice
+// b < B, slice b at column block b of the R.n x (G B) result,
+// out[row + ld (h + G b)].  k_group_mm's tile with two changes.  The column
+// side C are the labelled points and carry no basis factor: every slice's LDS
+// row is z = 1, log|z| = 0 (k_cross_slices_mm's row side; C.Z / C.LZ are not
+// read), so K_b(r, c) = k_b(x_r, x_c) beta_b(z_r) with the row side's factor
+// (1 for slice 0) and its Q7 zero rules, from cross_slice_pairs.  And the
+// slices are not summed: slice s of the pass has its own NF result fragments
+// racc[s][hb] (D register i of lane (lr, lk): R_b[16 w + lk + 4 i][16 hb + lr]),
+// carried over the workgroup's column tiles, while the tile's kf fragment is
+// zeroed and reused from slice to slice.  A pass (blockIdx.z) holds the ns <=
+// NS slices [ns z, ns z + ns); the slice loop stays rolled -- one copy of the
+// pair arithmetic -- and only GEMM2 is selected per accumulator set (wave
+// uniform).  A slice's bits depend on its own tiles alone, so not on ns.
+// Column ranges write partial results (part + js ldp G B), added in
+// ascending js by k_sum_parts.  Columns past C.n carry label -1; rows past
+// R.n are not stored.  LDS: group_mm_lds.
+// ---------------------------------------------------------------------------
+template <int PM, int KIND, int NS, int NF>
+__global__ __launch_bounds__(256, 2) void k_group_slices_mm(
+    PairSide R, PairSide C, int B, int ZS, TabView tab, int ns, const int *__restrict__ label,
+    int G, int tpw, double *__restrict__ part, int64_t ldp) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int64_t I = blockIdx.y, js = blockIdx.x;
+  const int b0 = (int)blockIdx.z * ns;
+  const int nb = (b0 + ns < B) ? ns : B - b0;
+  const int64_t nt = (C.n + AT - 1) / AT;
+  const int64_t J0 = js * tpw, J1 = (J0 + tpw < nt) ? J0 + tpw : nt;
+  const int64_t R0 = I * AT;
+  const int HB = (G + 15) / 16;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+  CROSS_LDS_POINTERS(lds, PM, B, KIND);
+  int *const Lab = (int *)(XI + 64 * xj_pitch(PM));
+  // the strip's row side, the weights, the tables and the column side's unit
+  // basis rows: staged once
+  cross_stage_x<PM, false, true>(XJ, XI, C, 0, R, R0, tid);
+  cross_stage_tab<PM, KIND>(E, Zc, LZc, W, tab, B, tid);
+  for (int e = tid; e < (B - 1) * 64; e += 256) {
+    Zc[e] = 1.0;
+    if (KIND == 0) LZc[e] = 0.0;
+  }
+  __syncthreads();
+  // the pass's slices alone: norms of slice b0 + s at Nr / Nc + (b0 + s) 64
+  cross_norms<PM, false, true>(XJ, XI, W + b0 * PM, Nc + b0 * 64, Nr + b0 * 64, nb, tid);
+  const int rl = 16 * w + lr;
+  const int64_t r = R0 + rl;
+  const bool rok = r < R.n;
+  RowX<PM> xr;
+  xr.load(XI + rl * xj_pitch(PM), lk);
+  d4 racc[NS][NF];
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int hb = 0; hb < NF; ++hb) racc[s][hb] = d4{0.0, 0.0, 0.0, 0.0};
+  for (int64_t J = J0; J < J1; ++J) {
+    const int64_t C0 = J * AT;
+    if (J > J0) __syncthreads();  // the previous tile's readers are done
+    cross_stage_x<PM, true, false>(XJ, XI, C, C0, R, 0, tid);
+    if (tid < 64) Lab[tid] = (C0 + tid < C.n) ? label[C0 + tid] : -1;
+    __syncthreads();
+    cross_norms<PM, true, false>(XJ, XI, W + b0 * PM, Nc + b0 * 64, Nr + b0 * 64, nb, tid);
+    __syncthreads();
+    int lb[4][4];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) lb[cb][v] = Lab[16 * cb + 4 * v + lk];
+#pragma unroll 1
+    for (int s = 0; s < nb; ++s) {
+      const int b = b0 + s;
+      double zr = 1.0, lzr = 0.0;  // issued ahead of GEMM1
+      if (b > 0) {
+        zr = rok ? R.Z[r * ZS + b - 1] : 0.0;
+        if (KIND == 0) lzr = rok ? R.LZ[r * ZS + b - 1] : 0.0;
+      }
+      double kf[4][4];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) kf[cb][v] = 0.0;
+      cross_slice_pairs<PM, KIND>(kf, XJ, W, Nr, Nc, Zc, LZc, E, xr, tab, b, zr, lzr, rl, lr, lk);
+      // the values are pinned here (as in k_cross_slices_mm): used only under
+      // the accumulator selects below, the pair math must not move into them
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) asm volatile("" : "+v"(kf[cb][v]));
+      // E's operands do not depend on the slice.  With one fragment the 16
+      // of them are left to be hoisted out of the slice loop (32 VGPRs); with
+      // four they would be 128 VGPRs (21 - 42 spills), so the labels are made
+      // opaque here and the selects are issued per slice.
+      int ls[4][4];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          ls[cb][v] = lb[cb][v];
+          if (NF > 1) asm volatile("" : "+v"(ls[cb][v]));
+        }
+      // GEMM2 into slice s's fragments:
+      // racc[s][hb] += K_b[rows][16 cb + 4 v + lk] E[16 cb + 4 v + lk][16 hb + lr]
+#pragma unroll
+      for (int t = 0; t < NS; ++t)
+        if (t == s) {
+#pragma unroll
+          for (int hb = 0; hb < NF; ++hb)
+            if (hb < HB) {
+              const int h = 16 * hb + lr;
+#pragma unroll
+              for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                  racc[t][hb] = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                      kf[cb][v], ls[cb][v] == h ? 1.0 : 0.0, racc[t][hb], 0, 0, 0);
+            }
+        }
+    }
+  }
+  double *const P = part + js * ldp * G * B;
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+    if (s < nb) {
+#pragma unroll
+      for (int hb = 0; hb < NF; ++hb) {
+        const int h = 16 * hb + lr;
+        if (hb < HB && h < G) {
+          double *const Pc = P + ldp * (h + (int64_t)G * (b0 + s));
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int64_t row = R0 + 16 * w + lk + 4 * i;
+            if (row < R.n) Pc[row] = racc[s][hb][i];
+          }
+        }
+      }
+    }
+}
+
+// Slices held per pass and fragments per slice of the two compiled shapes:
+// up to 16 groups one fragment and 8 slices, else four fragments and 2
+// slices -- 64 accumulator VGPRs either way, which keeps every bucket
+// without spills at 2 waves per SIMD (DESIGN §19 has the table).
+constexpr int GS_NS1 = 8, GS_NS4 = 2;
+
+// column tiles per workgroup: about 1024 workgroups over the row strips, at
+// most 64 column ranges; from the two point counts alone
+static int group_slices_tpw(int64_t nrows, int64_t ncols) {
+  const int64_t strips = (nrows + AT - 1) / AT, nt = (ncols + AT - 1) / AT;
+  const int64_t want = std::min<int64_t>((1024 + strips - 1) / strips, 64);
+  const int64_t ns = want < nt ? want : nt;
+  return (int)((nt + ns - 1) / ns);
+}
+
+int group_slices_parts(int64_t nrows, int64_t ncols) {
+  const int64_t nt = (ncols + AT - 1) / AT;
+  const int tpw = group_slices_tpw(nrows, ncols);
+  return (int)((nt + tpw - 1) / tpw);
+}
+
+hipError_t launch_group_slices(int kind, int PM, PairSide R, PairSide C, int B, int ZS,
+                               TabView tab, const int *label, int G, double *part, double *out,
+                               hipStream_t st) {
+  if (R.n <= 0 || C.n <= 0 || G < 1 || G > 64 || B < 1) return hipErrorInvalidValue;
+  const int tpw = group_slices_tpw(R.n, C.n);
+  const int nparts = group_slices_parts(R.n, C.n);
+  const bool one = G <= 16;
+  // ACE_GROUP_SLICES: slices per pass, read per call (tests), at most the
+  // compiled shape's
+  const int cap = one ? GS_NS1 : GS_NS4;
+  const int ns = std::max(1, std::min(env_int("ACE_GROUP_SLICES", cap), cap));
+  const dim3 grid((unsigned)nparts, (unsigned)((R.n + AT - 1) / AT), (unsigned)((B + ns - 1) / ns));
+  const hipError_t e = with_pm(PM, [&](auto pm) {
+    return with_kind(kind, [&](auto kd) {
+      constexpr int P = decltype(pm)::value, K = decltype(kd)::value;
+      const size_t lds = group_mm_lds(P, B, kind);
+      if (one)
+        return launch_lds(k_group_slices_mm<P, K, GS_NS1, 1>, grid, dim3(256), lds, st, R, C, B, ZS,
+                          tab, ns, label, G, tpw, part, R.n);
+      return launch_lds(k_group_slices_mm<P, K, GS_NS4, 4>, grid, dim3(256), lds, st, R, C, B, ZS,
+                        tab, ns, label, G, tpw, part, R.n);
+    });
+  });
+  if (e != hipSuccess) return e;
+  const int64_t count = R.n * G * B;
+  hipLaunchKernelGGL(k_sum_parts, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, part,
+                     nparts, count, out);
+  return hipGetLastError();
+}
+
 hipError_t launch_assembly_mm(int kind, int PM, PairSide S, int64_t npad, int B, int ZS,
                               TabView tab, double sig, double *out, int64_t ld, double *kcopy,
                               hipStream_t st, const Tile *tiles, int64_t ntiles, int G, int part) {

@@ -8,6 +8,7 @@
 //     _predict_marginal_groups, _robust_treatment;
 //   * coef_pass, coef_cross: ace_model_coef_posterior, _predict_surface,
 //     _coef_cross;
+//   * coef_group_pass: ace_model_coef_groups, _average_response;
 //   * joint_pass: ace_model_predict_joint (and ace_potrf_lower beside it).
 //
 // The reference's predict path (R/kernel_SE_R6.R:75-97) builds K_xX and
@@ -539,6 +540,88 @@ void coef_posterior(ace_model *m, const double *theta, int64_t nx, const double 
   coef_cov_from_gram(theta, nx, m->s.B, cov);
 }
 
+// ace_model_coef_groups: the posterior of the summed coefficient vectors
+// sum_{c in g} g(x_c) of the G groups of `label`, modelled on group_pass.
+// With s_{g,b} = sum_{c in g} Kc_b(x_c, X)^T (n-vectors, the columns of S):
+//   gmean[g,b]         = s_{g,b}^T A^-1 (y - mu)
+//   gcov[(g,b),(h,b')] = delta_bb' sum_{c in g, c' in h} k_b(x_c, x_c')
+//                        - s_{g,b}^T A^-1 s_{h,b'}.
+// S (n x G B) comes from k_group_slices_mm with the training side as rows --
+// the (nx B) x n matrix Kc is never formed, so the test points are not
+// chunked -- U = A^-1 S is G B right-hand sides (the rank's share when
+// sharded, then one all-reduce of G B (G B + 1) doubles), and the prior term
+// is the same kernel on the test points against themselves, then E^T R' (one
+// G x G block per slice).  The training rows are in the device's order, which
+// no output shows.  gcov is symmetrised exactly on the host; outputs are
+// written only at the end.
+void coef_group_pass(ace_model *m, const double *theta, int64_t nx, const double *X2, int G,
+                     const int32_t *label, double *gmean, double *gcov, int64_t *gcount,
+                     PredScratch &ps) {
+  ace_ctx *ctx = m->ctx;
+  hipStream_t st = ctx->stream;
+  const Shape &s = m->s;
+  const int64_t n = m->n;
+  const int B = s.B;
+  const int64_t GB = (int64_t)G * B;
+  const PredFront f(m, theta, nx, X2, nullptr, false, FRONT_W);
+  const PairSide tp = f.test.view(nx);
+  DBuf dlab, dE, dpart, dR, dQ, dwork, dtmp;
+  alloc(ctx, dlab, (size_t)nx * sizeof(int32_t), "alloc labels");
+  upload_bytes(ctx, dlab.p, label, (size_t)nx * sizeof(int32_t), "upload labels");
+  alloc(ctx, dE, (size_t)(nx * G) * sizeof(double), "alloc E");
+  ck(ctx, launch_label_matrix(dlab.i(), nx, G, dE.d(), st), "label matrix");
+  alloc(ctx, ps.K, (size_t)(n * GB) * sizeof(double), "alloc S");
+  alloc(ctx, ps.T, (size_t)(n * GB) * sizeof(double), "alloc U");
+  const int64_t npart =
+      std::max(group_slices_parts(n, nx) * n, group_slices_parts(nx, nx) * nx) * GB;
+  alloc(ctx, dpart, (size_t)npart * sizeof(double), "alloc grouped partials");
+  double *S = ps.K.d(), *U = ps.T.d();
+  ck(ctx, launch_group_slices(s.kind, s.PM, f.train, tp, B, s.ZS, f.tv, dlab.i(), G, dpart.d(), S,
+                              st),
+     "grouped slice sums (S)");
+  symm_resident(m, S, n, false, GB, U, dtmp);
+  // [Q_inv (G B x G B) | gmean (G B) | Q_xx (G x G per slice)]
+  alloc(ctx, dQ, (size_t)(GB * (GB + 1) + (int64_t)G * GB) * sizeof(double), "alloc Q");
+  double *Qinv = dQ.d(), *gm = Qinv + GB * GB, *Qxx = gm + GB;
+  const int64_t nwork = std::max(gemm_tn_work(GB, GB, n),
+                                 std::max(gemm_tn_work(GB, 1, n), gemm_tn_work(G, GB, nx)));
+  alloc(ctx, dwork, (size_t)nwork * sizeof(double), "alloc gemm partials");
+  ck(ctx, launch_gemm_tn(GB, GB, n, S, n, U, n, Qinv, GB, false, dwork.d(), st), "S^T U");
+  ck(ctx, launch_gemm_tn(GB, 1, n, U, n, f.dw.d(), n, gm, GB, false, dwork.d(), st), "U^T w");
+  if (m->shard) shard_allreduce_sum(m->shard, Qinv, GB * (GB + 1));
+  // R' = K_b(x, x) E per slice without K_b, Q_xx,b = E^T R'_b
+  alloc(ctx, dR, (size_t)(nx * GB) * sizeof(double), "alloc R");
+  ck(ctx, launch_group_slices(s.kind, s.PM, tp, tp, B, s.ZS, f.tv, dlab.i(), G, dpart.d(), dR.d(),
+                              st),
+     "grouped slice sums (prior)");
+  ck(ctx, launch_gemm_tn(G, GB, nx, dE.d(), nx, dR.d(), nx, Qxx, G, false, dwork.d(), st), "E^T R");
+  std::vector<double> q((size_t)(GB * (GB + 1) + (int64_t)G * GB));
+  download(ctx, q.data(), dQ.d(), q.size(), "download group sums");
+  sync(ctx);
+  const double *hQinv = q.data(), *hgm = hQinv + GB * GB, *hQxx = hgm + GB;
+  // index i = g + G b; the prior of g_b is independent across b
+  const auto raw = [&](int64_t i, int64_t j) {
+    const int64_t b = i / G, b2 = j / G;
+    const double prior = b == b2 ? hQxx[i % G + (int64_t)G * (j % G + (int64_t)G * b)] : 0.0;
+    return prior - hQinv[i + GB * j];
+  };
+  for (int64_t j = 0; j < GB; ++j)
+    for (int64_t i = 0; i < GB; ++i) gcov[i + GB * j] = 0.5 * (raw(i, j) + raw(j, i));
+  std::copy(hgm, hgm + GB, gmean);
+  std::fill(gcount, gcount + G, (int64_t)0);
+  for (int64_t c = 0; c < nx; ++c)
+    if (label[c] >= 0) ++gcount[label[c]];
+}
+
+// the arguments ace_model_coef_groups and ace_model_average_response share
+void coef_group_args(ace_model *m, int64_t nx, int G, const int32_t *label) {
+  ace_ctx *ctx = m->ctx;
+  arg(ctx, G >= 1 && G <= 64, "G must be in [1, 64]");
+  arg(ctx, (int64_t)G * m->s.B <= 2048, "G * B must be <= 2048");
+  for (int64_t i = 0; i < nx; ++i)
+    arg(ctx, label[i] >= -1 && label[i] < G, "label outside [-1, G)");
+}
+
 // ace_model_predict_joint: the joint posterior at nx <= JOINT_NX test points
 // of a single-GPU model.  K_xX, T' = A^-1 K_xX^T (the full symmetric product:
 // the triangular form only serves the diagonal) and K_xx as predict_impl
@@ -875,6 +958,54 @@ int ace_model_predict_surface(ace_model *m, const double *theta, int64_t nx, con
                                               std_y / std_Z, 0.0, 0.0, map, ci, var)
                           : ace_coef_contract(nx, B, nz, mean.data(), cov.data(), W.data(), mean_y,
                                               std_y, theta[1], std::exp(theta[0]), map, ci, var);
+  if (rc != ACE_OK) throw Fail{rc};
+  return ACE_OK;
+  ACE_CATCH
+}
+
+int ace_model_coef_groups(ace_model *m, const double *theta, int64_t nx, const double *X2, int G,
+                          const int32_t *label, double *gmean, double *gcov, int64_t *gcount) {
+  if (!m) return ACE_ERR_ARG;
+  ace_ctx *ctx = m->ctx;
+  ACE_TRY
+  enter(m, nx >= 1 && theta && label && gmean && gcov && gcount && (m->s.p == 0 || X2),
+        [&] { coef_group_args(m, nx, G, label); });
+  with_pred_scratch(ctx, [&](PredScratch &ps) {
+    coef_group_pass(m, theta, nx, X2, G, label, gmean, gcov, gcount, ps);
+  });
+  return ACE_OK;
+  ACE_CATCH
+}
+
+int ace_model_average_response(ace_model *m, const double *theta, int64_t nx, const double *X2,
+                               int G, const int32_t *label, int64_t nz, const double *Zb,
+                               int marginal, double mean_y, double std_y, double std_Z,
+                               double *map, double *ci, double *var, double *cov) {
+  if (!m) return ACE_ERR_ARG;
+  ace_ctx *ctx = m->ctx;
+  ACE_TRY
+  const int B = m->s.B;
+  enter(m,
+        nx >= 1 && nz >= 1 && theta && label && map && ci && var && (m->s.p == 0 || X2) &&
+            (B == 1 || Zb),
+        [&] { coef_group_args(m, nx, G, label); });
+  const int64_t GB = (int64_t)G * B;
+  std::vector<double> gmean((size_t)GB), gcov((size_t)(GB * GB));
+  std::vector<int64_t> gcount((size_t)G);
+  with_pred_scratch(ctx, [&](PredScratch &ps) {
+    coef_group_pass(m, theta, nx, X2, G, label, gmean.data(), gcov.data(), gcount.data(), ps);
+  });
+  // beta as ace_model_predict_surface's, without its noise term
+  std::vector<double> W((size_t)(nz * B));
+  for (int64_t j = 0; j < nz; ++j) {
+    W[(size_t)j] = (marginal && B > 1) ? 0.0 : 1.0;
+    for (int b = 1; b < B; ++b) W[(size_t)(j + nz * b)] = Zb[j + nz * (b - 1)];
+  }
+  const int rc =
+      marginal ? ace_coef_group_contract(G, B, nz, gmean.data(), gcov.data(), gcount.data(),
+                                         W.data(), 0.0, std_y / std_Z, 0.0, map, ci, var, cov)
+               : ace_coef_group_contract(G, B, nz, gmean.data(), gcov.data(), gcount.data(),
+                                         W.data(), mean_y, std_y, theta[1], map, ci, var, cov);
   if (rc != ACE_OK) throw Fail{rc};
   return ACE_OK;
   ACE_CATCH

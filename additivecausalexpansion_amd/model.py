@@ -246,6 +246,60 @@ class DeviceModel:
             ci.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ptr(var)), self.ctx.handle)
         return {"map": mp, "ci": ci, "var": var}
 
+    def _group_args(self, theta, X2, G, label):
+        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
+        X2f = fmat(X2)
+        nx = X2f.shape[0]
+        lab = np.ascontiguousarray(np.ravel(label), dtype=np.int32)
+        if lab.size != nx:
+            raise AceError("label must have one entry per test point")
+        return th, X2f, nx, lab, int(G)
+
+    def coef_groups(self, theta, X2, G, label):
+        """ace_model_coef_groups: the posterior of the coefficient vectors
+        summed over each of the G groups of `label` (int, -1 = no group) --
+        {"gmean": (G, B), "gcov": (G, B, G, B), "gcount": (G,)}, sums (not
+        averages) in normalised-y units, without mu and the noise term.
+        gcov[g, b, h, b'] is the covariance of group g's slice b with group
+        h's slice b'; G <= 64 and G B <= 2048."""
+        th, X2f, nx, lab, G = self._group_args(theta, X2, G, label)
+        Gs = max(G, 1)
+        gmean = np.empty((Gs, self.B), order="F")
+        gcov = np.empty((Gs, self.B, Gs, self.B), order="F")
+        gcount = np.zeros(Gs, dtype=np.int64)
+        check(lib().ace_model_coef_groups(
+            self.handle, ptr(th), nx, ptr(X2f), G,
+            lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(gmean), ptr(gcov),
+            gcount.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), self.ctx.handle)
+        return {"gmean": gmean, "gcov": gcov, "gcount": gcount}
+
+    def average_response(self, theta, X2, G, label, Zb, marginal, mean_y, std_y, std_Z,
+                         return_cov=False):
+        """ace_model_average_response: the average dose-response curve of
+        every group at the nz rows of Zb (the test basis, nz x (B-1), or with
+        marginal its derivative), predict_surface's conventions without a
+        noise term: {"map": (G, nz), "ci": (G, nz, 2), "var": (G, nz)} and,
+        with return_cov, "cov" (G, nz, nz).  An empty group gives NaN."""
+        th, X2f, nx, lab, G = self._group_args(theta, X2, G, label)
+        Zf = np.asarray(Zb, dtype=np.float64)
+        Zf = np.asfortranarray(Zf.reshape((-1, max(self.B - 1, 1)), order="F") if Zf.ndim != 2
+                               else Zf)
+        nz = Zf.shape[0]
+        Gs = max(G, 1)
+        mp = np.empty((Gs, nz), order="F")
+        var = np.empty((Gs, nz), order="F")
+        ci = np.empty((Gs, nz, 2), order="F")
+        cov = np.empty((Gs, nz, nz), order="F") if return_cov else None
+        check(lib().ace_model_average_response(
+            self.handle, ptr(th), nx, ptr(X2f), G,
+            lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), nz, ptr(Zf),
+            1 if marginal else 0, float(mean_y), float(std_y), float(np.ravel([std_Z])[0]),
+            ptr(mp), ptr(ci), ptr(var), ptr(cov)), self.ctx.handle)
+        out = {"map": mp, "ci": ci, "var": var}
+        if return_cov:
+            out["cov"] = cov
+        return out
+
     def predict_joint(self, theta, X2, Z2, mean_y, std_y, *, marginal=False, std_Z=1.0,
                       noise=True, jitter=0.0, xi=None, return_cov=False, return_factor=False):
         """ace_model_predict_joint: the joint posterior at the rows of X2 --
@@ -685,6 +739,24 @@ class _KernelClass:
                            "(para_update on the same data)")
         return self._model.predict_surface(self.parameters, X2, Zb, marginal, mean_y, std_y,
                                            std_Z)
+
+    def coef_groups(self, y, X, Z, X2, G, label):
+        """The group-summed posterior of the coefficient functions at the rows
+        of X2, on the fit's device model (DeviceModel.coef_groups)."""
+        if not self._resident(y, X, Z):
+            raise AceError("coef_groups needs the fit's device-resident inverse "
+                           "(para_update on the same data)")
+        return self._model.coef_groups(self.parameters, X2, G, label)
+
+    def average_response(self, y, X, Z, X2, G, label, Zb, marginal, mean_y, std_y, std_Z,
+                         return_cov=False):
+        """The groups' average dose-response curves at the rows of Zb, on the
+        fit's device model (DeviceModel.average_response)."""
+        if not self._resident(y, X, Z):
+            raise AceError("average_response needs the fit's device-resident inverse "
+                           "(para_update on the same data)")
+        return self._model.average_response(self.parameters, X2, G, label, Zb, marginal, mean_y,
+                                            std_y, std_Z, return_cov)
 
     def predict_joint(self, y, X, Z, X2, Z2, mean_y, std_y, **kw):
         """The joint posterior at the test points on the fit's device model

@@ -475,6 +475,39 @@ def coef_contract(mean, cov, W, offset=0.0, scale=1.0, shift=0.0, noise=0.0):
     return {"map": mp, "ci": ci, "var": var}
 
 
+def coef_group_contract(gmean, gcov, gcount, W, offset=0.0, scale=1.0, shift=0.0,
+                        return_cov=False):
+    """ace_coef_group_contract: a group-summed coefficient posterior (gmean
+    G x B, gcov G x B x G x B, gcount G: DeviceModel.coef_groups) contracted
+    with the nz weight rows W (nz x B) into group averages:
+    map = offset + scale (W_j . gmean_g / |g| + shift), var = scale^2
+    |W_j^T C_gg W_j| / |g|^2 with C_gg group g's diagonal block.  Returns
+    {"map": (G, nz), "ci": (G, nz, 2), "var": (G, nz)} and, with return_cov,
+    "cov" (G, nz, nz), the signed scale^2 W_j^T C_gg W_j' / |g|^2.  An empty
+    group gives NaN."""
+    mf = fmat(gmean)
+    if mf.ndim != 2:
+        raise AceError("gmean must be G x B")
+    G, B = mf.shape
+    cf = np.asfortranarray(np.asarray(gcov, dtype=np.float64).reshape((G, B, G, B), order="F"))
+    cnt = np.ascontiguousarray(np.ravel(gcount), dtype=np.int64)
+    if cnt.size != G:
+        raise AceError("gcount must have one entry per group")
+    Wf = np.asfortranarray(np.asarray(W, dtype=np.float64).reshape((-1, B), order="F"))
+    nz = Wf.shape[0]
+    mp = np.empty((G, nz), order="F")
+    var = np.empty((G, nz), order="F")
+    ci = np.empty((G, nz, 2), order="F")
+    cov = np.empty((G, nz, nz), order="F") if return_cov else None
+    check(lib().ace_coef_group_contract(G, B, nz, ptr(mf), ptr(cf), iptr(cnt), ptr(Wf),
+                                        float(offset), float(scale), float(shift), ptr(mp),
+                                        ptr(ci), ptr(var), ptr(cov)))
+    out = {"map": mp, "ci": ci, "var": var}
+    if return_cov:
+        out["cov"] = cov
+    return out
+
+
 def potrf_lower(A, jitter=0.0, lda=None):
     """ace_potrf_lower: (L, info) with L the lower Cholesky factor of A +
     jitter I (the lower triangle of A is read; zeros above L's diagonal),

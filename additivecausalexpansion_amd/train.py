@@ -672,3 +672,60 @@ def response_surface(obj, newX, newZ, marginal=False):
     return obj["Kernel"].predict_surface(obj["train_data"]["y"], X, obj["Basis"].B, Xn,
                                          tb["dB"] if marginal else tb["B"], marginal, mom[0, 0],
                                          mom[0, 1], mom[1 + px:1 + px + pz, 1])
+
+
+def _group_labels(nx, groups):
+    """(distinct labels in np.unique order, int32 label per row) of `groups`
+    (one entry per row; None: one group of all rows)."""
+    if groups is None:
+        return np.array([0]), np.zeros(nx, dtype=np.int32)
+    g = np.ravel(np.asarray(groups))
+    if g.size != nx:
+        raise AceError("groups must have one entry per row of newX (the training rows if None)")
+    names, lab = np.unique(g, return_inverse=True)
+    if names.size > 64:
+        raise AceError(f"groups has {names.size} distinct labels; at most 64 are supported")
+    return names, np.ravel(lab).astype(np.int32)
+
+
+def average_coef_posterior(obj, newX=None, groups=None):
+    """Posterior of the group averages (1/|g|) sum_{c in g} g(x_c) of the
+    coefficient functions over the rows of newX (raw units; None: the training
+    points).  groups: one label per row (None: one group of all rows).
+    Returns {"groups": the distinct labels in np.unique order, "count": (G,),
+    "mean": (G, B), "cov": (G, B, G, B)}, averages in normalised-y units,
+    without mu and the noise term; cov[g, :, h, :] is the covariance between
+    two groups' averages, so contrasts of groups need no second pass."""
+    Xn, _ = _surface_points(obj, newX)
+    names, lab = _group_labels(Xn.shape[0], groups)
+    r = obj["Kernel"].coef_groups(obj["train_data"]["y"], obj["train_data"]["X"], obj["Basis"].B,
+                                  Xn, names.size, lab)
+    cnt = r["gcount"].astype(np.float64)
+    return {"groups": names, "count": r["gcount"], "mean": r["gmean"] / cnt[:, None],
+            "cov": r["gcov"] / (cnt[:, None, None, None] * cnt[None, None, :, None])}
+
+
+def average_response(obj, newZ, newX=None, groups=None, marginal=False, return_cov=False):
+    """The average dose-response curve z -> (1/|g|) sum_{c in g} E[y | x_c, z]
+    of every group of rows of newX (raw units; None: the training points) at
+    the nz raw treatment values newZ, with its credible band; marginal: the
+    average derivative curve (for a binary fit ATE / ATT / ATU with groups
+    None / the treatment).  One grouped coefficient pass, whatever nz.
+    Returns {"groups", "count", "map": (G, nz), "var": (G, nz), "ci":
+    (G, nz, 2)} and, with return_cov, "cov" (G, nz, nz) for simultaneous
+    bands over z.  No noise term: the posterior of the averaged mean
+    function, not of averaged observations."""
+    X = obj["train_data"]["X"]
+    px = X.shape[1]
+    pz = obj["train_data"]["Z"].shape[1]
+    mom = obj["moments"]
+    Xn, Zn = _surface_points(obj, newX, newZ)
+    names, lab = _group_labels(Xn.shape[0], groups)
+    tb = obj["Basis"].testbasis(Zn)
+    r = obj["Kernel"].average_response(obj["train_data"]["y"], X, obj["Basis"].B, Xn, names.size,
+                                       lab, tb["dB"] if marginal else tb["B"], marginal,
+                                       mom[0, 0], mom[0, 1], mom[1 + px:1 + px + pz, 1],
+                                       return_cov)
+    r["groups"] = names
+    r["count"] = np.bincount(lab, minlength=names.size).astype(np.int64)
+    return r

@@ -394,6 +394,59 @@ int ace_model_predict_surface(ace_model *m, const double *theta, int64_t nx,
                               const double *X2, int64_t nz, const double *Zb,
                               int marginal, double mean_y, double std_y,
                               double std_Z, double *map, double *ci, double *var);
+/* Group-summed posterior of the coefficient functions: for the G groups of
+ * label (nx; 1 <= G <= 64, -1 = in no group) the posterior of
+ * sum_{c in g} g(x_c), the quantity behind every group-average dose-response
+ * curve z -> (1/|g|) sum_{c in g} E[y | x_c, z] and every contrast of two
+ * groups' curves, which need the covariance between different covariate
+ * points that ace_model_coef_posterior does not return.  With s_{g,b} =
+ * sum_{c in g} Kc_b(x_c, X)^T (n-vectors):
+ *   gmean[g + G*b]                    = s_{g,b}^T A^-1 (y - mu)
+ *   gcov[(g + G*b) + G*B*(h + G*b')]  = delta_bb' sum_{c in g, c' in h}
+ *                                       k_b(x_c, x_c') - s_{g,b}^T A^-1 s_{h,b'}
+ * gmean (G x B) and gcov ((G B) x (G B), column-major) hold sums, not
+ * averages, so a union of groups is a sum of entries; gcount (G) the group
+ * sizes.  Normalised-y units, without mu and without the noise term.
+ * Neither the nx x nx test kernel nor the (nx B) x n cross kernels are
+ * stored: their group sums are reduced while the pair tiles are evaluated,
+ * and the resident inverse sees G B right-hand sides whatever nx is.
+ * Kernels at theta, the resident inverse of the last para_update (Q6: gcov
+ * need not be positive semidefinite far from convergence).  gcov is exactly
+ * symmetric and both outputs are bitwise reproducible.  No per-point
+ * weights.  Works on sharded models (collective; one all-reduce of
+ * G B (G B + 1) doubles).  ACE_ERR_ARG for G outside [1, 64], G B > 2048, a
+ * label outside [-1, G), nx < 1, or before the first para_update. */
+int ace_model_coef_groups(ace_model *m, const double *theta, int64_t nx,
+                          const double *X2, int G, const int32_t *label,
+                          double *gmean, double *gcov, int64_t *gcount);
+/* Host only, no context: contracts ace_model_coef_groups' sums with nz weight
+ * rows W (nz x B, column-major) into group averages.  out index g + G*j; ci
+ * is (G*nz) x 2.  With C_gg the B x B diagonal block of gcov of group g:
+ *   map = offset + scale * (W_j . gmean_g / |g| + shift)
+ *   var = scale^2 * |W_j^T C_gg W_j| / |g|^2,  ci = map -+ 1.96 sqrt(var)
+ * cov (G x nz x nz, index g + G*(j + nz*j'); may be NULL): the signed
+ * scale^2 W_j^T C_gg W_j' / |g|^2, exactly symmetric in (j, j'), for
+ * simultaneous bands over z.  An empty group gives NaN (0/0, the C
+ * semantics of ace_pred_marginal's averages). */
+int ace_coef_group_contract(int G, int B, int64_t nz, const double *gmean,
+                            const double *gcov, const int64_t *gcount,
+                            const double *W, double offset, double scale,
+                            double shift, double *map, double *ci, double *var,
+                            double *cov);
+/* The average dose-response curve of every group at the nz rows of Zb
+ * (nz x (B-1): the test basis, or with marginal != 0 its derivative), with
+ * ace_model_predict_surface's conventions: one ace_model_coef_groups pass
+ * plus ace_coef_group_contract.  Response: W_j = (1, Zb_j), offset mean_y,
+ * scale std_y, shift mu = theta[1]; marginal: W_j = (0, Zb_j) ((1) for
+ * B == 1), scale std_y / std_Z, no offset or shift.  No noise term in either
+ * mode: the posterior of the averaged mean function, not of averaged
+ * observations.  map, var (G x nz), ci ((G*nz) x 2), cov (G x nz x nz, may be
+ * NULL) as ace_coef_group_contract's; errors as ace_model_coef_groups'. */
+int ace_model_average_response(ace_model *m, const double *theta, int64_t nx,
+                               const double *X2, int G, const int32_t *label,
+                               int64_t nz, const double *Zb, int marginal,
+                               double mean_y, double std_y, double std_Z,
+                               double *map, double *ci, double *var, double *cov);
 /* The joint posterior at the test points: the matrix the reference forms in
  * full (src/pred_cpp.cpp:22, :72) and reduces to its diagonal,
  *   C = scale^2 (K_xx - K_xX A^-1 K_xX^T [+ exp(theta[0]) I]),
