@@ -15,11 +15,24 @@ import ctypes
 import numpy as np
 
 from . import native
-from ._lib import _I64P, KIND, UNIQUE_ID_BYTES, AceError, check, default_context, fmat, lib, ptr
+from ._lib import (KIND, OPTIMIZER, UNIQUE_ID_BYTES, AceError, Handle, check, default_context, fmat,
+                   lib, ptr)
+from ._marshal import (ate_dicts, cols, i32ptr, iptr, labels, map_ci_var, pack_folds, rows, scalar,
+                       vec)
 
 
-class DeviceModel:
+class _ModelHandle(Handle):
+    """A handle that lives in a Context (`self.ctx`): every entry point takes
+    the handle first and reports its errors through the context."""
+
+    def _call(self, name, *args):
+        check(getattr(lib(), name)(self.handle, *args), self.ctx.handle)
+
+
+class DeviceModel(_ModelHandle):
     """ace_model handle: one fit's resident data and the last inverse."""
+
+    _destroy = "ace_model_destroy"
 
     def __init__(self, kind, n, p, B, ctx=None, world=1, rank=0, unique_id=None,
                  sharded=False, host_comm=None):
@@ -34,41 +47,31 @@ class DeviceModel:
         self.kind, self.n, self.p, self.B = kind, n, p, B
         self.P = 2 + B * (p + 1)
         self.world, self.rank = (world, rank) if sharded else (1, 0)
-        h = ctypes.c_void_p()
+        c, h = self.ctx.handle, ctypes.c_void_p()
         if sharded and host_comm is not None:
             self._host_comm = host_comm  # keeps the callbacks alive
-            check(lib().ace_model_create_sharded_host(self.ctx.handle, KIND[kind], n, p, B,
-                                                      int(world), int(rank),
+            check(lib().ace_model_create_sharded_host(c, KIND[kind], n, p, B, int(world), int(rank),
                                                       ctypes.byref(host_comm.ops),
-                                                      ctypes.byref(h)),
-                  self.ctx.handle)
+                                                      ctypes.byref(h)), c)
         elif sharded:
             if unique_id is not None and len(unique_id) != UNIQUE_ID_BYTES:
                 raise ValueError("unique_id must be 128 bytes")
-            check(lib().ace_model_create_sharded(self.ctx.handle, KIND[kind], n, p, B, int(world),
-                                                 int(rank), unique_id, ctypes.byref(h)),
-                  self.ctx.handle)
+            check(lib().ace_model_create_sharded(c, KIND[kind], n, p, B, int(world), int(rank),
+                                                 unique_id, ctypes.byref(h)), c)
         else:
-            check(lib().ace_model_create(self.ctx.handle, KIND[kind], n, p, B, ctypes.byref(h)),
-                  self.ctx.handle)
+            check(lib().ace_model_create(c, KIND[kind], n, p, B, ctypes.byref(h)), c)
         self.handle = h
 
     def set_data(self, y, X, Z, std_y):
-        yv = np.ascontiguousarray(np.ravel(y), dtype=np.float64)
-        Xf = fmat(X)
-        Zf = np.asfortranarray(np.asarray(Z, dtype=np.float64).reshape(self.n, -1))
-        check(lib().ace_model_set_data(self.handle, ptr(yv), ptr(Xf), ptr(Zf), float(std_y)),
-              self.ctx.handle)
+        yv, Xf, Zf = vec(y), fmat(X), cols(Z, self.n)
+        self._call("ace_model_set_data", ptr(yv), ptr(Xf), ptr(Zf), float(std_y))
 
     def para_update(self, it, theta):
         """theta (float64, P) is mutated at it == 1 (mu overwrite)."""
         g = np.empty(self.P)
         st = np.empty(2)
         mu = ctypes.c_double()
-        check(lib().ace_model_para_update(self.handle, int(it), ptr(theta), ptr(g), ptr(st),
-                                          ctypes.cast(ctypes.pointer(mu),
-                                                      ctypes.POINTER(ctypes.c_double))),
-              self.ctx.handle)
+        self._call("ace_model_para_update", int(it), ptr(theta), ptr(g), ptr(st), ctypes.byref(mu))
         return g, st, mu.value
 
     def train(self, theta, optimizer="Nadam", learning_rate=0.01, momentum=0.0, beta1=0.9,
@@ -76,100 +79,79 @@ class DeviceModel:
         """ace_model_train: the whole ace.train loop natively (R/main_ace.R:213-235).
         theta (float64, P) is updated in place; returns (stats 2 x (maxiter+2),
         iterations, converged)."""
-        from ._lib import OPTIMIZER
         if optimizer == "GD":
             momentum = 0.0
         stats = np.zeros((2, maxiter + 2), order="F")
         it = ctypes.c_int()
         conv = ctypes.c_int()
-        check(lib().ace_model_train(self.handle, OPTIMIZER[optimizer], float(learning_rate),
-                                    float(momentum), float(beta1), float(beta2),
-                                    1 if norm_clip else 0, float(clip_at), int(maxiter),
-                                    float(tol), ptr(theta), ptr(stats), ctypes.byref(it),
-                                    ctypes.byref(conv)), self.ctx.handle)
+        self._call("ace_model_train", OPTIMIZER[optimizer], float(learning_rate), float(momentum),
+                   float(beta1), float(beta2), 1 if norm_clip else 0, float(clip_at), int(maxiter),
+                   float(tol), ptr(theta), ptr(stats), ctypes.byref(it), ctypes.byref(conv))
         return stats, it.value, bool(conv.value)
 
     def train_stats(self, theta):
         th = np.ascontiguousarray(theta, dtype=np.float64)
         st = np.empty(2)
-        check(lib().ace_model_train_stats(self.handle, ptr(th), ptr(st)), self.ctx.handle)
+        self._call("ace_model_train_stats", ptr(th), ptr(st))
         return st
 
     def inverse(self):
         out = np.empty((self.n, self.n), order="F")
-        check(lib().ace_model_get_inverse(self.handle, ptr(out)), self.ctx.handle)
+        self._call("ace_model_get_inverse", ptr(out))
         return out
 
     def apply_inverse(self, V):
         """ace_model_apply_inverse: A^-1 V with the resident inverse (V n x k)."""
-        Vf = np.asfortranarray(np.asarray(V, dtype=np.float64).reshape(self.n, -1))
+        Vf = cols(V, self.n)
         out = np.empty_like(Vf, order="F")
-        check(lib().ace_model_apply_inverse(self.handle, Vf.shape[1], ptr(Vf), ptr(out)),
-              self.ctx.handle)
+        self._call("ace_model_apply_inverse", Vf.shape[1], ptr(Vf), ptr(out))
         return out if np.ndim(V) == 2 else out.ravel()
+
+    def _test_side(self, theta, X2, Z2=None, label=None):
+        """What every query at test points starts from: theta, the rows X2
+        and, where given, their basis rows (nx x (B-1)) and int32 group
+        labels, converted for the library; and nx."""
+        X2f = fmat(X2)
+        nx = X2f.shape[0]
+        return (vec(theta), X2f, None if Z2 is None else cols(Z2, nx),
+                None if label is None else labels(label, nx), nx)
 
     def predict(self, theta, X2, Z2, mean_y, std_y):
         """ace_model_predict: pred_cpp with the resident inverse (Q6), kernels at theta."""
-        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
-        X2f = fmat(X2)
-        nx = X2f.shape[0]
-        Z2f = np.asfortranarray(np.asarray(Z2, dtype=np.float64).reshape(nx, -1))
-        mp, var = np.empty(nx), np.empty(nx)
-        ci = np.empty((nx, 2), order="F")
-        check(lib().ace_model_predict(self.handle, ptr(th), nx, ptr(X2f), ptr(Z2f), float(mean_y),
-                                      float(std_y), ptr(mp), ptr(ci), ptr(var)), self.ctx.handle)
-        return {"map": mp, "ci": ci, "var": var}
+        th, X2f, Z2f, _, nx = self._test_side(theta, X2, Z2)
+        mp, ci, var, out = map_ci_var(nx)
+        self._call("ace_model_predict", ptr(th), nx, ptr(X2f), ptr(Z2f), float(mean_y),
+                   float(std_y), ptr(mp), ptr(ci), ptr(var))
+        return out
 
     def predict_marginal(self, theta, X2, dZ2, Z_x, std_y, std_Z, calculate_ate):
         """ace_model_predict_marginal: pred_marginal_cpp with the resident inverse."""
-        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
-        X2f = fmat(X2)
-        nx = X2f.shape[0]
-        dZf = np.asfortranarray(np.asarray(dZ2, dtype=np.float64).reshape(nx, -1))
-        zx = (np.ascontiguousarray(np.ravel(Z_x), dtype=np.float64)
-              if calculate_ate else None)
-        mp, var, avg = np.empty(nx), np.empty(nx), np.empty(12)
-        ci = np.empty((nx, 2), order="F")
-        check(lib().ace_model_predict_marginal(self.handle, ptr(th), nx, ptr(X2f), ptr(dZf),
-                                               ptr(zx), float(std_y),
-                                               float(np.ravel([std_Z])[0]),
-                                               1 if calculate_ate else 0, ptr(mp), ptr(ci),
-                                               ptr(var), ptr(avg)), self.ctx.handle)
-        out = {"map": mp, "ci": ci, "var": var}
+        th, X2f, dZf, _, nx = self._test_side(theta, X2, dZ2)
+        zx = vec(Z_x) if calculate_ate else None
+        mp, ci, var, out = map_ci_var(nx)
+        avg = np.empty(12)
+        self._call("ace_model_predict_marginal", ptr(th), nx, ptr(X2f), ptr(dZf), ptr(zx),
+                   float(std_y), scalar(std_Z), 1 if calculate_ate else 0, ptr(mp), ptr(ci),
+                   ptr(var), ptr(avg))
         if calculate_ate:
-            for j, key in enumerate(("ate", "att", "atu")):
-                a = avg[4 * j:4 * j + 4]
-                out[key] = {"map": a[0], "ci": np.array([a[1], a[2]]), "var": a[3]}
+            out.update(ate_dicts(avg))
         return out
-
-    def _test_side(self, theta, X2, dZ2):
-        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
-        X2f = fmat(X2)
-        nx = X2f.shape[0]
-        dZf = np.asfortranarray(np.asarray(dZ2, dtype=np.float64).reshape(nx, -1))
-        return th, X2f, dZf, nx
 
     def predict_marginal_groups(self, theta, X2, dZ2, std_y, std_Z, G, label):
         """ace_model_predict_marginal_groups: predict_marginal's map / ci / var
         plus, for the G groups of `label` (int, -1 = no group), gsum (the sum
         of map), gcount and gcov = E^T C E (G x G) with C the unscaled
         marginal posterior covariance; the nx x nx test kernel is never built."""
-        th, X2f, dZf, nx = self._test_side(theta, X2, dZ2)
-        lab = np.ascontiguousarray(np.ravel(label), dtype=np.int32)
-        if lab.size != nx:
-            raise AceError("label must have one entry per test point")
+        th, X2f, dZf, lab, nx = self._test_side(theta, X2, dZ2, label)
         G = int(G)
-        mp, var = np.empty(nx), np.empty(nx)
-        ci = np.empty((nx, 2), order="F")
-        gsum = np.empty(max(G, 1))
-        gcount = np.zeros(max(G, 1), dtype=np.int64)
-        gcov = np.empty((max(G, 1), max(G, 1)), order="F")
-        check(lib().ace_model_predict_marginal_groups(
-            self.handle, ptr(th), nx, ptr(X2f), ptr(dZf), float(std_y),
-            float(np.ravel([std_Z])[0]), G, lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(mp), ptr(ci), ptr(var),
-            ptr(gsum), gcount.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ptr(gcov)),
-            self.ctx.handle)
-        return {"map": mp, "ci": ci, "var": var, "gsum": gsum, "gcount": gcount, "gcov": gcov}
+        Gs = max(G, 1)
+        mp, ci, var, out = map_ci_var(nx)
+        out.update(gsum=np.empty(Gs), gcount=np.zeros(Gs, dtype=np.int64),
+                   gcov=np.empty((Gs, Gs), order="F"))
+        self._call("ace_model_predict_marginal_groups", ptr(th), nx, ptr(X2f), ptr(dZf),
+                   float(std_y), scalar(std_Z), G, i32ptr(lab), ptr(mp), ptr(ci), ptr(var),
+                   ptr(out["gsum"]), iptr(out["gcount"]), ptr(out["gcov"]))
+        return out
 
     def robust_treatment(self, theta, X2, dZ2, Z_x, std_y, std_Z, n_steps=5):
         """ace_model_robust_treatment: the ATE / ATT / ATU of every discard step
@@ -177,52 +159,40 @@ class DeviceModel:
         avg is 12 x (n_steps + 1) (column t as predict_marginal's averages on
         step t's subset), counts 3 x (n_steps + 1) (retained, treated,
         untreated); "ate" / "att" / "atu" hold the per-step map, ci, var."""
-        th, X2f, dZf, nx = self._test_side(theta, X2, dZ2)
-        zx = np.ascontiguousarray(np.ravel(Z_x), dtype=np.float64)
+        th, X2f, dZf, _, nx = self._test_side(theta, X2, dZ2)
+        zx = vec(Z_x)
         if zx.size != nx:
             raise AceError("Z_x must have one entry per test point")
         n_steps = int(n_steps)
         T = max(n_steps, 0) + 1
-        mp, var = np.empty(nx), np.empty(nx)
-        ci = np.empty((nx, 2), order="F")
+        mp, ci, var, out = map_ci_var(nx)
         thr = np.empty(T)
         level = np.empty(nx, dtype=np.int32)
         avg = np.empty((12, T), order="F")
         counts = np.zeros((3, T), dtype=np.int64, order="F")
-        check(lib().ace_model_robust_treatment(
-            self.handle, ptr(th), nx, ptr(X2f), ptr(dZf), ptr(zx), float(std_y),
-            float(np.ravel([std_Z])[0]), n_steps, ptr(mp), ptr(ci), ptr(var), ptr(thr),
-            level.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(avg),
-            counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), self.ctx.handle)
-        out = {"map": mp, "ci": ci, "var": var, "thresholds": thr, "level": level, "avg": avg,
-               "counts": counts}
-        for j, key in enumerate(("ate", "att", "atu")):
-            out[key] = {"map": avg[4 * j], "ci": avg[4 * j + 1:4 * j + 3].T, "var": avg[4 * j + 3]}
+        self._call("ace_model_robust_treatment", ptr(th), nx, ptr(X2f), ptr(dZf), ptr(zx),
+                   float(std_y), scalar(std_Z), n_steps, ptr(mp), ptr(ci), ptr(var), ptr(thr),
+                   i32ptr(level), ptr(avg), iptr(counts))
+        out.update(thresholds=thr, level=level, avg=avg, counts=counts)
+        out.update(ate_dicts(avg))
         return out
 
     def coef_posterior(self, theta, X2):
         """ace_model_coef_posterior: the posterior of the coefficient vector
         g(x) at every row of X2 -- {"mean": (nx, B), "cov": (nx, B, B)} in
         normalised-y units, without mu and without the noise term."""
-        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
-        X2f = fmat(X2)
-        nx = X2f.shape[0]
+        th, X2f, _, _, nx = self._test_side(theta, X2)
         mean = np.empty((nx, self.B), order="F")
         cov = np.empty((nx, self.B, self.B), order="F")
-        check(lib().ace_model_coef_posterior(self.handle, ptr(th), nx, ptr(X2f), ptr(mean),
-                                             cov.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
-              self.ctx.handle)
+        self._call("ace_model_coef_posterior", ptr(th), nx, ptr(X2f), ptr(mean), ptr(cov))
         return {"mean": mean, "cov": cov}
 
     def coef_cross(self, theta, X2):
         """ace_model_coef_cross: the per-slice cross kernels (nx, n, B) the
         coefficient posterior is formed from (a test basis of ones)."""
-        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
-        X2f = fmat(X2)
-        nx = X2f.shape[0]
+        th, X2f, _, _, nx = self._test_side(theta, X2)
         Kc = np.empty((nx, self.n, self.B), order="F")
-        check(lib().ace_model_coef_cross(self.handle, ptr(th), nx, ptr(X2f), ptr(Kc)),
-              self.ctx.handle)
+        self._call("ace_model_coef_cross", ptr(th), nx, ptr(X2f), ptr(Kc))
         return Kc
 
     def predict_surface(self, theta, X2, Zb, marginal, mean_y, std_y, std_Z):
@@ -230,30 +200,14 @@ class DeviceModel:
         basis, nz x (B-1)) or pred_marginal_cpp (Zb its derivative) on the
         grid of every row of X2 with every row of Zb, from one coefficient
         pass: {"map": (nx, nz), "ci": (nx, nz, 2), "var": (nx, nz)}."""
-        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
-        X2f = fmat(X2)
-        nx = X2f.shape[0]
-        Zf = np.asarray(Zb, dtype=np.float64)
-        Zf = np.asfortranarray(Zf.reshape((-1, max(self.B - 1, 1)), order="F") if Zf.ndim != 2
-                               else Zf)
+        th, X2f, _, _, nx = self._test_side(theta, X2)
+        Zf = rows(Zb, max(self.B - 1, 1))
         nz = Zf.shape[0]
-        mp = np.empty((nx, nz), order="F")
-        var = np.empty((nx, nz), order="F")
-        ci = np.empty((nx, nz, 2), order="F")
-        check(lib().ace_model_predict_surface(
-            self.handle, ptr(th), nx, ptr(X2f), nz, ptr(Zf), 1 if marginal else 0, float(mean_y),
-            float(std_y), float(np.ravel([std_Z])[0]), ptr(mp),
-            ci.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ptr(var)), self.ctx.handle)
-        return {"map": mp, "ci": ci, "var": var}
-
-    def _group_args(self, theta, X2, G, label):
-        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
-        X2f = fmat(X2)
-        nx = X2f.shape[0]
-        lab = np.ascontiguousarray(np.ravel(label), dtype=np.int32)
-        if lab.size != nx:
-            raise AceError("label must have one entry per test point")
-        return th, X2f, nx, lab, int(G)
+        mp, ci, var, out = map_ci_var(nx, nz)
+        self._call("ace_model_predict_surface", ptr(th), nx, ptr(X2f), nz, ptr(Zf),
+                   1 if marginal else 0, float(mean_y), float(std_y), scalar(std_Z), ptr(mp),
+                   ptr(ci), ptr(var))
+        return out
 
     def coef_groups(self, theta, X2, G, label):
         """ace_model_coef_groups: the posterior of the coefficient vectors
@@ -262,15 +216,14 @@ class DeviceModel:
         averages) in normalised-y units, without mu and the noise term.
         gcov[g, b, h, b'] is the covariance of group g's slice b with group
         h's slice b'; G <= 64 and G B <= 2048."""
-        th, X2f, nx, lab, G = self._group_args(theta, X2, G, label)
+        th, X2f, _, lab, nx = self._test_side(theta, X2, label=label)
+        G = int(G)
         Gs = max(G, 1)
         gmean = np.empty((Gs, self.B), order="F")
         gcov = np.empty((Gs, self.B, Gs, self.B), order="F")
         gcount = np.zeros(Gs, dtype=np.int64)
-        check(lib().ace_model_coef_groups(
-            self.handle, ptr(th), nx, ptr(X2f), G,
-            lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ptr(gmean), ptr(gcov),
-            gcount.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), self.ctx.handle)
+        self._call("ace_model_coef_groups", ptr(th), nx, ptr(X2f), G, i32ptr(lab), ptr(gmean),
+                   ptr(gcov), iptr(gcount))
         return {"gmean": gmean, "gcov": gcov, "gcount": gcount}
 
     def average_response(self, theta, X2, G, label, Zb, marginal, mean_y, std_y, std_Z,
@@ -280,24 +233,16 @@ class DeviceModel:
         marginal its derivative), predict_surface's conventions without a
         noise term: {"map": (G, nz), "ci": (G, nz, 2), "var": (G, nz)} and,
         with return_cov, "cov" (G, nz, nz).  An empty group gives NaN."""
-        th, X2f, nx, lab, G = self._group_args(theta, X2, G, label)
-        Zf = np.asarray(Zb, dtype=np.float64)
-        Zf = np.asfortranarray(Zf.reshape((-1, max(self.B - 1, 1)), order="F") if Zf.ndim != 2
-                               else Zf)
+        th, X2f, _, lab, nx = self._test_side(theta, X2, label=label)
+        G = int(G)
+        Zf = rows(Zb, max(self.B - 1, 1))
         nz = Zf.shape[0]
-        Gs = max(G, 1)
-        mp = np.empty((Gs, nz), order="F")
-        var = np.empty((Gs, nz), order="F")
-        ci = np.empty((Gs, nz, 2), order="F")
-        cov = np.empty((Gs, nz, nz), order="F") if return_cov else None
-        check(lib().ace_model_average_response(
-            self.handle, ptr(th), nx, ptr(X2f), G,
-            lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), nz, ptr(Zf),
-            1 if marginal else 0, float(mean_y), float(std_y), float(np.ravel([std_Z])[0]),
-            ptr(mp), ptr(ci), ptr(var), ptr(cov)), self.ctx.handle)
-        out = {"map": mp, "ci": ci, "var": var}
+        mp, ci, var, out = map_ci_var(max(G, 1), nz)
         if return_cov:
-            out["cov"] = cov
+            out["cov"] = np.empty((max(G, 1), nz, nz), order="F")
+        self._call("ace_model_average_response", ptr(th), nx, ptr(X2f), G, i32ptr(lab), nz,
+                   ptr(Zf), 1 if marginal else 0, float(mean_y), float(std_y), scalar(std_Z),
+                   ptr(mp), ptr(ci), ptr(var), ptr(out.get("cov")))
         return out
 
     def predict_joint(self, theta, X2, Z2, mean_y, std_y, *, marginal=False, std_Z=1.0,
@@ -311,11 +256,11 @@ class DeviceModel:
         was not positive -- L and draws are NaN, map and cov valid; under Q6
         (kernels at a theta other than the resident inverse's) cov need not be
         positive semidefinite.  nx <= 8192, S <= 4096, single-GPU models."""
-        th, X2f, Zf, nx = self._test_side(theta, X2, Z2)
+        th, X2f, Zf, _, nx = self._test_side(theta, X2, Z2)
         S = 0
         xif = draws = None
         if xi is not None:
-            xif = np.asfortranarray(np.asarray(xi, dtype=np.float64).reshape(nx, -1))
+            xif = cols(xi, nx)
             S = xif.shape[1]
             draws = np.empty((nx, S), order="F") if S else None
             if not S:
@@ -324,10 +269,9 @@ class DeviceModel:
         cov = np.empty((nx, nx), order="F") if return_cov else None
         L = np.empty((nx, nx), order="F") if return_factor else None
         info = ctypes.c_int64(0)
-        check(lib().ace_model_predict_joint(
-            self.handle, ptr(th), nx, ptr(X2f), ptr(Zf), 1 if marginal else 0, float(mean_y),
-            float(std_y), float(np.ravel([std_Z])[0]), 1 if noise else 0, float(jitter), S,
-            ptr(xif), ptr(mp), ptr(cov), ptr(L), ptr(draws), ctypes.byref(info)), self.ctx.handle)
+        self._call("ace_model_predict_joint", ptr(th), nx, ptr(X2f), ptr(Zf), 1 if marginal else 0,
+                   float(mean_y), float(std_y), scalar(std_Z), 1 if noise else 0, float(jitter), S,
+                   ptr(xif), ptr(mp), ptr(cov), ptr(L), ptr(draws), ctypes.byref(info))
         out = {"map": mp, "info": int(info.value)}
         if return_cov:
             out["cov"] = cov
@@ -347,16 +291,14 @@ class DeviceModel:
         -- its outputs are NaN, the other folds are unaffected.  The inverse
         is the last para_update's, mu = theta[1] (Q6), as predict uses them.
         Single-GPU models."""
-        th = np.ascontiguousarray(np.ravel(theta), dtype=np.float64)
-        nf, off, idx = native.pack_folds(folds)
+        th = vec(theta)
+        nf, off, idx = pack_folds(folds)
         tot = int(off[-1])
         mp, var, res = (np.empty(max(tot, 1)) for _ in range(3))
         lpd, mh = np.empty(nf), np.empty(nf)
         st = np.zeros(nf, dtype=np.int32)
-        check(lib().ace_model_cv(self.handle, ptr(th), nf, native.iptr(off), native.iptr(idx),
-                                 float(mean_y), float(std_y), ptr(mp), ptr(var), ptr(res), ptr(lpd),
-                                 ptr(mh), st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
-              self.ctx.handle)
+        self._call("ace_model_cv", ptr(th), nf, iptr(off), iptr(idx), float(mean_y), float(std_y),
+                   ptr(mp), ptr(var), ptr(res), ptr(lpd), ptr(mh), i32ptr(st))
         return {"map": mp[:tot], "var": var[:tot], "resid": res[:tot], "lpd": lpd, "mahal": mh,
                 "status": st, "off": off}
 
@@ -364,35 +306,26 @@ class DeviceModel:
         """ace_model_comm_calls: collectives this rank issued since creation,
         {"broadcast", "allgather", "allreduce", "groups"} (zeros when simulated)."""
         c = (ctypes.c_int64 * 4)()
-        check(lib().ace_model_comm_calls(self.handle, c), self.ctx.handle)
+        self._call("ace_model_comm_calls", c)
         return dict(zip(("broadcast", "allgather", "allreduce", "groups"), c))
 
     def profile(self, enable):
-        check(lib().ace_model_profile(self.handle, 1 if enable else 0), self.ctx.handle)
+        self._call("ace_model_profile", 1 if enable else 0)
 
     def kernel_time(self, which):
         ms = ctypes.c_double()
         nl = ctypes.c_int64()
         work = ctypes.c_double()
-        check(lib().ace_model_kernel_time(self.handle, which, ctypes.byref(ms), ctypes.byref(nl),
-                                          ctypes.byref(work)), self.ctx.handle)
+        self._call("ace_model_kernel_time", which, ctypes.byref(ms), ctypes.byref(nl),
+                   ctypes.byref(work))
         return ms.value, nl.value, work.value
 
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().ace_model_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BatchModel:
+class BatchModel(_ModelHandle):
     """ace_batch handle: M independent models of at most nmax <= 512 rows, one
     kernel kind, p and B; one workgroup per model (single GPU)."""
+
+    _destroy = "ace_batch_destroy"
 
     def __init__(self, kind, M, nmax, p, B, ctx=None):
         self.ctx = ctx or default_context()
@@ -405,12 +338,10 @@ class BatchModel:
         self.handle = h
 
     def set_data(self, j, y, X, Z, std_y):
-        yv = np.ascontiguousarray(np.ravel(y), dtype=np.float64)
+        yv = vec(y)
         n = yv.size
-        Xf = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(n, -1))
-        Zf = np.asfortranarray(np.asarray(Z, dtype=np.float64).reshape(n, -1))
-        check(lib().ace_batch_set_data(self.handle, int(j), n, ptr(yv), ptr(Xf), ptr(Zf),
-                                       float(std_y)), self.ctx.handle)
+        Xf, Zf = cols(X, n), cols(Z, n)
+        self._call("ace_batch_set_data", int(j), n, ptr(yv), ptr(Xf), ptr(Zf), float(std_y))
         self.n[int(j)] = n
 
     def para_update(self, it, theta):
@@ -420,8 +351,7 @@ class BatchModel:
         g = np.empty((self.P, self.M), order="F")
         st = np.empty((2, self.M), order="F")
         mu = np.empty(self.M)
-        check(lib().ace_batch_para_update(self.handle, int(it), ptr(theta), ptr(g), ptr(st),
-                                          ptr(mu)), self.ctx.handle)
+        self._call("ace_batch_para_update", int(it), ptr(theta), ptr(g), ptr(st), ptr(mu))
         return g, st, mu
 
     def train(self, theta, optimizer="Nadam", learning_rate=0.01, momentum=0.0, beta1=0.9,
@@ -430,55 +360,46 @@ class BatchModel:
         (float64, P x M column-major) is updated in place; returns (stats
         2 x (maxiter + 2) x M, iterations M, converged M, status M -- 0 or
         ACE_ERR_NONFINITE = 5 per model)."""
-        from ._lib import OPTIMIZER
         assert theta.shape == (self.P, self.M) and theta.flags.f_contiguous
         if optimizer == "GD":
             momentum = 0.0
         stats = np.zeros((2, maxiter + 2, self.M), order="F")
-        it = np.zeros(self.M, dtype=np.int32)
-        conv = np.zeros(self.M, dtype=np.int32)
-        status = np.zeros(self.M, dtype=np.int32)
-        i32 = ctypes.POINTER(ctypes.c_int32)
-        check(lib().ace_batch_train(self.handle, OPTIMIZER[optimizer], float(learning_rate),
-                                    float(momentum), float(beta1), float(beta2),
-                                    1 if norm_clip else 0, float(clip_at), int(maxiter),
-                                    float(tol), ptr(theta),
-                                    stats.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                    it.ctypes.data_as(i32), conv.ctypes.data_as(i32),
-                                    status.ctypes.data_as(i32)), self.ctx.handle)
+        it, conv, status = (np.zeros(self.M, dtype=np.int32) for _ in range(3))
+        self._call("ace_batch_train", OPTIMIZER[optimizer], float(learning_rate), float(momentum),
+                   float(beta1), float(beta2), 1 if norm_clip else 0, float(clip_at), int(maxiter),
+                   float(tol), ptr(theta), ptr(stats), i32ptr(it), i32ptr(conv), i32ptr(status))
         return stats, it, conv.astype(bool), status
 
     def inverse(self, j):
         n = self.n[int(j)]
         out = np.empty((n, n), order="F")
-        check(lib().ace_batch_get_inverse(self.handle, int(j), ptr(out)), self.ctx.handle)
+        self._call("ace_batch_get_inverse", int(j), ptr(out))
         return out
 
     def set_inverse(self, j, inv):
         """ace_set_inverse_batch: inv (n_j x n_j, symmetric) becomes model j's
         resident inverse (after its set_data)."""
         n = self.n[int(j)] if 0 <= int(j) < self.M else 0
-        a = np.asfortranarray(np.asarray(inv, dtype=np.float64))
+        a = fmat(inv)
         if n and a.shape != (n, n):
             raise AceError(f"ACE_ERR_ARG: the inverse of model {j} must be {n} x {n}")
-        check(lib().ace_set_inverse_batch(self.handle, int(j), ptr(a)), self.ctx.handle)
+        self._call("ace_set_inverse_batch", int(j), ptr(a))
 
     def _pack_test(self, theta, X2s, Zts):
         """theta (P x M), and the packed test side: off (M + 1), every model's
         X2 block (nx_j x p) and basis block (nx_j x (B - 1)), column-major."""
-        th = np.asfortranarray(np.asarray(theta, dtype=np.float64))
+        th = fmat(theta)
         if th.shape != (self.P, self.M) or len(X2s) != self.M or len(Zts) != self.M:
             raise AceError(f"ACE_ERR_ARG: theta must be P x M = {self.P} x {self.M} and the test "
                            "sides sequences of length M")
-        xs = [np.asfortranarray(np.asarray(x, dtype=np.float64)) for x in X2s]
+        xs = [fmat(x) for x in X2s]
         xs = [x.reshape(-1, self.p, order="F") if self.p else x.reshape(-1, 0) for x in xs]
         nx = [x.shape[0] for x in xs]
         off = np.zeros(self.M + 1, dtype=np.int64)
         off[1:] = np.cumsum(nx)
         zs = []
         for j, z in enumerate(Zts):
-            z = (np.asfortranarray(np.asarray(z, dtype=np.float64)) if self.B > 1
-                 else np.zeros((nx[j], 0)))
+            z = fmat(z) if self.B > 1 else np.zeros((nx[j], 0))
             if z.size != nx[j] * (self.B - 1):
                 raise AceError(f"ACE_ERR_ARG: the test basis of model {j} must be nx_j x (B - 1) = "
                                f"{nx[j]} x {self.B - 1}")
@@ -504,9 +425,8 @@ class BatchModel:
         my, sy = self._per_model(mean_y), self._per_model(std_y)
         N = int(off[-1])
         mp, var, ci = np.empty(N), np.empty(N), np.empty(2 * N)
-        check(lib().ace_predict_batch(self.handle, ptr(th), off.ctypes.data_as(_I64P), ptr(x2),
-                                      ptr(z2), ptr(my), ptr(sy), ptr(mp), ptr(ci), ptr(var)),
-              self.ctx.handle)
+        self._call("ace_predict_batch", ptr(th), iptr(off), ptr(x2), ptr(z2), ptr(my), ptr(sy),
+                   ptr(mp), ptr(ci), ptr(var))
         return [self._split(off, j, mp, ci, var) for j in range(self.M)]
 
     @staticmethod
@@ -533,30 +453,14 @@ class BatchModel:
                 raise AceError("ACE_ERR_ARG: Z_xs must hold one value per test point")
             avg = np.empty((12, self.M), order="F")
         mp, var, ci = np.empty(N), np.empty(N), np.empty(2 * N)
-        check(lib().ace_predict_marginal_batch(self.handle, ptr(th), off.ctypes.data_as(_I64P),
-                                               ptr(x2), ptr(dz), ptr(zx), ptr(sy), ptr(sz),
-                                               1 if calculate_ate else 0, ptr(mp), ptr(ci),
-                                               ptr(var), ptr(avg)), self.ctx.handle)
-        outs = []
-        for j in range(self.M):
-            out = self._split(off, j, mp, ci, var)
-            if calculate_ate:
-                for k, key in enumerate(("ate", "att", "atu")):
-                    a = avg[4 * k:4 * k + 4, j]
-                    out[key] = {"map": a[0], "ci": np.array([a[1], a[2]]), "var": a[3]}
-            outs.append(out)
+        self._call("ace_predict_marginal_batch", ptr(th), iptr(off), ptr(x2), ptr(dz), ptr(zx),
+                   ptr(sy), ptr(sz), 1 if calculate_ate else 0, ptr(mp), ptr(ci), ptr(var),
+                   ptr(avg))
+        outs = [self._split(off, j, mp, ci, var) for j in range(self.M)]
+        if calculate_ate:
+            for j, out in enumerate(outs):
+                out.update(ate_dicts(avg[:, j]))
         return outs
-
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().ace_batch_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def comm_unique_id():
@@ -600,18 +504,18 @@ class _KernelClass:
 
     @property
     def invKmatn(self):
-        if self._inv_from_model:
-            if self._inv is None:
-                self._inv = self._model.inverse()
-            return self._inv
+        if self._inv_from_model and self._inv is None:
+            self._inv = self._model.inverse()
         return self._inv
+
+    def _sym(self, X, Z, theta=None):
+        """This kind's symmetric kernel list at theta (None: the parameters)."""
+        return native._kernmat_sym(KIND[self.kernel], X, Z,
+                                   self.parameters if theta is None else theta, self.ctx)
 
     def _materialise(self):
         if self._kcache is None:
-            X, Z = self._kern_data
-            f = (native.kernmat_SE_symmetric_cpp if self.kernel == "SE"
-                 else native.kernmat_Matern32_symmetric_cpp)
-            self._kcache = f(X, Z, self._kern_theta, ctx=self.ctx)
+            self._kcache = self._sym(*self._kern_data, self._kern_theta)
         return self._kcache
 
     def _mark_kernel(self, X, Z):
@@ -621,15 +525,11 @@ class _KernelClass:
 
     # ----------------------------------------------------------- R6 methods
     def kernel_mat(self, X1, X2, Z1, Z2):
-        f = native.kernmat_SE_cpp if self.kernel == "SE" else native.kernmat_Matern32_cpp
-        return f(X1, X2, Z1, Z2, self.parameters, ctx=self.ctx)
+        return native._kernmat_cross(KIND[self.kernel], X1, X2, Z1, Z2, self.parameters, self.ctx)
 
     def kernel_mat_sym(self, X, Z):
-        f = (native.kernmat_SE_symmetric_cpp if self.kernel == "SE"
-             else native.kernmat_Matern32_symmetric_cpp)
-        Klist = f(X, Z, self.parameters, ctx=self.ctx)
-        self._kern_theta = self.parameters.copy()
-        self._kern_data = (X, Z)
+        Klist = self._sym(X, Z)
+        self._mark_kernel(X, Z)
         self._kcache = Klist
         return Klist
 
@@ -689,15 +589,20 @@ class _KernelClass:
         return (self._inv_from_model and self._model is not None and
                 self._data_id == (id(y), id(X), id(Z)))
 
+    def _on_model(self, what, y, X, Z):
+        """The fit's device model, for the queries that exist only on it."""
+        if not self._resident(y, X, Z):
+            raise AceError(f"{what} needs the fit's device-resident inverse "
+                           "(para_update on the same data)")
+        return self._model
+
     def predict(self, y, X, Z, X2, Z2, mean_y, std_y):
         """R/kernel_SE_R6.R:75-83.  With the fit's device model the inverse
         stays in HBM (ace_model_predict); otherwise the pred_cpp ABI."""
         if self._resident(y, X, Z):
             return self._model.predict(self.parameters, X2, Z2, mean_y, std_y)
         K_xX = self.kernel_mat(X2, X, Z2, Z)["full"]
-        f = (native.kernmat_SE_symmetric_cpp if self.kernel == "SE"
-             else native.kernmat_Matern32_symmetric_cpp)
-        K_xx = f(X2, Z2, self.parameters, ctx=self.ctx)["full"]
+        K_xx = self._sym(X2, Z2)["full"]
         return native.pred_cpp(y, self.parameters[0], self.parameters[1], self.invKmatn, K_xX,
                                K_xx, mean_y, std_y, ctx=self.ctx)
 
@@ -707,9 +612,7 @@ class _KernelClass:
             return self._model.predict_marginal(self.parameters, X2, dZ2, Z2, std_y, std_Z,
                                                 calculate_ate)
         Km_xX = self.kernel_mat(X2, X, dZ2, Z)["elements"]
-        f = (native.kernmat_SE_symmetric_cpp if self.kernel == "SE"
-             else native.kernmat_Matern32_symmetric_cpp)
-        Km_xx = f(X2, dZ2, self.parameters, ctx=self.ctx)["elements"]
+        Km_xx = self._sym(X2, dZ2)["elements"]
         return native.pred_marginal_cpp(y, Z2, self.parameters[0], self.parameters[1],
                                         self.invKmatn, Km_xX, Km_xx, mean_y, std_y, std_Z,
                                         calculate_ate, ctx=self.ctx)
@@ -717,63 +620,44 @@ class _KernelClass:
     def robust_treatment(self, y, X, Z, X2, Z2, dZ2, std_y, std_Z, n_steps=5):
         """R/robust_treatment.R:83-128 on the fit's device model: Z2 is the
         binary treatment of the test points, dZ2 their derivative basis."""
-        if not self._resident(y, X, Z):
-            raise AceError("robust_treatment needs the fit's device-resident inverse "
-                           "(para_update on the same data)")
-        return self._model.robust_treatment(self.parameters, X2, dZ2, Z2, std_y, std_Z, n_steps)
+        return self._on_model("robust_treatment", y, X, Z).robust_treatment(
+            self.parameters, X2, dZ2, Z2, std_y, std_Z, n_steps)
 
     def coef_posterior(self, y, X, Z, X2):
         """The posterior of the coefficient functions at the rows of X2, on
         the fit's device model (DeviceModel.coef_posterior)."""
-        if not self._resident(y, X, Z):
-            raise AceError("coef_posterior needs the fit's device-resident inverse "
-                           "(para_update on the same data)")
-        return self._model.coef_posterior(self.parameters, X2)
+        return self._on_model("coef_posterior", y, X, Z).coef_posterior(self.parameters, X2)
 
     def predict_surface(self, y, X, Z, X2, Zb, marginal, mean_y, std_y, std_Z):
         """predict / predict_marginal on the grid of the rows of X2 and of Zb
         (the test basis, or its derivative when marginal), on the fit's device
         model (DeviceModel.predict_surface)."""
-        if not self._resident(y, X, Z):
-            raise AceError("predict_surface needs the fit's device-resident inverse "
-                           "(para_update on the same data)")
-        return self._model.predict_surface(self.parameters, X2, Zb, marginal, mean_y, std_y,
-                                           std_Z)
+        return self._on_model("predict_surface", y, X, Z).predict_surface(
+            self.parameters, X2, Zb, marginal, mean_y, std_y, std_Z)
 
     def coef_groups(self, y, X, Z, X2, G, label):
         """The group-summed posterior of the coefficient functions at the rows
         of X2, on the fit's device model (DeviceModel.coef_groups)."""
-        if not self._resident(y, X, Z):
-            raise AceError("coef_groups needs the fit's device-resident inverse "
-                           "(para_update on the same data)")
-        return self._model.coef_groups(self.parameters, X2, G, label)
+        return self._on_model("coef_groups", y, X, Z).coef_groups(self.parameters, X2, G, label)
 
     def average_response(self, y, X, Z, X2, G, label, Zb, marginal, mean_y, std_y, std_Z,
                          return_cov=False):
         """The groups' average dose-response curves at the rows of Zb, on the
         fit's device model (DeviceModel.average_response)."""
-        if not self._resident(y, X, Z):
-            raise AceError("average_response needs the fit's device-resident inverse "
-                           "(para_update on the same data)")
-        return self._model.average_response(self.parameters, X2, G, label, Zb, marginal, mean_y,
-                                            std_y, std_Z, return_cov)
+        return self._on_model("average_response", y, X, Z).average_response(
+            self.parameters, X2, G, label, Zb, marginal, mean_y, std_y, std_Z, return_cov)
 
     def predict_joint(self, y, X, Z, X2, Z2, mean_y, std_y, **kw):
         """The joint posterior at the test points on the fit's device model
         (DeviceModel.predict_joint and its keywords; Z2 the test basis, or its
         derivative with marginal=True)."""
-        if not self._resident(y, X, Z):
-            raise AceError("predict_joint needs the fit's device-resident inverse "
-                           "(para_update on the same data)")
-        return self._model.predict_joint(self.parameters, X2, Z2, mean_y, std_y, **kw)
+        return self._on_model("predict_joint", y, X, Z).predict_joint(
+            self.parameters, X2, Z2, mean_y, std_y, **kw)
 
     def cross_validate(self, y, X, Z, folds, mean_y, std_y):
         """Cross-validation from the fit's resident inverse, without a refit
         (DeviceModel.cv; folds a list of index arrays)."""
-        if not self._resident(y, X, Z):
-            raise AceError("cross_validate needs the fit's device-resident inverse "
-                           "(para_update on the same data)")
-        return self._model.cv(self.parameters, folds, mean_y, std_y)
+        return self._on_model("cross_validate", y, X, Z).cv(self.parameters, folds, mean_y, std_y)
 
     def mean_solution(self, y):
         """R/kernel_SE_R6.R:99-102 (private in the SE class)."""

@@ -13,6 +13,7 @@ import ctypes
 import numpy as np
 
 from ._lib import KIND, AceError, check, default_context, fmat, lib, ptr
+from ._marshal import ate_dicts, i32ptr, iptr, map_ci_var, pack_folds, scalar, u32ptr, vec
 
 
 def _ctx(ctx):
@@ -95,15 +96,27 @@ def _any_dev(*xs):
     return any(isinstance(x, DMat) for x in xs)
 
 
+def _mat_args(ms, ctx):
+    """The matrix arguments `ms` (None passes through) of a routine with a
+    host-buffer and a handle entry point: (True, handles, keep) if any is a
+    DMat -- the others are uploaded -- else (False, double*s, keep); `keep`
+    holds what the arguments point into until the call has returned."""
+    keep = []
+    if _any_dev(*ms):
+        return True, [None if m is None else _dmat(m, ctx, keep) for m in ms], keep
+    keep = [None if m is None else fmat(m) for m in ms]
+    return False, [ptr(f) for f in keep], keep
+
+
+def _shape(a):
+    return a.shape if isinstance(a, DMat) else np.shape(a)  # np.shape would read a DMat
+
+
 def _zmat(Z, n):
     Z = np.asarray(Z, dtype=np.float64)
     if Z.ndim == 1:
         Z = Z.reshape(n, 1)
     return np.asfortranarray(Z)
-
-
-def _theta(parameters):
-    return np.ascontiguousarray(np.ravel(parameters), dtype=np.float64)
 
 
 def _check_theta(theta, B, p, grad=False):
@@ -123,7 +136,7 @@ def _kernmat_cross(kind, X1, X2, Z1, Z2, parameters, ctx=None, elements=True, de
     Z1 = _zmat(Z1, n1)
     Z2 = _zmat(Z2, n2)
     B = Z1.shape[1] + 1
-    th = _theta(parameters)
+    th = vec(parameters)
     _check_theta(th, B, p)
     if device:
         hf, he = ctypes.c_void_p(), ctypes.c_void_p()
@@ -143,7 +156,7 @@ def _kernmat_sym(kind, X, Z, parameters, ctx=None, elements=True, device=False):
     n, p = X.shape
     Z = _zmat(Z, n)
     B = Z.shape[1] + 1
-    th = _theta(parameters)
+    th = vec(parameters)
     _check_theta(th, B, p)
     if device:
         hf, he = ctypes.c_void_p(), ctypes.c_void_p()
@@ -180,22 +193,21 @@ def kernmat_Matern32_symmetric_cpp(X, Z, parameters, ctx=None, device=False):
 def invkernel_cpp(pdmat, sigma, ctx=None):
     """src/kernel_SE_cpp.cpp:137-157.  `eigenval` holds the elimination
     pivots (sum(log(.)) == log det, the only use the reference makes of it)."""
-    sig = float(np.ravel([sigma])[0])
-    if _any_dev(pdmat):  # handle in, handle out: the inverse stays in HBM
-        n = pdmat.shape[0]
-        ev = np.empty(n)
-        h = ctypes.c_void_p()
-        check(lib().ace_invkernel_dev(_ctx(ctx), pdmat.handle, sig, ptr(ev), ctypes.byref(h)),
-              _ctx(ctx))
-        return {"eigenval": ev, "inv": DMat(h, ctx)}
-    K = fmat(pdmat)
+    sig = scalar(sigma)
+    dev = _any_dev(pdmat)
+    K = pdmat if dev else fmat(pdmat)
     n = K.shape[0]
-    if K.shape != (n, n):
+    if not dev and K.shape != (n, n):
         raise AceError("pdmat must be square")
     ev = np.empty(n)
-    inv = np.empty((n, n), order="F")
-    check(lib().ace_invkernel(_ctx(ctx), n, ptr(K), float(np.ravel([sigma])[0]), ptr(ev),
-                              ptr(inv)), _ctx(ctx))
+    if dev:  # handle in, handle out: the inverse stays in HBM
+        h = ctypes.c_void_p()
+        check(lib().ace_invkernel_dev(_ctx(ctx), K.handle, sig, ptr(ev), ctypes.byref(h)),
+              _ctx(ctx))
+        inv = DMat(h, ctx)
+    else:
+        inv = np.empty((n, n), order="F")
+        check(lib().ace_invkernel(_ctx(ctx), n, ptr(K), sig, ptr(ev), ptr(inv)), _ctx(ctx))
     return {"eigenval": ev, "inv": inv}
 
 
@@ -205,28 +217,18 @@ def _grad(kind, y, X, Z, Kfull, K, invKmatn, eigenval, parameters, stats, B, std
     Z = _zmat(Z, n)
     if Z.shape[1] + 1 != B:
         raise AceError("B != ncol(Z) + 1")
-    yv = np.ascontiguousarray(np.ravel(y), dtype=np.float64)
-    th = _theta(parameters)
+    yv = vec(y)
+    th = vec(parameters)
     _check_theta(th, B, p, grad=True)
-    dev = _any_dev(Kfull, K, invKmatn)
-    Kf = fmat(Kfull) if not dev else None
-    Kc = fmat(K) if (K is not None and not dev) else None
-    inv = fmat(invKmatn) if not dev else None
-    ev = np.ascontiguousarray(np.ravel(eigenval), dtype=np.float64)
+    ev = vec(eigenval)
     if not (isinstance(stats, np.ndarray) and stats.dtype == np.float64 and stats.size >= 2):
         raise AceError("stats must be a float64 numpy array of length 2 (mutated in place)")
     st = np.ascontiguousarray(stats)
     g = np.empty(th.shape[0])
-    if dev:
-        keep = []
-        hK = _dmat(Kfull, ctx, keep)
-        hC = _dmat(K, ctx, keep) if K is not None else None
-        hI = _dmat(invKmatn, ctx, keep)
-        check(lib().ace_grad_dev(_ctx(ctx), kind, n, p, B, ptr(yv), ptr(X), ptr(Z), hK, hC, hI,
-                                 ptr(ev), ptr(th), ptr(st), float(std_y), ptr(g)), _ctx(ctx))
-    else:
-        check(lib().ace_grad(_ctx(ctx), kind, n, p, B, ptr(yv), ptr(X), ptr(Z), ptr(Kf), ptr(Kc),
-                             ptr(inv), ptr(ev), ptr(th), ptr(st), float(std_y), ptr(g)), _ctx(ctx))
+    dev, mats, _keep = _mat_args((Kfull, K, invKmatn), ctx)
+    fn = lib().ace_grad_dev if dev else lib().ace_grad
+    check(fn(_ctx(ctx), kind, n, p, B, ptr(yv), ptr(X), ptr(Z), *mats, ptr(ev), ptr(th), ptr(st),
+             float(std_y), ptr(g)), _ctx(ctx))
     stats.flat[0:2] = st.flat[0:2]
     return g
 
@@ -246,95 +248,56 @@ def grad_Matern_cpp(y, X, Z, Kfull, K, invKmatn, eigenval, parameters, stats, B,
 
 def stats_cpp(y, Kmat, invKmatn, eigenval, mu, std_y=1.0, ctx=None):
     """src/stats_cpp.cpp:9-32"""
-    yv = np.ascontiguousarray(np.ravel(y), dtype=np.float64)
-    n = yv.shape[0]
+    yv, ev = vec(y), vec(eigenval)
     out = np.empty(2)
-    if _any_dev(Kmat, invKmatn):
-        keep = []
-        check(lib().ace_stats_dev(_ctx(ctx), n, ptr(yv), _dmat(Kmat, ctx, keep),
-                                  _dmat(invKmatn, ctx, keep),
-                                  ptr(np.ascontiguousarray(np.ravel(eigenval), dtype=np.float64)),
-                                  float(np.ravel([mu])[0]), float(std_y), ptr(out)), _ctx(ctx))
-        return out
-    check(lib().ace_stats(_ctx(ctx), n, ptr(yv), ptr(fmat(Kmat)), ptr(fmat(invKmatn)),
-                          ptr(np.ascontiguousarray(np.ravel(eigenval), dtype=np.float64)),
-                          float(np.ravel([mu])[0]), float(std_y), ptr(out)), _ctx(ctx))
+    dev, mats, _keep = _mat_args((Kmat, invKmatn), ctx)
+    fn = lib().ace_stats_dev if dev else lib().ace_stats
+    check(fn(_ctx(ctx), yv.shape[0], ptr(yv), *mats, ptr(ev), scalar(mu), float(std_y),
+             ptr(out)), _ctx(ctx))
     return out
 
 
 def mu_solution_cpp(y, invKmat, ctx=None):
     """src/utilities_cpp.cpp:6-10"""
-    yv = np.ascontiguousarray(np.ravel(y), dtype=np.float64)
+    yv = vec(y)
     out = ctypes.c_double()
-    if _any_dev(invKmat):
-        check(lib().ace_mu_solution_dev(_ctx(ctx), yv.shape[0], ptr(yv), invKmat.handle,
-                                        ctypes.cast(ctypes.pointer(out),
-                                                    ctypes.POINTER(ctypes.c_double))), _ctx(ctx))
-        return out.value
-    check(lib().ace_mu_solution(_ctx(ctx), yv.shape[0], ptr(yv), ptr(fmat(invKmat)),
-                                ctypes.cast(ctypes.pointer(out), ctypes.POINTER(ctypes.c_double))),
-          _ctx(ctx))
+    dev, mats, _keep = _mat_args((invKmat,), ctx)
+    fn = lib().ace_mu_solution_dev if dev else lib().ace_mu_solution
+    check(fn(_ctx(ctx), yv.shape[0], ptr(yv), *mats, ctypes.byref(out)), _ctx(ctx))
     return out.value
 
 
 def pred_cpp(y_X, sigma, mu, invK_XX, K_xX, K_xx, mean_y, std_y, ctx=None):
     """src/pred_cpp.cpp:8-34"""
-    yv = np.ascontiguousarray(np.ravel(y_X), dtype=np.float64)
-    if _any_dev(invK_XX, K_xX, K_xx):
-        keep = []
-        nx, nX = K_xX.shape if isinstance(K_xX, DMat) else np.shape(K_xX)
-        mp, var = np.empty(nx), np.empty(nx)
-        ci = np.empty((nx, 2), order="F")
-        check(lib().ace_pred_dev(_ctx(ctx), nX, nx, ptr(yv), float(sigma), float(mu),
-                                 _dmat(invK_XX, ctx, keep), _dmat(K_xX, ctx, keep),
-                                 _dmat(K_xx, ctx, keep), float(mean_y), float(std_y), ptr(mp),
-                                 ptr(ci), ptr(var)), _ctx(ctx))
-        return {"map": mp, "ci": ci, "var": var}
-    KxX = fmat(K_xX)
-    nx, nX = KxX.shape
-    mp = np.empty(nx)
-    ci = np.empty((nx, 2), order="F")
-    var = np.empty(nx)
-    check(lib().ace_pred(_ctx(ctx), nX, nx, ptr(yv), float(sigma), float(mu),
-                         ptr(fmat(invK_XX)), ptr(KxX), ptr(fmat(K_xx)), float(mean_y),
-                         float(std_y), ptr(mp), ptr(ci), ptr(var)), _ctx(ctx))
-    return {"map": mp, "ci": ci, "var": var}
+    yv = vec(y_X)
+    nx, nX = _shape(K_xX)
+    mp, ci, var, out = map_ci_var(nx)
+    dev, mats, _keep = _mat_args((invK_XX, K_xX, K_xx), ctx)
+    fn = lib().ace_pred_dev if dev else lib().ace_pred
+    check(fn(_ctx(ctx), nX, nx, ptr(yv), float(sigma), float(mu), *mats, float(mean_y),
+             float(std_y), ptr(mp), ptr(ci), ptr(var)), _ctx(ctx))
+    return out
 
 
 def pred_marginal_cpp(y_X, Z_x, sigma, mu, invK_XX, K_xX, K_xx, mean_y, std_y, std_Z,
                       calculate_ate, ctx=None):
     """src/pred_cpp.cpp:37-126"""
-    yv = np.ascontiguousarray(np.ravel(y_X), dtype=np.float64)
-    zx = np.ascontiguousarray(np.ravel(Z_x), dtype=np.float64) if Z_x is not None else None
+    yv = vec(y_X)
+    zx = vec(Z_x) if Z_x is not None else None
     avg = np.empty(12)
-    if _any_dev(invK_XX, K_xX, K_xx):
-        keep = []
-        nx, nX = (K_xX.shape if isinstance(K_xX, DMat) else np.shape(K_xX))[:2]
-        mp, var = np.empty(nx), np.empty(nx)
-        ci = np.empty((nx, 2), order="F")
-        check(lib().ace_pred_marginal_dev(_ctx(ctx), nX, nx, ptr(yv), ptr(zx), float(sigma),
-                                          float(mu), _dmat(invK_XX, ctx, keep),
-                                          _dmat(K_xX, ctx, keep), _dmat(K_xx, ctx, keep),
-                                          float(mean_y), float(std_y),
-                                          float(np.ravel([std_Z])[0]), 1 if calculate_ate else 0,
-                                          ptr(mp), ptr(ci), ptr(var), ptr(avg)), _ctx(ctx))
+    shape = _shape(K_xX)
+    nx, nX = shape[:2]
+    mp, ci, var, out = map_ci_var(nx)
+    dev, mats, _keep = _mat_args((invK_XX, K_xX, K_xx), ctx)
+    if dev:  # the handles carry their slice count
+        fn, dims = lib().ace_pred_marginal_dev, (nX, nx)
     else:
-        cX = fmat(K_xX)
-        cx = fmat(K_xx)
-        nx, nX, B = cX.shape
-        mp = np.empty(nx)
-        ci = np.empty((nx, 2), order="F")
-        var = np.empty(nx)
-        check(lib().ace_pred_marginal(_ctx(ctx), nX, nx, B, ptr(yv), ptr(zx), float(sigma),
-                                      float(mu), ptr(fmat(invK_XX)), ptr(cX), ptr(cx),
-                                      float(mean_y), float(std_y), float(np.ravel([std_Z])[0]),
-                                      1 if calculate_ate else 0, ptr(mp), ptr(ci), ptr(var),
-                                      ptr(avg)), _ctx(ctx))
-    out = {"map": mp, "ci": ci, "var": var}
+        fn, dims = lib().ace_pred_marginal, (nX, nx, shape[2])
+    check(fn(_ctx(ctx), *dims, ptr(yv), ptr(zx), float(sigma), float(mu), *mats, float(mean_y),
+             float(std_y), scalar(std_Z), 1 if calculate_ate else 0, ptr(mp), ptr(ci), ptr(var),
+             ptr(avg)), _ctx(ctx))
     if calculate_ate:
-        for j, key in enumerate(("ate", "att", "atu")):
-            a = avg[4 * j:4 * j + 4]
-            out[key] = {"map": a[0], "ci": np.array([a[1], a[2]]), "var": a[3]}
+        out.update(ate_dicts(avg))
     return out
 
 
@@ -346,27 +309,29 @@ def _inplace(a, name):
     return a
 
 
+def _optimizer(entry, hyper, state, grad, para):
+    """One optimizer step: `state` ({name: array}) and para in place."""
+    g = vec(grad)
+    return bool(getattr(lib(), entry)(g.shape[0], *map(float, hyper),
+                                      *[ptr(_inplace(a, k)) for k, a in state.items()], ptr(g),
+                                      ptr(_inplace(para, "para"))))
+
+
 def Nesterov_cpp(learn_rate, momentum, nu, grad, para):
     """src/optimizer_cpp.cpp:8-20 (nu, para in place)."""
-    g = np.ascontiguousarray(np.ravel(grad), dtype=np.float64)
-    return bool(lib().ace_nesterov(g.shape[0], float(learn_rate), float(momentum),
-                                   ptr(_inplace(nu, "nu")), ptr(g), ptr(_inplace(para, "para"))))
+    return _optimizer("ace_nesterov", (learn_rate, momentum), {"nu": nu}, grad, para)
 
 
 def Nadam_cpp(iter, learn_rate, beta1, beta2, eps, m, v, grad, para):  # noqa: A002
     """src/optimizer_cpp.cpp:23-42 (m, v, para in place)."""
-    g = np.ascontiguousarray(np.ravel(grad), dtype=np.float64)
-    return bool(lib().ace_nadam(g.shape[0], float(iter), float(learn_rate), float(beta1),
-                                float(beta2), float(eps), ptr(_inplace(m, "m")),
-                                ptr(_inplace(v, "v")), ptr(g), ptr(_inplace(para, "para"))))
+    return _optimizer("ace_nadam", (iter, learn_rate, beta1, beta2, eps), {"m": m, "v": v}, grad,
+                      para)
 
 
 def Adam_cpp(iter, learn_rate, beta1, beta2, eps, m, v, grad, para):  # noqa: A002
     """src/optimizer_cpp.cpp:45-63 (m, v, para in place)."""
-    g = np.ascontiguousarray(np.ravel(grad), dtype=np.float64)
-    return bool(lib().ace_adam(g.shape[0], float(iter), float(learn_rate), float(beta1),
-                               float(beta2), float(eps), ptr(_inplace(m, "m")),
-                               ptr(_inplace(v, "v")), ptr(g), ptr(_inplace(para, "para"))))
+    return _optimizer("ace_adam", (iter, learn_rate, beta1, beta2, eps), {"m": m, "v": v}, grad,
+                      para)
 
 
 def norm_clip_cpp(flag, grads, max_length):
@@ -376,8 +341,7 @@ def norm_clip_cpp(flag, grads, max_length):
 
 
 def _ncs(fn, x, knots):
-    xv = np.ascontiguousarray(np.ravel(x), dtype=np.float64)
-    kv = np.ascontiguousarray(np.ravel(knots), dtype=np.float64)
+    xv, kv = vec(x), vec(knots)
     nk = np.unique(kv).shape[0]
     out = np.empty((xv.shape[0], nk), order="F")
     ncols = ctypes.c_int64()
@@ -423,11 +387,10 @@ def robust_levels(var, n_steps):
     """ace_robust_levels (R/robust_treatment.R:83-84, 94): the type-7 quantile
     thresholds of var at seq(0, 1, 1 / n_steps) and, per point, the first step
     at which it is retained.  Returns (thresholds (n_steps + 1), level (int32))."""
-    v = np.ascontiguousarray(np.ravel(var), dtype=np.float64)
+    v = vec(var)
     thr = np.empty(max(int(n_steps), 0) + 1)
     level = np.empty(v.size, dtype=np.int32)
-    check(lib().ace_robust_levels(v.size, ptr(v), int(n_steps), ptr(thr),
-                                  level.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    check(lib().ace_robust_levels(v.size, ptr(v), int(n_steps), ptr(thr), i32ptr(level)))
     return thr, level
 
 
@@ -444,11 +407,14 @@ def zero_pattern_order(Z):
     perm = np.empty(n, dtype=np.int64)
     mask = np.zeros((n + 63) // 64, dtype=np.uint32)
     has = np.zeros(1, dtype=np.int32)
-    check(lib().ace_zero_pattern_order(n, ZS, ptr(Zf) if ZS else None,
-                                       perm.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                       mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                                       has.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    check(lib().ace_zero_pattern_order(n, ZS, ptr(Zf) if ZS else None, iptr(perm), u32ptr(mask),
+                                       i32ptr(has)))
     return perm, (mask if has[0] else None)
+
+
+def _weights(W, B):
+    """nz x B column-major weight rows of W, read column-major whatever its shape."""
+    return np.asfortranarray(np.asarray(W, dtype=np.float64).reshape((-1, B), order="F"))
 
 
 def coef_contract(mean, cov, W, offset=0.0, scale=1.0, shift=0.0, noise=0.0):
@@ -463,16 +429,12 @@ def coef_contract(mean, cov, W, offset=0.0, scale=1.0, shift=0.0, noise=0.0):
         raise AceError("mean must be nx x B")
     nx, B = mf.shape
     cf = np.asfortranarray(np.asarray(cov, dtype=np.float64).reshape((nx, B, B), order="F"))
-    Wf = np.asfortranarray(np.asarray(W, dtype=np.float64).reshape((-1, B), order="F"))
-    nz = Wf.shape[0]
-    mp = np.empty((nx, nz), order="F")
-    var = np.empty((nx, nz), order="F")
-    ci = np.empty((nx, nz, 2), order="F")
-    check(lib().ace_coef_contract(nx, B, nz, ptr(mf), cf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                  ptr(Wf), float(offset), float(scale), float(shift), float(noise),
-                                  ptr(mp), ci.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+    Wf = _weights(W, B)
+    mp, ci, var, out = map_ci_var(nx, Wf.shape[0])
+    check(lib().ace_coef_contract(nx, B, Wf.shape[0], ptr(mf), ptr(cf), ptr(Wf), float(offset),
+                                  float(scale), float(shift), float(noise), ptr(mp), ptr(ci),
                                   ptr(var)))
-    return {"map": mp, "ci": ci, "var": var}
+    return out
 
 
 def coef_group_contract(gmean, gcov, gcount, W, offset=0.0, scale=1.0, shift=0.0,
@@ -493,18 +455,14 @@ def coef_group_contract(gmean, gcov, gcount, W, offset=0.0, scale=1.0, shift=0.0
     cnt = np.ascontiguousarray(np.ravel(gcount), dtype=np.int64)
     if cnt.size != G:
         raise AceError("gcount must have one entry per group")
-    Wf = np.asfortranarray(np.asarray(W, dtype=np.float64).reshape((-1, B), order="F"))
+    Wf = _weights(W, B)
     nz = Wf.shape[0]
-    mp = np.empty((G, nz), order="F")
-    var = np.empty((G, nz), order="F")
-    ci = np.empty((G, nz, 2), order="F")
-    cov = np.empty((G, nz, nz), order="F") if return_cov else None
+    mp, ci, var, out = map_ci_var(G, nz)
+    if return_cov:
+        out["cov"] = np.empty((G, nz, nz), order="F")
     check(lib().ace_coef_group_contract(G, B, nz, ptr(mf), ptr(cf), iptr(cnt), ptr(Wf),
                                         float(offset), float(scale), float(shift), ptr(mp),
-                                        ptr(ci), ptr(var), ptr(cov)))
-    out = {"map": mp, "ci": ci, "var": var}
-    if return_cov:
-        out["cov"] = cov
+                                        ptr(ci), ptr(var), ptr(out.get("cov"))))
     return out
 
 
@@ -527,22 +485,6 @@ def potrf_lower(A, jitter=0.0, lda=None):
     return L, int(info.value)
 
 
-def pack_folds(folds):
-    """(nf, off, idx) of a list of integer index arrays: the packed fold list
-    of ace_model_cv / ace_cv_from_inverse (fold f = idx[off[f]:off[f + 1]])."""
-    fl = [np.ascontiguousarray(np.ravel(f), dtype=np.int64) for f in folds]
-    if not fl:
-        raise AceError("folds must hold at least one fold")
-    off = np.zeros(len(fl) + 1, dtype=np.int64)
-    np.cumsum([f.size for f in fl], out=off[1:])
-    idx = np.concatenate(fl) if off[-1] else np.zeros(1, dtype=np.int64)
-    return len(fl), off, np.ascontiguousarray(idx, dtype=np.int64)
-
-
-def iptr(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-
-
 def cv_from_inverse(P, alpha, folds, ctx=None):
     """ace_cv_from_inverse: for every fold F (a list of integer arrays) of a
     symmetric P (n x n, the lower triangle is read) and alpha (n):
@@ -555,7 +497,7 @@ def cv_from_inverse(P, alpha, folds, ctx=None):
     if Pf.ndim != 2 or Pf.shape[0] != Pf.shape[1]:
         raise AceError("P must be a square matrix")
     n = Pf.shape[0]
-    al = np.ascontiguousarray(np.ravel(alpha), dtype=np.float64)
+    al = vec(alpha)
     if al.size != n:
         raise AceError("alpha must have n entries")
     nf, off, idx = pack_folds(folds)
@@ -565,6 +507,5 @@ def cv_from_inverse(P, alpha, folds, ctx=None):
     st = np.zeros(nf, dtype=np.int32)
     h = _ctx(ctx)
     check(lib().ace_cv_from_inverse(h, n, ptr(Pf), n, ptr(al), nf, iptr(off), iptr(idx), ptr(r),
-                                    ptr(v), ptr(ld), ptr(mh),
-                                    st.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), h)
+                                    ptr(v), ptr(ld), ptr(mh), i32ptr(st)), h)
     return {"resid": r[:tot], "var": v[:tot], "logdet": ld, "mahal": mh, "status": st, "off": off}

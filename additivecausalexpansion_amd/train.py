@@ -6,12 +6,15 @@ path underneath is the device-resident para_update (model.py).
 from __future__ import annotations
 
 import math
+from collections import namedtuple
+from contextlib import contextmanager
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import native
 from ._lib import AceError
-from .model import KernelClass_Matern32_R6, KernelClass_SE_R6, set_optimizer
+from .model import BatchModel, KernelClass_Matern32_R6, KernelClass_SE_R6, set_optimizer
 
 
 # --------------------------------------------------------------------------
@@ -128,6 +131,33 @@ class AceFit(dict):
     """The S3 "ace" list (R/main_ace.R:242-253)."""
 
 
+def _make_fit(myKernel, q, settings, bias_corrected, init_length_scale, convergence, stats):
+    """The fit of one prepared dataset q (_prepare) from its trained kernel
+    object; settings = (optimizer, learning_rate, momentum, beta1, beta2),
+    stats the 2 x iterations table of the iterations that ran."""
+    return AceFit(Kernel=myKernel, Basis=q.basis,
+                  OptimSettings=dict(zip(("optim", "lr", "momentum", "beta1", "beta2"), settings)),
+                  moments=q.moments,
+                  train_data={"y": q.y, "X": q.X, "Z": q.Z, "Zbinary": q.isbinary},
+                  train_stats={"RIC_bias_corrected": bias_corrected,
+                               "init.length_scale": init_length_scale,
+                               "convergence": convergence, "final_evidence": stats[1, -1],
+                               "stats": stats})
+
+
+def _view(fit):
+    """What the queries on a fit read from it, unpacked once."""
+    td, mom = fit["train_data"], fit["moments"]
+    px, pz = td["X"].shape[1], td["Z"].shape[1]
+    return SimpleNamespace(K=fit["Kernel"], basis=fit["Basis"], Btr=fit["Basis"].B, y=td["y"],
+                           X=td["X"], Z=td["Z"], mom=mom, px=px, pz=pz, mean_y=mom[0, 0],
+                           std_y=mom[0, 1], std_Z=mom[1 + px:1 + px + pz, 1],
+                           binary=bool(np.all(td["Zbinary"])))
+
+
+_Prepared = namedtuple("_Prepared", "y X Z px moments isbinary basis theta0")
+
+
 def _prepare(y, X, Z, pi, basis, n_knots, init_sigma, init_length_scale, verbose):
     """ace.train's host preprocessing (R/main_ace.R:146-211): normalisation,
     the basis and the initial parameters of one dataset."""
@@ -164,7 +194,7 @@ def _prepare(y, X, Z, pi, basis, n_knots, init_sigma, init_length_scale, verbose
     myBasis.trainbasis(Zi, n_knots, verbose)
     theta0 = set_initial_parameters(px, myBasis.dim(), n, yv, Xi, Zi, init_sigma,
                                     init_length_scale, verbose)
-    return yv, Xi, Zi, px, moments, isbinary, myBasis, theta0
+    return _Prepared(yv, Xi, Zi, px, moments, isbinary, myBasis, theta0)
 
 
 def ace_train(y, X, Z, pi=None, kernel="SE", basis="linear", n_knots=1, optimizer="Nadam",
@@ -176,10 +206,10 @@ def ace_train(y, X, Z, pi=None, kernel="SE", basis="linear", n_knots=1, optimize
     through Python; same arithmetic, so the same trajectory)."""
     if norm_clip is None:
         norm_clip = optimizer in ("Adam", "Nadam")  # R/main_ace.R:143 (Q5)
-    yv, Xi, Zi, px, moments, isbinary, myBasis, theta0 = _prepare(
-        y, X, Z, pi, basis, n_knots, init_sigma, init_length_scale, verbose)
+    q = _prepare(y, X, Z, pi, basis, n_knots, init_sigma, init_length_scale, verbose)
+    yv, Xi, myBasis = q.y, q.X, q.basis
     Kc = KernelClass_Matern32_R6 if kernel == "Matern32" else KernelClass_SE_R6
-    myKernel = Kc(px, myBasis.dim(), theta0, moments[0, 1], verbose, ctx=ctx)
+    myKernel = Kc(q.px, myBasis.dim(), q.theta0, q.moments[0, 1], verbose, ctx=ctx)
     myOptimizer = set_optimizer(optimizer, myKernel, learning_rate, momentum, beta1, beta2,
                                 norm_clip, clip_at)
     if native_loop:
@@ -191,46 +221,65 @@ def ace_train(y, X, Z, pi=None, kernel="SE", basis="linear", n_knots=1, optimize
         myKernel._mark_kernel(Xi, myBasis.B)
         myKernel._inv = None
         myKernel._inv_from_model = True
-        if verbose:
-            print("Final training log Evidence: ", stats[1, it + 1])
-        stats = stats[:, 2:it + 2]
-        return AceFit(Kernel=myKernel, Basis=myBasis,
-                      OptimSettings={"optim": optimizer, "lr": learning_rate, "momentum": momentum,
-                                     "beta1": beta1, "beta2": beta2},
-                      moments=moments,
-                      train_data={"y": yv, "X": Xi, "Z": Zi, "Zbinary": isbinary},
-                      train_stats={"RIC_bias_corrected": pi is not None,
-                                   "init.length_scale": init_length_scale,
-                                   "convergence": convergence, "final_evidence": stats[1, -1],
-                                   "stats": stats})
-    stats = np.zeros((2, maxiter + 2))
-    it = 0
-    for it in range(1, maxiter + 1):
-        stats[:, it] = myKernel.para_update(it, yv, Xi, myBasis.B, myOptimizer, verbose=verbose)
-        change = abs(stats[1, it] - stats[1, it - 1])
-        if change < tol and it > 3:
-            if verbose:
-                print(f"Stopped: change smaller than tolerance after {it} iterations")
-            break
-    convergence = it < maxiter
-    stats[:, it + 1] = myKernel.get_train_stats(yv, Xi, myBasis.B)
-    if verbose and not convergence:
-        print("WARNING NO CONVERGENCE - Optimization stopped: maximum iterations reached")
+    else:
+        stats = np.zeros((2, maxiter + 2))
+        it = 0
+        for it in range(1, maxiter + 1):
+            stats[:, it] = myKernel.para_update(it, yv, Xi, myBasis.B, myOptimizer,
+                                                verbose=verbose)
+            change = abs(stats[1, it] - stats[1, it - 1])
+            if change < tol and it > 3:
+                if verbose:
+                    print(f"Stopped: change smaller than tolerance after {it} iterations")
+                break
+        convergence = it < maxiter
+        stats[:, it + 1] = myKernel.get_train_stats(yv, Xi, myBasis.B)
+        if verbose and not convergence:
+            print("WARNING NO CONVERGENCE - Optimization stopped: maximum iterations reached")
     if verbose:
         print("Final training log Evidence: ", stats[1, it + 1])
-    stats = stats[:, 2:it + 2]
-    return AceFit(Kernel=myKernel, Basis=myBasis,
-                  OptimSettings={"optim": optimizer, "lr": learning_rate, "momentum": momentum,
-                                 "beta1": beta1, "beta2": beta2},
-                  moments=moments,
-                  train_data={"y": yv, "X": Xi, "Z": Zi, "Zbinary": isbinary},
-                  train_stats={"RIC_bias_corrected": pi is not None,
-                               "init.length_scale": init_length_scale,
-                               "convergence": convergence, "final_evidence": stats[1, -1],
-                               "stats": stats})
+    return _make_fit(myKernel, q, (optimizer, learning_rate, momentum, beta1, beta2),
+                     pi is not None, init_length_scale, convergence, stats[:, 2:it + 2])
 
 
 BATCH_NMAX = 512  # rows of the largest model the batched engine takes
+
+
+def _check_nmax(noun, j, n, instead):
+    if n > BATCH_NMAX:
+        raise AceError(f"{noun} {j}: n = {n} > {BATCH_NMAX}, the batched engine's limit (use "
+                       f"{instead})")
+
+
+def _batch(noun, items, ctx, instead=None):
+    """The batch of `items`, one (kernel, p, B, y, X, basis, std_y) per model.
+    Checked at once, before a GPU is touched: the models agree in kernel, p
+    and B and, with `instead` (the unbatched function to name), fit in the
+    engine; `noun` names them in the errors.  Returns a context manager:
+    entering it gives a BatchModel that holds every model's training data,
+    leaving it closes that."""
+    k0, p0, B0 = items[0][:3]
+    for j, (k, p, B, y, *_) in enumerate(items):
+        if k != k0:
+            raise AceError(f"{noun} {j} uses kernel {k}, {noun} 0 {k0}: the {noun}s of a "
+                           "batch must use one kernel")
+        if p != p0:
+            raise AceError(f"{noun} {j} has p = {p}, {noun} 0 has p = {p0}")
+        if B != B0:
+            raise AceError(f"{noun} {j} has basis dimension B = {B}, {noun} 0 has B = {B0}")
+        if instead:
+            _check_nmax(noun, j, y.size, instead)
+
+    @contextmanager
+    def opened():
+        bm = BatchModel(k0, len(items), max(it[3].size for it in items), p0, B0, ctx=ctx)
+        try:
+            for j, (_k, _p, _B, y, X, basis, std_y) in enumerate(items):
+                bm.set_data(j, y, X, basis, std_y)
+            yield bm
+        finally:
+            bm.close()
+    return opened()
 
 
 def ace_train_batch(ys, Xs, Zs, pis=None, kernel="SE", basis="linear", n_knots=1,
@@ -248,7 +297,6 @@ def ace_train_batch(ys, Xs, Zs, pis=None, kernel="SE", basis="linear", n_knots=1
     gradient becomes non-finite stops alone: nonfinite="raise" then raises
     AceError naming the models (ace_train's behaviour), nonfinite="none" puts
     None in their places and returns the other fits."""
-    from .model import BatchModel
     M = len(ys)
     if M < 1 or len(Xs) != M or len(Zs) != M or (pis is not None and len(pis) != M):
         raise AceError("ys, Xs, Zs (and pis) must be sequences of one length M >= 1")
@@ -267,29 +315,17 @@ def ace_train_batch(ys, Xs, Zs, pis=None, kernel="SE", basis="linear", n_knots=1
         return v[j] if isinstance(v, (list, tuple, np.ndarray)) else v
 
     for j in range(M):
-        if np.size(ys[j]) > BATCH_NMAX:
-            raise AceError(f"dataset {j}: n = {np.size(ys[j])} > {BATCH_NMAX}, the batched "
-                           "engine's limit (use ace_train)")
+        _check_nmax("dataset", j, np.size(ys[j]), "ace_train")
     for v in (init_length_scale, init_sigma):
         if isinstance(v, (list, tuple, np.ndarray)) and len(v) != M:
             raise AceError("init_length_scale / init_sigma sequences must have length M")
     prep = [_prepare(ys[j], Xs[j], Zs[j], None if pis is None else pis[j], basis, n_knots,
                      per_model(init_sigma, j), per_model(init_length_scale, j), verbose)
             for j in range(M)]
-    px, B = prep[0][3], prep[0][6].dim()
-    for j, q in enumerate(prep):
-        if q[3] != px:
-            raise AceError(f"dataset {j} has p = {q[3]}, dataset 0 has p = {px}")
-        if q[6].dim() != B:
-            raise AceError(f"dataset {j} has basis dimension B = {q[6].dim()}, dataset 0 has "
-                           f"B = {B}")
-    nmax = max(q[0].size for q in prep)
-    bm = BatchModel(kernel, M, nmax, px, B, ctx=ctx)
-    try:
-        theta = np.empty((2 + B * (px + 1), M), order="F")
-        for j, q in enumerate(prep):
-            bm.set_data(j, q[0], q[1], q[6].B, q[4][0, 1])
-            theta[:, j] = q[7]
+    px, B = prep[0].px, prep[0].basis.dim()
+    with _batch("dataset", [(kernel, q.px, q.basis.dim(), q.y, q.X, q.basis.B, q.moments[0, 1])
+                            for q in prep], ctx) as bm:
+        theta = np.asfortranarray(np.column_stack([q.theta0 for q in prep]))
         stats, its, conv, status = bm.train(theta, optimizer, learning_rate, momentum, beta1,
                                             beta2, norm_clip, clip_at, maxiter, tol)
         bad = [j for j in range(M) if status[j] != 0]
@@ -297,89 +333,76 @@ def ace_train_batch(ys, Xs, Zs, pis=None, kernel="SE", basis="linear", n_knots=1
             raise AceError(f"ACE_ERR_NONFINITE: models {bad}: Some gradients are not finite, "
                            "NaN, or NA. Often this is due to too large learning rates.")
         invs = [None if j in bad else bm.inverse(j) for j in range(M)]
-    finally:
-        bm.close()
     Kc = KernelClass_Matern32_R6 if kernel == "Matern32" else KernelClass_SE_R6
     fits = []
-    for j, (yv, Xi, Zi, _, moments, isbinary, myBasis, _t0) in enumerate(prep):
+    for j, q in enumerate(prep):
         if invs[j] is None:
             fits.append(None)
             continue
-        myKernel = Kc(px, B, theta[:, j].copy(), moments[0, 1], False, ctx=ctx)
-        myKernel._mark_kernel(Xi, myBasis.B)
+        myKernel = Kc(px, B, theta[:, j].copy(), q.moments[0, 1], False, ctx=ctx)
+        myKernel._mark_kernel(q.X, q.basis.B)
         myKernel._inv = invs[j]
         myKernel._inv_from_model = False
-        it = int(its[j])
-        st = stats[:, 2:it + 2, j]
-        fits.append(AceFit(
-            Kernel=myKernel, Basis=myBasis,
-            OptimSettings={"optim": optimizer, "lr": learning_rate, "momentum": momentum,
-                           "beta1": beta1, "beta2": beta2},
-            moments=moments,
-            train_data={"y": yv, "X": Xi, "Z": Zi, "Zbinary": isbinary},
-            train_stats={"RIC_bias_corrected": pis is not None and pis[j] is not None,
-                         "init.length_scale": per_model(init_length_scale, j),
-                         "convergence": bool(conv[j]), "final_evidence": st[1, -1],
-                         "stats": st}))
+        fits.append(_make_fit(myKernel, q, (optimizer, learning_rate, momentum, beta1, beta2),
+                              pis is not None and pis[j] is not None,
+                              per_model(init_length_scale, j), bool(conv[j]),
+                              stats[:, 2:int(its[j]) + 2, j]))
     return fits
 
 
-def _test_points(obj, newX, newZ, normalize):
+def _new_X(v, newX, Zn=None, normalize=True, check=True):
+    """Raw test rows newX as the fit (view v) takes them: a column-major
+    copy, its width checked against the training X, normalised with the fit's
+    moments -- together with the treatment column Zn(nx) of the same points
+    (a function of their number; normalised with them), else on its own.
+    Returns (Xn, Zn)."""
+    Xn = np.array(newX, dtype=np.float64, order="F", copy=True)
+    if check and (Xn.ndim != 2 or Xn.shape[1] != v.px):
+        raise AceError("Dimension mismatch of X with newX")
+    Zn = np.zeros((Xn.shape[0], v.pz), order="F") if Zn is None else Zn(Xn.shape[0])
+    if normalize:
+        native.normalize_test(Xn, Zn, v.mom)
+    return Xn, Zn
+
+
+def _test_points(v, newX, newZ, normalize):
     """predict.ace's argument handling (R/predict.ace.R:30-80): the normalised
-    test points (Xn, Zn) of one fit for the four newX / newZ cases."""
-    X = obj["train_data"]["X"]
-    px = X.shape[1]
-    pz = obj["train_data"]["Z"].shape[1]
-    mom = obj["moments"]
+    test points (Xn, Zn) of one fit (view v) for the four newX / newZ cases."""
+    def level(n):
+        return np.full((n, 1), float(np.ravel(newZ)[0]), order="F")
+
     if newX is None and newZ is None:
-        Xn = X
-        Zn = obj["train_data"]["Z"]
+        Xn, Zn = v.X, v.Z
     elif newX is None:
-        Xn = np.array(X, order="F", copy=True)
+        Xn = np.array(v.X, order="F", copy=True)
         if np.size(newZ) == 1:
-            Zn = np.full((Xn.shape[0], 1), float(np.ravel(newZ)[0]), order="F")
+            Zn = level(Xn.shape[0])
         else:
             Zn = np.asfortranarray(np.ravel(newZ).astype(np.float64).reshape(-1, 1))
             if normalize:
-                native.normalize_test(Xn, Zn, mom)
-            Xn = X
+                native.normalize_test(Xn, Zn, v.mom)
+            Xn = v.X
     elif newZ is None:
-        Xn = np.array(newX, dtype=np.float64, order="F", copy=True)
+        Xn, _ = _new_X(v, newX, None, normalize, check=False)
         Zn = np.zeros((Xn.shape[0], 1), order="F")
-        if normalize:
-            native.normalize_test(Xn, Zn, mom)
-        Zn = np.zeros((Xn.shape[0], 1), order="F")
+    elif np.size(newZ) == 1:
+        Xn, Zn = _new_X(v, newX, level, normalize)
     else:
-        Xn = np.array(newX, dtype=np.float64, order="F", copy=True)
-        if Xn.shape[1] != px:
-            raise AceError("Dimension mismatch of X with newX")
-        if np.size(newZ) == 1:
-            Zn = np.full((Xn.shape[0], 1), float(np.ravel(newZ)[0]), order="F")
-        else:
-            Zn = np.array(newZ, dtype=np.float64, order="F", copy=True).reshape(-1, pz, order="F")
-        if normalize:
-            native.normalize_test(Xn, Zn, mom)
+        Xn, Zn = _new_X(v, newX, lambda n: np.array(newZ, dtype=np.float64, order="F", copy=True)
+                        .reshape(-1, v.pz, order="F"), normalize)
     return Xn, Zn
 
 
 def predict_ace(obj, newX=None, newZ=None, marginal=False, return_average_treatments=False,
                 normalize=True):
     """R/predict.ace.R:30-99 (predict.ace)."""
-    isbinary = obj["train_data"]["Zbinary"]
-    X = obj["train_data"]["X"]
-    px = X.shape[1]
-    pz = obj["train_data"]["Z"].shape[1]
-    mom = obj["moments"]
-    Xn, Zn = _test_points(obj, newX, newZ, normalize)
-    K = obj["Kernel"]
-    y = obj["train_data"]["y"]
-    Btr = obj["Basis"].B
+    v = _view(obj)
+    Xn, Zn = _test_points(v, newX, newZ, normalize)
+    tb = v.basis.testbasis(Zn)
     if not marginal:
-        return K.predict(y, X, Btr, Xn, obj["Basis"].testbasis(Zn)["B"], mom[0, 0], mom[0, 1])
-    tb = obj["Basis"].testbasis(Zn)
-    return K.predict_marginal(y, X, Btr, Xn, tb["B"], tb["dB"], mom[0, 0], mom[0, 1],
-                              mom[1 + px:1 + px + pz, 1],
-                              bool(np.all(isbinary)) and return_average_treatments)
+        return v.K.predict(v.y, v.X, v.Btr, Xn, tb["B"], v.mean_y, v.std_y)
+    return v.K.predict_marginal(v.y, v.X, v.Btr, Xn, tb["B"], tb["dB"], v.mean_y, v.std_y,
+                                v.std_Z, v.binary and return_average_treatments)
 
 
 def posterior_draws(fit, newX=None, newZ=None, marginal=False, n_draws=1000, seed=0, xi=None,
@@ -397,29 +420,22 @@ def posterior_draws(fit, newX=None, newZ=None, marginal=False, n_draws=1000, see
     return_average_treatments with a binary treatment adds "ate", "att",
     "atu" (S each): every draw's mean over all, the treated and the untreated
     test points (NaN for an empty group).  return_cov adds "cov"."""
-    X = fit["train_data"]["X"]
-    px = X.shape[1]
-    pz = fit["train_data"]["Z"].shape[1]
-    mom = fit["moments"]
-    Xn, Zn = _test_points(fit, newX, newZ, True)
-    K = fit["Kernel"]
-    y = fit["train_data"]["y"]
-    Btr = fit["Basis"].B
-    tb = fit["Basis"].testbasis(Zn)
+    v = _view(fit)
+    Xn, Zn = _test_points(v, newX, newZ, True)
+    tb = v.basis.testbasis(Zn)
     nx = Xn.shape[0]
     if xi is None:
         xi = np.random.default_rng(seed).standard_normal((nx, int(n_draws)))
     xi = np.asfortranarray(np.asarray(xi, dtype=np.float64).reshape(nx, -1))
-    std_Z = mom[1 + px:1 + px + pz, 1]
     if jitter is None:
         jitter = 0.0
         if marginal:
-            v = K.predict_marginal(y, X, Btr, Xn, tb["B"], tb["dB"], mom[0, 0], mom[0, 1], std_Z,
-                                   False)["var"]
-            jitter = 1e-10 * float(np.mean(v))
-    r = K.predict_joint(y, X, Btr, Xn, tb["dB"] if marginal else tb["B"], mom[0, 0], mom[0, 1],
-                        marginal=marginal, std_Z=std_Z, noise=True, jitter=jitter, xi=xi,
-                        return_cov=return_cov)
+            var = v.K.predict_marginal(v.y, v.X, v.Btr, Xn, tb["B"], tb["dB"], v.mean_y, v.std_y,
+                                       v.std_Z, False)["var"]
+            jitter = 1e-10 * float(np.mean(var))
+    r = v.K.predict_joint(v.y, v.X, v.Btr, Xn, tb["dB"] if marginal else tb["B"], v.mean_y,
+                          v.std_y, marginal=marginal, std_Z=v.std_Z, noise=True, jitter=jitter,
+                          xi=xi, return_cov=return_cov)
     if r["info"] > 0:
         raise AceError(
             f"posterior_draws: the posterior covariance is not positive definite at pivot "
@@ -429,7 +445,7 @@ def posterior_draws(fit, newX=None, newZ=None, marginal=False, n_draws=1000, see
     out = {"map": r["map"], "draws": r["draws"]}
     if return_cov:
         out["cov"] = r["cov"]
-    if return_average_treatments and bool(np.all(fit["train_data"]["Zbinary"])):
+    if return_average_treatments and v.binary:
         D = r["draws"]
         zx = np.ravel(tb["B"]).astype(np.float64)
         with np.errstate(invalid="ignore", divide="ignore"):
@@ -456,10 +472,8 @@ def cross_validate(fit, folds=10, seed=0, groups=None):
     "size", "status"; and "elpd" = sum lpd, "rmse", "coverage" (the share of
     held-out y inside ci).  The inverse is the last para_update's, theta_{T-1}'s,
     while mu is the final one (Q6): the model predict_ace uses in-sample."""
-    K = fit["Kernel"]
-    y = fit["train_data"]["y"]
-    X = fit["train_data"]["X"]
-    mom = fit["moments"]
+    K, mom = fit["Kernel"], fit["moments"]  # Z is not read: no _view
+    y, X = fit["train_data"]["y"], fit["train_data"]["X"]
     n = X.shape[0]
     if groups is not None:
         g = np.ravel(np.asarray(groups))
@@ -499,9 +513,9 @@ def cross_validate(fit, folds=10, seed=0, groups=None):
     if np.unique(idx).size != idx.size:  # overlapping folds: packed fold after fold
         out.update(packed, off=r["off"])
         return out
-    for k, v in packed.items():
-        full = np.full((n,) + v.shape[1:], np.nan)
-        full[idx] = v
+    for k, a in packed.items():
+        full = np.full((n,) + a.shape[1:], np.nan)
+        full[idx] = a
         out[k] = full
     fid = np.full(n, -1, dtype=np.int64)
     fid[idx] = np.repeat(np.arange(len(fl)), [f.size for f in fl])
@@ -519,7 +533,6 @@ def predict_ace_batch(fits, newXs=None, newZs=None, marginal=False,
     included).  The fits may come from ace_train_batch or from ace_train; each
     one's inverse of its last para_update (Q6) is installed next to its
     training data, and the kernels are evaluated at its final parameters."""
-    from .model import BatchModel
     fits = list(fits)
     M = len(fits)
     if M < 1:
@@ -532,50 +545,28 @@ def predict_ace_batch(fits, newXs=None, newZs=None, marginal=False,
     for name, v in (("newXs", newXs), ("newZs", newZs)):
         if v is not None and (not isinstance(v, (list, tuple)) or len(v) != M):
             raise AceError(f"{name} must be None or a sequence of length M = {M}")
-    K0 = fits[0]["Kernel"]
-    for j, f in enumerate(fits):
-        K = f["Kernel"]
-        if K.kernel != K0.kernel:
-            raise AceError(f"fit {j} uses kernel {K.kernel}, fit 0 {K0.kernel}: the fits of a "
-                           "batch must use one kernel")
-        if K.p != K0.p:
-            raise AceError(f"fit {j} has p = {K.p}, fit 0 has p = {K0.p}")
-        if K.B != K0.B:
-            raise AceError(f"fit {j} has basis dimension B = {K.B}, fit 0 has B = {K0.B}")
-        n = f["train_data"]["y"].size
-        if n > BATCH_NMAX:
-            raise AceError(f"fit {j}: n = {n} > {BATCH_NMAX}, the batched engine's limit (use "
-                           "predict_ace)")
-    px, B = K0.p, K0.B
-    pts = [_test_points(f, None if newXs is None else newXs[j],
+    vs = [_view(f) for f in fits]
+    batch = _batch("fit", [(v.K.kernel, v.K.p, v.K.B, v.y, v.X, v.Btr, v.std_y) for v in vs],
+                   vs[0].K.ctx, instead="predict_ace")
+    pts = [_test_points(v, None if newXs is None else newXs[j],
                         None if newZs is None else newZs[j], normalize)
-           for j, f in enumerate(fits)]
-    tbs = [f["Basis"].testbasis(Zn) for f, (_, Zn) in zip(fits, pts)]
-    theta = np.asfortranarray(np.column_stack([f["Kernel"].parameters for f in fits]))
-    nmax = max(f["train_data"]["y"].size for f in fits)
-    bm = BatchModel(K0.kernel, M, nmax, px, B, ctx=K0.ctx)
-    try:
-        for j, f in enumerate(fits):
-            bm.set_data(j, f["train_data"]["y"], f["train_data"]["X"], f["Basis"].B,
-                        f["moments"][0, 1])
-            bm.set_inverse(j, f["Kernel"].invKmatn)
+           for j, v in enumerate(vs)]
+    tbs = [v.basis.testbasis(Zn) for v, (_, Zn) in zip(vs, pts)]
+    theta = np.asfortranarray(np.column_stack([v.K.parameters for v in vs]))
+    with batch as bm:
+        for j, v in enumerate(vs):
+            bm.set_inverse(j, v.K.invKmatn)
         Xns = [q[0] for q in pts]
         if not marginal:
-            return bm.predict(theta, Xns, [t["B"] for t in tbs],
-                              [f["moments"][0, 0] for f in fits],
-                              [f["moments"][0, 1] for f in fits])
-        ate = [bool(np.all(f["train_data"]["Zbinary"])) and return_average_treatments
-               for f in fits]
+            return bm.predict(theta, Xns, [t["B"] for t in tbs], [v.mean_y for v in vs],
+                              [v.std_y for v in vs])
+        ate = [v.binary and return_average_treatments for v in vs]
         if any(ate) != all(ate):
             raise AceError("return_average_treatments needs a binary treatment in every fit of "
                            "the batch, or in none")
-        pz = fits[0]["train_data"]["Z"].shape[1]
-        return bm.predict_marginal(
-            theta, Xns, [t["dB"] for t in tbs], [t["B"] for t in tbs],
-            [f["moments"][0, 1] for f in fits],
-            [np.ravel(f["moments"][1 + px:1 + px + pz, 1])[0] for f in fits], ate[0])
-    finally:
-        bm.close()
+        return bm.predict_marginal(theta, Xns, [t["dB"] for t in tbs], [t["B"] for t in tbs],
+                                   [v.std_y for v in vs], [np.ravel(v.std_Z)[0] for v in vs],
+                                   ate[0])
 
 
 def robust_treatment(obj, newX=None, n_steps=5):
@@ -590,24 +581,16 @@ def robust_treatment(obj, newX=None, n_steps=5):
     return value), "ate": its ate_results table (map, ci0, ci1, var, retained;
     in-sample also treated, untreated), "thresholds"} and in-sample "att" /
     "atu" (map, ci0, ci1, var; NaN rows where the group is empty)."""
-    if not np.all(obj["train_data"]["Zbinary"]):
+    v = _view(obj)
+    if not v.binary:
         raise AceError("Average treatment effect requires binary treatment indicator.")
-    X = obj["train_data"]["X"]
-    px = X.shape[1]
-    pz = obj["train_data"]["Z"].shape[1]
-    mom = obj["moments"]
     insample = newX is None
     if insample:
-        Xn, Zn = X, obj["train_data"]["Z"]
+        Xn, Zn = v.X, v.Z
     else:
-        Xn = np.array(newX, dtype=np.float64, order="F", copy=True)
-        if Xn.ndim != 2 or Xn.shape[1] != px:
-            raise AceError("Dimension mismatch of X with newX")
-        Zn = np.full((Xn.shape[0], 1), 1.0, order="F")
-        native.normalize_test(Xn, Zn, mom)
-    tb = obj["Basis"].testbasis(Zn)
-    r = obj["Kernel"].robust_treatment(obj["train_data"]["y"], X, obj["Basis"].B, Xn, tb["B"],
-                                       tb["dB"], mom[0, 1], mom[1 + px:1 + px + pz, 1], n_steps)
+        Xn, Zn = _new_X(v, newX, lambda n: np.full((n, 1), 1.0, order="F"))  # newZ = 1
+    tb = v.basis.testbasis(Zn)
+    r = v.K.robust_treatment(v.y, v.X, v.Btr, Xn, tb["B"], tb["dB"], v.std_y, v.std_Z, n_steps)
     T = int(n_steps) + 1
     avg, counts = r["avg"], r["counts"]
     out = {"idx": r["level"][:, None] <= np.arange(T)[None, :], "thresholds": r["thresholds"]}
@@ -626,25 +609,15 @@ def robust_treatment(obj, newX=None, n_steps=5):
     return out
 
 
-def _surface_points(obj, newX, newZ=None):
+def _surface_points(v, newX, newZ=None):
     """newX (nx raw rows) and newZ (nz raw treatment values) normalised with
     the fit's moments as predict_ace normalises them, each on its own."""
-    X = obj["train_data"]["X"]
-    px = X.shape[1]
-    pz = obj["train_data"]["Z"].shape[1]
-    mom = obj["moments"]
-    if newX is None:
-        Xn = X
-    else:
-        Xn = np.array(newX, dtype=np.float64, order="F", copy=True)
-        if Xn.ndim != 2 or Xn.shape[1] != px:
-            raise AceError("Dimension mismatch of X with newX")
-        native.normalize_test(Xn, np.zeros((Xn.shape[0], pz), order="F"), mom)
+    Xn = v.X if newX is None else _new_X(v, newX)[0]
     if newZ is None:
         return Xn, None
-    Zn = np.array(np.ravel(newZ), dtype=np.float64).reshape(-1, pz, order="F")
+    Zn = np.array(np.ravel(newZ), dtype=np.float64).reshape(-1, v.pz, order="F")
     Zn = np.asfortranarray(Zn)
-    native.normalize_test(np.zeros((Zn.shape[0], px), order="F"), Zn, mom)
+    native.normalize_test(np.zeros((Zn.shape[0], v.px), order="F"), Zn, v.mom)
     return Xn, Zn
 
 
@@ -652,9 +625,9 @@ def coef_posterior(obj, newX=None):
     """Posterior of the coefficient functions g_b(x) of the fit at the rows
     of newX (raw units; None: the training points): {"mean": (nx, B), "cov":
     (nx, B, B)} in normalised-y units, without mu and the noise term."""
-    Xn, _ = _surface_points(obj, newX)
-    return obj["Kernel"].coef_posterior(obj["train_data"]["y"], obj["train_data"]["X"],
-                                        obj["Basis"].B, Xn)
+    v = _view(obj)
+    Xn, _ = _surface_points(v, newX)
+    return v.K.coef_posterior(v.y, v.X, v.Btr, Xn)
 
 
 def response_surface(obj, newX, newZ, marginal=False):
@@ -663,15 +636,11 @@ def response_surface(obj, newX, newZ, marginal=False):
     curves and surfaces (R/plot_ace.R:146-154, 288, 350-351), from one
     coefficient pass: {"map": (nx, nz), "ci": (nx, nz, 2), "var": (nx, nz)};
     raveled in Fortran order the first two axes are expand.grid(X, Z)."""
-    X = obj["train_data"]["X"]
-    px = X.shape[1]
-    pz = obj["train_data"]["Z"].shape[1]
-    mom = obj["moments"]
-    Xn, Zn = _surface_points(obj, newX, newZ)
-    tb = obj["Basis"].testbasis(Zn)
-    return obj["Kernel"].predict_surface(obj["train_data"]["y"], X, obj["Basis"].B, Xn,
-                                         tb["dB"] if marginal else tb["B"], marginal, mom[0, 0],
-                                         mom[0, 1], mom[1 + px:1 + px + pz, 1])
+    v = _view(obj)
+    Xn, Zn = _surface_points(v, newX, newZ)
+    tb = v.basis.testbasis(Zn)
+    return v.K.predict_surface(v.y, v.X, v.Btr, Xn, tb["dB"] if marginal else tb["B"], marginal,
+                               v.mean_y, v.std_y, v.std_Z)
 
 
 def _group_labels(nx, groups):
@@ -696,10 +665,10 @@ def average_coef_posterior(obj, newX=None, groups=None):
     "mean": (G, B), "cov": (G, B, G, B)}, averages in normalised-y units,
     without mu and the noise term; cov[g, :, h, :] is the covariance between
     two groups' averages, so contrasts of groups need no second pass."""
-    Xn, _ = _surface_points(obj, newX)
+    v = _view(obj)
+    Xn, _ = _surface_points(v, newX)
     names, lab = _group_labels(Xn.shape[0], groups)
-    r = obj["Kernel"].coef_groups(obj["train_data"]["y"], obj["train_data"]["X"], obj["Basis"].B,
-                                  Xn, names.size, lab)
+    r = v.K.coef_groups(v.y, v.X, v.Btr, Xn, names.size, lab)
     cnt = r["gcount"].astype(np.float64)
     return {"groups": names, "count": r["gcount"], "mean": r["gmean"] / cnt[:, None],
             "cov": r["gcov"] / (cnt[:, None, None, None] * cnt[None, None, :, None])}
@@ -715,17 +684,13 @@ def average_response(obj, newZ, newX=None, groups=None, marginal=False, return_c
     (G, nz, 2)} and, with return_cov, "cov" (G, nz, nz) for simultaneous
     bands over z.  No noise term: the posterior of the averaged mean
     function, not of averaged observations."""
-    X = obj["train_data"]["X"]
-    px = X.shape[1]
-    pz = obj["train_data"]["Z"].shape[1]
-    mom = obj["moments"]
-    Xn, Zn = _surface_points(obj, newX, newZ)
+    v = _view(obj)
+    Xn, Zn = _surface_points(v, newX, newZ)
     names, lab = _group_labels(Xn.shape[0], groups)
-    tb = obj["Basis"].testbasis(Zn)
-    r = obj["Kernel"].average_response(obj["train_data"]["y"], X, obj["Basis"].B, Xn, names.size,
-                                       lab, tb["dB"] if marginal else tb["B"], marginal,
-                                       mom[0, 0], mom[0, 1], mom[1 + px:1 + px + pz, 1],
-                                       return_cov)
+    tb = v.basis.testbasis(Zn)
+    r = v.K.average_response(v.y, v.X, v.Btr, Xn, names.size, lab,
+                             tb["dB"] if marginal else tb["B"], marginal, v.mean_y, v.std_y,
+                             v.std_Z, return_cov)
     r["groups"] = names
     r["count"] = np.bincount(lab, minlength=names.size).astype(np.int64)
     return r
